@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — edges/s per Gauss-Newton iteration on the BASELINE.json workload.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3_100k|c2_10k|c5_1m] [--precision 64]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3_100k|c2_10k|c5_1m] [--precision 64] [--full] [--dump-outputs DIR]
   N > 1, either way: `python bench.py --gpus N ...` starts its own N ranks (a child `python -m torch.distributed.run --nnodes=1
   --nproc-per-node N --master-addr 127.0.0.1 ...` of this script, started BEFORE this process makes any GPU call; the parent
   never touches the GPU), or the same command line under an external `torch.distributed.run` (RANK / WORLD_SIZE in the
@@ -23,9 +23,19 @@ explicit level-0 matrix; --implicit-cycle shards and all-reduces them too), the 
 `--request-parallel` instead gives every rank its OWN graph of the named configuration (what a multi-GPU
 graph_optimizer does with independent connections; no data-path collective, "scaling": "weak").
 
-Extra objects on the JSON line: `roofline` (the kernel with the largest time share: algorithmic bytes / hipEvent time
-measured here; plus SURVEY 8d's byte model for the whole step and for one PCG iteration) and `cpu_baseline` (the CPU twin
-of the same math on the host cores, and the reference's dense algorithm at config 1; rank 0, N = 1 only).
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; nothing else.  --full adds what
+is measured beside the headline figure.  After the timed region: `roofline` (the kernel with the largest time share:
+algorithmic bytes / hipEvent time measured here; plus SURVEY 8d's byte model for the whole step and for one PCG iteration),
+`iters_to_chi2_tol` (the 50-iteration convergence runs; --no-conv skips them), `cpu_baseline` (the CPU twin of the same math
+on the host cores, and the reference's dense algorithm at config 1; rank 0, N = 1 only; --no-cpu skips it) and
+`request_parallel` (the leg beside a sharded run; --no-request-parallel skips it).  Before the warm-up, once the graph is set:
+`allreduce_us` (sharded or --force-collective runs: the solver's three all-reduce sizes timed on its communicator).
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed, as a caller of tsgo_optimize receives it, in
+DIR/<name>.npy (float64): `vertices` (every vertex after the step, [n, 3]; the pose and landmark states of a sharded run gathered
+from their owners; above 1.9 M vertices a fixed seeded sample of 1.9 M rows, listed in `vertex_rows`), `chi2` (the chi^2 of
+the step's linearisation) and `delta_norm` (||delta|| of its solve).  Request-parallel runs write rank 0's graph.  The inputs are
+seeded: the same arguments give the same graph on every run.
 """
 import argparse
 import json
@@ -294,7 +304,42 @@ def timed_steps(opt, barrier, n_edges):
         ms["linearize"] += r["ms_linearize"]; ms["solve"] += r["ms_solve"]; ms["update"] += r["ms_update"]; ms_setup = r["ms_setup"]; graph_replay = graph_replay or r["graph_replay"]
     barrier()
     dt = time.perf_counter() - t0
-    return {"dt": dt, "chi2": chi2, "cg": cg, "ms": {k: v / ARGS.steps for k, v in ms.items()}, "ms_setup": ms_setup, "graph_replay": graph_replay}
+    return {"dt": dt, "chi2": chi2, "cg": cg, "ms": {k: v / ARGS.steps for k, v in ms.items()}, "ms_setup": ms_setup, "graph_replay": graph_replay,
+            "last": r}
+
+
+DUMP_MAX_ROWS = 1_900_000        # vertices 24 B + vertex_rows 8 B per kept row: 60.8 MB in all; larger graphs (config 5) are sampled
+
+
+def merge_shards(v_in, every):
+    """The vertices of a sharded run from every rank's HipOptimizer.vertices(): a shard returns the replicated poses and its OWN
+    landmarks and keeps the input everywhere else, so a row's value is the one that differs from the input (the owner's; identical
+    to the input where nothing moved).  every[0] (rank 0) is applied last: its poses are the ones every rank holds."""
+    v = v_in.copy()
+    for o in reversed(every):
+        moved = (o != v_in).any(axis=1)
+        v[moved] = o[moved]
+    return v
+
+
+def dump_outputs(out_dir, opt, last, g, rank, gather=None):
+    """--dump-outputs: the last timed step's result as tsgo_optimize's caller receives it (module docstring).  `gather` (sharded
+    runs, called on every rank): this rank's vertices -> every rank's, in rank order; rank 0 merges them and writes."""
+    v = opt.vertices()
+    if gather is not None:
+        every = gather(v)
+        if rank != 0:
+            return
+        v = merge_shards(g.v_pos, every)
+    elif rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"vertices": v, "chi2": np.array([last["chi2_last"]]), "delta_norm": np.array([last["delta_norm"]])}
+    if len(v) > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(len(v), DUMP_MAX_ROWS, replace=False))
+        out["vertices"], out["vertex_rows"] = v[rows], rows.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def main():
@@ -367,7 +412,7 @@ def main():
         torch.cuda.synchronize()
 
     allreduce_us = None
-    if shard or (ARGS.force_collective and world == 1):
+    if ARGS.full and (shard or (ARGS.force_collective and world == 1)):
         # what each of the solver's collectives costs on THIS fabric (every rank calls alike): after a sharded product, after a linearisation,
         # after the level-0 blocks of a hierarchy build (that one is f32 in the solver; timed here in the handle's precision at the same BYTES)
         word = 8 if ARGS.precision == 64 else 4
@@ -392,11 +437,20 @@ def main():
             dist.all_reduce(e, op=dist.ReduceOp.SUM)
             n_edges = int(e.item())
     timed_cg = cg[ARGS.warmup:]
+    n_cg = float(np.mean(timed_cg)) if timed_cg else 0.0
+    if ARGS.dump_outputs:
+        with watch.phase("--dump-outputs", ARGS.phase_timeout if shard else None):
+            def gather(v):
+                mine = torch.from_numpy(v).cuda()
+                every = [torch.empty_like(mine) for _ in range(world)]
+                dist.all_gather(every, mine)
+                return [e.cpu().numpy() for e in every]
+            dump_outputs(ARGS.dump_outputs, opt, run["last"], g, rank, gather if shard else None)
 
     # The other multi-GPU mode beside it, same K / W: every rank its OWN graph of the configuration on its own handle, no data-path
     # collective (what a multi-GPU graph_optimizer does with independent connections): "request_parallel" in the line.
     req_par = None
-    if shard and not ARGS.no_request_parallel:
+    if ARGS.full and shard and not ARGS.no_request_parallel:
         with watch.phase("request-parallel leg"):
             g_own = synth.make_config(ARGS.workload, seed=rank)
             opt_own = make_opt(0, 1, False)
@@ -415,9 +469,8 @@ def main():
     out = None
     # Probes after the timed region.  In a sharded run every probe that linearises or iterates contains collectives, so
     # EVERY rank runs them (rank 0 alone would wait for the others forever); request-parallel ranks are independent.
-    if rank == 0 or shard:
-        n_cg = float(np.mean(timed_cg)) if timed_cg else 0.0
-        amg = ARGS.precond == "amg"
+    amg = ARGS.precond == "amg"
+    if ARGS.full and (rank == 0 or shard):
         # In situ: one PCG iteration launched eagerly with a hipEvent before every kernel, on the engine's stream, averaged over 20
         # iterations (tsgo_profile_iteration) — every kernel in the cache state the solve leaves it in.  An event between two
         # kernels costs a little itself: the sum of the marks against the same iteration timed without them gives that cost per
@@ -490,15 +543,8 @@ def main():
                 conv["other_configs"] = other
                 opt.set_graph(g)
     if rank == 0:
-        dom = max(shares, key=lambda k: shares[k]["us_per_step"])
-        us, nbytes = shares[dom]["us_in_situ"], shares[dom]["algorithmic_bytes_per_launch"]
-        achieved = nbytes / (us * 1e-6) / 1e9
-        s = 8 if ARGS.precision == 64 else 4
         Eo, El = int((g.e_type == 0).sum()), int((g.e_type == 1).sum())
-        b_lin, b_cg, b_upd = survey_bytes(g.n_poses, g.n_landmarks, Eo, El, s)
-        b_gn = b_lin + n_cg * b_cg + b_upd
         ms_step = 1e3 * dt / ARGS.steps
-        traffic = pmc_traffic(dom, ARGS.workload, ARGS.precision)
         out = {
             "metric": "edges/sec per GN iter", "value": n_edges * ARGS.steps / dt, "unit": "edges/s",
             "n_gpus": world, "steps": ARGS.steps, "warmup": ARGS.warmup, "ms_per_step": ms_step,
@@ -522,34 +568,42 @@ def main():
             "chi2_first_last": [chi2[0], chi2[-1]],
             "ms_per_step_device": {"linearize": ms_lin / ARGS.steps, "solve": ms_solve / ARGS.steps, "update": ms_upd / ARGS.steps},
             "ms_setup_once_per_graph": ms_setup,
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": (PMC_TRAFFIC + " (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE passes of this same command, committed; NOT measured in this run)") if traffic is not None else None,
-                         "us_per_launch": us, "algorithmic_bytes_per_launch": nbytes,
-                         "us_per_launch_rocprof_stats": shares[dom].get("us_rocprof_stats"), "rocprof_stats_source": ROCPROF_STATS,
-                         "kernel_chosen_by": "largest in-situ time per step, grouped by kernel symbol as rocprofv3 groups them (all levels / call sites of one instantiation together)",
-                         "timing": "hipEvent before every launch of 20 eagerly launched PCG iterations on the engine's stream (tsgo_profile_iteration), minus the per-launch cost of the events themselves (%.2f us: sum of the marks vs the same iteration without them); algorithmic bytes = average over the symbol's launches in one iteration" % overhead,
-                         "event_overhead_us_per_launch": overhead,
-                         "kernels": shares,
-                         "iteration_in_launch_order": [{"kernel": e["name"], "where": e["where"], "us_in_situ_raw": e["us"], "algorithmic_bytes": e["bytes"]} for e in prof],
-                         # SURVEY 8d's own byte model, with the measured PCG iteration count: what a perfect implementation of the
-                         # reference's sparse-equivalent algorithm would have to move, against what this run took
-                         "step": {"algorithmic_bytes": b_gn, "B_lin": b_lin, "B_cg": b_cg, "B_upd": b_upd, "N_cg": n_cg, "ms": ms_step,
-                                  "achieved": b_gn / (ms_step * 1e-3) / 1e9, "frac": b_gn / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                         "pcg_iteration": {"algorithmic_bytes": b_cg, "us": us_pcg, "achieved": b_cg / (us_pcg * 1e-6) / 1e9,
-                                           "frac": b_cg / (us_pcg * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                                           "note": "the byte model prices ONE block-SpMV + vector passes; a multigrid-preconditioned iteration runs three level-0 products and the coarse levels"},
-                         "us_per_pcg_iteration": us_pcg,
-                         "latency_model": {"us_per_pcg_iteration": model_iter, "floor_us_per_launch": 3.7, "stream_GBps": 6000.0,
-                                           "launches_per_pcg_iteration": len(prof),
-                                           "note": "sum over the iteration's launches of (3.7 us of dependent round trips + memory-side bytes / 6 TB/s); kernels[*].us_latency_model per symbol"},
-                         "ms_solve_outside_iterations": ms_solve / ARGS.steps - n_cg * us_pcg * 1e-3,
-                         "us_multigrid_numeric_setup": us_setup},
         }
-        if conv is not None:
-            out["iters_to_chi2_tol"] = conv
-        if world == 1 and not ARGS.no_cpu:
-            out["cpu_baseline"] = cpu_baseline(g, ARGS.cpu_threads or min(16, len(os.sched_getaffinity(0))))
+        if ARGS.full:
+            dom = max(shares, key=lambda k: shares[k]["us_per_step"])
+            us, nbytes = shares[dom]["us_in_situ"], shares[dom]["algorithmic_bytes_per_launch"]
+            achieved = nbytes / (us * 1e-6) / 1e9
+            s = 8 if ARGS.precision == 64 else 4
+            b_lin, b_cg, b_upd = survey_bytes(g.n_poses, g.n_landmarks, Eo, El, s)
+            b_gn = b_lin + n_cg * b_cg + b_upd
+            traffic = pmc_traffic(dom, ARGS.workload, ARGS.precision)
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                               "traffic_source": (PMC_TRAFFIC + " (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE passes of this same command, committed; NOT measured in this run)") if traffic is not None else None,
+                               "us_per_launch": us, "algorithmic_bytes_per_launch": nbytes,
+                               "us_per_launch_rocprof_stats": shares[dom].get("us_rocprof_stats"), "rocprof_stats_source": ROCPROF_STATS,
+                               "kernel_chosen_by": "largest in-situ time per step, grouped by kernel symbol as rocprofv3 groups them (all levels / call sites of one instantiation together)",
+                               "timing": "hipEvent before every launch of 20 eagerly launched PCG iterations on the engine's stream (tsgo_profile_iteration), minus the per-launch cost of the events themselves (%.2f us: sum of the marks vs the same iteration without them); algorithmic bytes = average over the symbol's launches in one iteration" % overhead,
+                               "event_overhead_us_per_launch": overhead,
+                               "kernels": shares,
+                               "iteration_in_launch_order": [{"kernel": e["name"], "where": e["where"], "us_in_situ_raw": e["us"], "algorithmic_bytes": e["bytes"]} for e in prof],
+                               # SURVEY 8d's own byte model, with the measured PCG iteration count: what a perfect implementation of the
+                               # reference's sparse-equivalent algorithm would have to move, against what this run took
+                               "step": {"algorithmic_bytes": b_gn, "B_lin": b_lin, "B_cg": b_cg, "B_upd": b_upd, "N_cg": n_cg, "ms": ms_step,
+                                        "achieved": b_gn / (ms_step * 1e-3) / 1e9, "frac": b_gn / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
+                               "pcg_iteration": {"algorithmic_bytes": b_cg, "us": us_pcg, "achieved": b_cg / (us_pcg * 1e-6) / 1e9,
+                                                 "frac": b_cg / (us_pcg * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                                                 "note": "the byte model prices ONE block-SpMV + vector passes; a multigrid-preconditioned iteration runs three level-0 products and the coarse levels"},
+                               "us_per_pcg_iteration": us_pcg,
+                               "latency_model": {"us_per_pcg_iteration": model_iter, "floor_us_per_launch": 3.7, "stream_GBps": 6000.0,
+                                                 "launches_per_pcg_iteration": len(prof),
+                                                 "note": "sum over the iteration's launches of (3.7 us of dependent round trips + memory-side bytes / 6 TB/s); kernels[*].us_latency_model per symbol"},
+                               "ms_solve_outside_iterations": ms_solve / ARGS.steps - n_cg * us_pcg * 1e-3,
+                               "us_multigrid_numeric_setup": us_setup}
+            if conv is not None:
+                out["iters_to_chi2_tol"] = conv
+            if world == 1 and not ARGS.no_cpu:
+                out["cpu_baseline"] = cpu_baseline(g, ARGS.cpu_threads or min(16, len(os.sched_getaffinity(0))))
     probes_watch.__exit__(None, None, None)
     opt.close()
     if world > 1:
@@ -592,6 +646,11 @@ if __name__ == "__main__":
                     help="N > 1 without a launcher: seconds before the parent kills the ranks it started")
     ap.add_argument("--dry-run-cpu", dest="dry_run_cpu", action="store_true",
                     help="rehearsal of the N-rank launch path without GPUs: gloo + the CPU twin (tests/bench_dry_run.py); prints a line marked dry_run, not a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline figure, after the timed region: roofline, convergence runs, CPU baseline, "
+                         "all-reduce timings, the request-parallel leg (module docstring)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu", dest="no_cpu", action="store_true")
     ap.add_argument("--no-conv", dest="no_conv", action="store_true", help="skip the 50-iteration convergence run")
     ap.add_argument("--cpu-threads", dest="cpu_threads", type=int, default=0)

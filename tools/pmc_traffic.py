@@ -1,5 +1,5 @@
 """HBM-side traffic per kernel launch from rocprofv3 PMC counters (GPU box): two separate --pmc passes (FETCH_SIZE,
-WRITE_SIZE — they do not fit one pass, MI355X_MICROARCH.md) of `bench.py --steps 2 --warmup 1 --no-cpu --no-conv`,
+WRITE_SIZE — the two counters do not fit one --pmc pass on gfx950) of `bench.py --steps 2 --warmup 1 --full --no-cpu --no-conv`,
 per-dispatch median, gfx950 correction FETCH_SIZE x2 (calibrated on the streaming k_cg_update in round 1).
 Writes a text digest and the JSON bench.py reads for roofline.traffic.
 
@@ -11,7 +11,7 @@ root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 out_dir, tag = os.path.abspath(sys.argv[1]), sys.argv[2]          # rocprofv3 runs from /tmp: relative paths would land there
 os.makedirs(out_dir, exist_ok=True)
 workload = sys.argv[3] if len(sys.argv) > 3 else "c3_100k"
-cmd = ["python3", os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu", "--no-conv", "--workload", workload]
+cmd = ["python3", os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-conv", "--workload", workload]
 os.environ.setdefault("TMPDIR", "/tmp")
 
 
