@@ -88,10 +88,10 @@
         if (l == 0 && explicit0) { if (int rc = dalloc(&D.Apm, (size_t)D.nnzA * kCyWordsF32)) return rc; }
         if (l > 0) {
             if (int rc = dalloc(&D.Apm, (size_t)D.nnzA * kCyWordsF32)) return rc;
-            if (int rc = dalloc(&D.r, (size_t)D.n * 3)) return rc;
-            if (int rc = dalloc(&D.z, (size_t)D.n * 3)) return rc;
-            if (int rc = dalloc(&D.res, (size_t)D.n * 3)) return rc;
-            if (int rc = dalloc(&D.z2, (size_t)D.n * 3)) return rc;
+            if (int rc = valloc(&D.r, (size_t)D.n * 3)) return rc;
+            if (int rc = valloc(&D.z, (size_t)D.n * 3)) return rc;
+            if (int rc = valloc(&D.res, (size_t)D.n * 3)) return rc;
+            if (int rc = valloc(&D.z2, (size_t)D.n * 3)) return rc;
         }
         return 0;
     }
@@ -258,8 +258,8 @@
         if (nb_last * 3 > kDenseMax) return set_error(-2, "tsgo_set_graph: coarsest multigrid level too large");
         if (int rc = dalloc(&A_last, (size_t)nnz_last * 9)) return rc;
         if (int rc = dalloc(&inv_last, (size_t)nb_last * 3 * nb_last * 3)) return rc;
-        if (int rc = dalloc(&r_last, (size_t)nb_last * 3)) return rc;
-        if (int rc = dalloc(&z_last, (size_t)nb_last * 3)) return rc;
+        if (int rc = valloc(&r_last, (size_t)nb_last * 3)) return rc;
+        if (int rc = valloc(&z_last, (size_t)nb_last * 3)) return rc;
         if (int rc = dalloc(&rzpart, (size_t)nbP)) return rc;
         if (int rc = dalloc(&fold_part, (size_t)2 * kFoldOut)) return rc;
         if (int rc = dalloc(&omega_dev, 16)) return rc;
@@ -311,14 +311,14 @@
             if (int rc = dalloc(&tail_Ef, n3 * nd)) return rc;
             if (int rc = dalloc(&tail_Etf, n3 * nd)) return rc;
             if (int rc = dalloc(&tail_Gf, n3 * nd)) return rc;
-            if (int rc = dalloc(&tail_t, nd)) return rc;
+            if (int rc = valloc(&tail_t, nd)) return rc;
         }
         return 0;
     }
     int n_upper0 = -1; int *mirror0 = nullptr, *upper0 = nullptr, *lower0 = nullptr;      // level 0: blocks on / above the diagonal, and the mirror of every block below it
     bool bottom_dense = false, tail2 = false;
     T *bot_S = nullptr, *bot_B = nullptr, *bot_P = nullptr, *bot_E = nullptr, *bot_F = nullptr; float* bot_Bf = nullptr;
-    T* tail_t = nullptr; float *tail_Ef = nullptr, *tail_Etf = nullptr, *tail_Gf = nullptr;
+    void* tail_t = nullptr; float *tail_Ef = nullptr, *tail_Etf = nullptr, *tail_Gf = nullptr;
     // B = W + S W + E C E^T of the last explicit level (after k_dense_inverse, and again whenever the level's damping changes), then
     // E = P - W (A P) and G = E B of the level above it
     int launch_bottom_setup() {

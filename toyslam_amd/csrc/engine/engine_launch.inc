@@ -21,8 +21,12 @@
     double od_slots_live() { if (od_live < 0) { od_live = 0; for (uint32_t e : pr.odom.edge) od_live += e != kNoEdge; } return od_live; }
     double bytes_schur_lm(bool low) const { const double s = low ? 4 : sizeof(T), v = sizeof(T); return (double)pr.n_lm_edges * (4 + 4 * s) + pr.P * 5.0 * v + pr.L * 5.0 * v; }
     double bytes_schur_pose(bool low) { const double s = low ? 4 : sizeof(T), v = sizeof(T); return (double)pr.n_lm_edges * (4 + 4 * s) + pr.L * 2.0 * v + pr.P * 14.0 * v + od_slots_live() * (4 + 6 * v); }
-    double bytes_sweep(const DevLevel<T>& L) const { return (double)L.nnzA * (4.0 * cyw() + 4) + (double)L.n * (3 * 3 * sizeof(T) + 9 * sizeof(H) + 4); }
-    double bytes_transfer(const DevLevel<T>& L, int vecs_fine) const { return (double)L.nnzP * (4.0 * cyw() + 4) + (double)L.n * 3 * sizeof(T) * vecs_fine + (double)L.n_agg * (3 * sizeof(T) + 4); }
+    // (fine vectors of level 0 are T, every other cycle vector cv_bytes())
+    double bytes_sweep(const DevLevel<T>& L) const { return (double)L.nnzA * (4.0 * cyw() + 4) + (double)L.n * (3 * 3 * cv_bytes() + 9 * sizeof(H) + 4); }
+    double bytes_transfer(const DevLevel<T>& L, int vecs_fine, bool fine_is_l0 = false) const {
+        return (double)L.nnzP * (4.0 * cyw() + 4) + (double)L.n * 3 * (fine_is_l0 ? sizeof(T) : cv_bytes()) * vecs_fine + (double)L.n_agg * (3 * cv_bytes() + 4);
+    }
+    const char* vname() const { return cv_bytes() == 8 ? "double" : "float"; }      // the cycle vectors' type in the kernel names
 
     // ---- launches --------------------------------------------------------------------------------
     // damping of the current linearisation (rules = 1, graph_optimizer.py:24-43; 0 under the cpu/eigen rules) and the step the update takes
@@ -151,24 +155,24 @@
         }                                                                                                                \
     } while (0)
     // a block-row sweep over the cycle-format copy of a level's matrix (MODE 0 residual, 1 smoothing sweep), f32 or packed half
-#define SWEEP_INST16(L_) k_bcsr_residual<T, L_, SWEEP_MODE, 1, 1>
-#define SWEEP_INST32(L_) k_bcsr_residual<T, L_, SWEEP_MODE, 1, 0>
-#define RESTRICT_INST16(L_) k_restrict<T, L_, SWEEP_MODE, 1>
-#define RESTRICT_INST32(L_) k_restrict<T, L_, SWEEP_MODE, 0>
-#define PROLONG_INST16(L_) k_prolong_add<T, L_, 1>
-#define PROLONG_INST32(L_) k_prolong_add<T, L_, 0>
+#define SWEEP_INST16(L_) k_bcsr_residual<T, L_, SWEEP_MODE, 1, 1, V>
+#define SWEEP_INST32(L_) k_bcsr_residual<T, L_, SWEEP_MODE, 1, 0, V>
+#define RESTRICT_INST16(L_) k_restrict<T, L_, SWEEP_MODE, 1, VI, VO>
+#define RESTRICT_INST32(L_) k_restrict<T, L_, SWEEP_MODE, 0, VI, VO>
+#define PROLONG_INST16(L_) k_prolong_add<T, L_, 1, VE, VZ>
+#define PROLONG_INST32(L_) k_prolong_add<T, L_, 0, VE, VZ>
 #define APPLY_INST16(L_) k_bcsr_apply<T, L_, 1>
 #define APPLY_INST32(L_) k_bcsr_apply<T, L_, 0>
-    template <int SWEEP_MODE> void launch_sweep(int lpr, DevLevel<T>& L, const T* rhs, const T* cur, T* out, const T* omega, const CgState<T>* s) {
+    template <int SWEEP_MODE, typename V> void launch_sweep(int lpr, DevLevel<T>& L, const V* rhs, const V* cur, V* out, const T* omega, const CgState<T>* s) {
         if (cy16) LAUNCH_LPR_(lpr, SWEEP_INST16, L.n, L.n, L.A_ptr, L.A_col, (const void*)L.Apm, rhs, cur, (const H*)L.Dinv, out, omega, s);
         else LAUNCH_LPR_(lpr, SWEEP_INST32, L.n, L.n, L.A_ptr, L.A_col, (const void*)L.Apm, rhs, cur, (const H*)L.Dinv, out, omega, s);
     }
-    template <int SWEEP_MODE> void launch_restrict(int lpr, DevLevel<T>& L, const T* va, const T* vb, T* rc, const H* dinv_next, T* z_next, const T* omega, const CgState<T>* s) {
+    template <int SWEEP_MODE, typename VI, typename VO> void launch_restrict(int lpr, DevLevel<T>& L, const VI* va, const VI* vb, VO* rc, const H* dinv_next, VO* z_next, const T* omega, const CgState<T>* s) {
         if (cy16) LAUNCH_LPR_(lpr, RESTRICT_INST16, L.n_agg, L.n_agg, L.R_ptr, L.R_col, (const uint32_t*)L.Rpm, va, vb, rc, dinv_next, z_next, omega, s);
         else LAUNCH_LPR_(lpr, RESTRICT_INST32, L.n_agg, L.n_agg, L.R_ptr, L.R_col, (const uint32_t*)L.Rpm, va, vb, rc, dinv_next, z_next, omega, s);
     }
-    void launch_prolong(DevLevel<T>& L, const T* e, T* z, int zs, const CgState<T>* s, size_t level) {
-        PF(bytes_transfer(L, 2), lvl("prolong into", level).c_str(), "k_prolong_add<%s, %d, %d>", tname(), lanes_for((double)L.nnzP / std::max(1, L.n)), cy16 ? 1 : 0);
+    template <typename VE, typename VZ> void launch_prolong(DevLevel<T>& L, const VE* e, VZ* z, int zs, const CgState<T>* s, size_t level) {
+        PF(bytes_transfer(L, 2, level == 0), lvl("prolong into", level).c_str(), "k_prolong_add<%s, %d, %d, %s, %s>", tname(), lanes_for((double)L.nnzP / std::max(1, L.n)), cy16 ? 1 : 0, vname(), level == 0 ? tname() : vname());
         const int lpr = lanes_for((double)L.nnzP / std::max(1, L.n));
         float* z32 = (level == 0 && low_cycle && !explicit0) ? zc32 : (float*)nullptr;      // level 0 prolongs into the pose records: keep their f32 copy current
         if (cy16) LAUNCH_LPR_(lpr, PROLONG_INST16, L.n, L.n, L.P_ptr, L.P_col, (const uint32_t*)L.Ppm, e, z, zs, s, z32);
@@ -182,7 +186,7 @@
         const size_t nl = lv.size();
         for (size_t l = 0; l < nl; ++l) {
             DevLevel<T>& L = lv[l];
-            T* a = l == 0 ? pw_a : L.res; T* b = l == 0 ? pw_b : L.z2;
+            T* a = pw_a; T* b = pw_b;      // (sized for level 0: every level fits; the power iteration runs in T)
             const int n3 = L.n * 3;
             hipLaunchKernelGGL((k_seed_vector<T>), dim3(grid_for(n3)), dim3(kBlock), 0, stream, n3, a);
             const int lprA = lanes_for((double)L.nnzA / std::max(1, L.n));
@@ -234,7 +238,16 @@
         else LAUNCH_LPR_(lpr, APPLY_INST32, L.n, L.n, L.A_ptr, L.A_col, (const uint32_t*)L.Apm, (const T*)zc, kPoseRec, sbuf, (const CgState<T>*)st[slot]);
         return 0;
     }
+    // the cycle's vectors below level 0 are V (CV<T>; T under cyc64, testing builds only)
     int launch_vcycle(int slot, const GateArgs<T>* gate = nullptr) {
+#ifdef TSGO_TESTING
+        if (cyc64) return launch_vcycle_v<T>(slot, gate);
+#endif
+        return launch_vcycle_v<CV<T>>(slot, gate);
+    }
+    template <typename V> int launch_vcycle_v(int slot, const GateArgs<T>* gate) {
+        auto v = [](void* q) { return static_cast<V*>(q); };
+        auto cv = [](void* q) { return static_cast<const V*>(q); };
         const CgState<T>* s = st[slot];
         const size_t nl = lv.size();              // explicit levels 0 .. nl-1, dense level below
         // the cycle's first product leaves the residual r - S z itself (pose pass epilogue) where it reads f32 copies and needs no all-reduce:
@@ -245,9 +258,9 @@
             DevLevel<T>& L = lv[0];
             const int lpr = lanes_for((double)L.nnzP / std::max(1, L.n_agg));
             const H* dnext = (bottom_dense && nl == 2) ? (const H*)nullptr : (nl > 1 ? (const H*)lv[1].Dinv : (const H*)nullptr);      // (nl == 3 with the factored level: lv[1] keeps its pre-sweep)
-            if (nl > 1) PF(bytes_transfer(L, res_fused ? 1 : 2), "restrict from L0", "k_restrict<%s, %d, %d, %d>", tname(), lpr, res_fused ? 0 : 1, cy16 ? 1 : 0);
-            if (nl > 1 && res_fused) launch_restrict<0>(lpr, L, (const T*)sbuf, (const T*)sbuf, lv[1].r, dnext, lv[1].z, (const T*)(omega_dev + 1), s);
-            else if (nl > 1) launch_restrict<1>(lpr, L, (const T*)r, (const T*)sbuf, lv[1].r, dnext, lv[1].z, (const T*)(omega_dev + 1), s);
+            if (nl > 1) PF(bytes_transfer(L, res_fused ? 1 : 2, true), "restrict from L0", "k_restrict<%s, %d, %d, %d, %s, %s>", tname(), lpr, res_fused ? 0 : 1, cy16 ? 1 : 0, tname(), vname());
+            if (nl > 1 && res_fused) launch_restrict<0>(lpr, L, (const T*)sbuf, (const T*)sbuf, v(lv[1].r), dnext, v(lv[1].z), (const T*)(omega_dev + 1), s);
+            else if (nl > 1) launch_restrict<1>(lpr, L, (const T*)r, (const T*)sbuf, v(lv[1].r), dnext, v(lv[1].z), (const T*)(omega_dev + 1), s);
         }
         // coarse levels: V(nu,nu) with nu = coarse_sweeps block-Jacobi sweeps (the first pre-sweep comes fused
         // with the restriction above).  The current iterate alternates between L.z and L.z2; it ends in L.z2.
@@ -258,72 +271,72 @@
             DevLevel<T>& L = lv[l];
             const int nu = nu_at(l);
             const int lprA = lanes_for_sweep((double)L.nnzA / std::max(1, L.n), L.n);
-            T* cur = L.z; T* oth = L.z2;
+            V* cur = v(L.z); V* oth = v(L.z2);
             for (int sw = 1; sw < nu; ++sw) {
-                PF(bytes_sweep(L), lvl("pre-sweep", l).c_str(), "k_bcsr_residual<%s, %d, 1, 1, %d>", tname(), lprA, cy16 ? 1 : 0);
-                launch_sweep<1>(lprA, L, (const T*)L.r, (const T*)cur, oth, (const T*)(omega_dev + l), s);
+                PF(bytes_sweep(L), lvl("pre-sweep", l).c_str(), "k_bcsr_residual<%s, %d, 1, 1, %d, %s>", tname(), lprA, cy16 ? 1 : 0, vname());
+                launch_sweep<1>(lprA, L, cv(L.r), (const V*)cur, oth, (const T*)(omega_dev + l), s);
                 std::swap(cur, oth);
             }
-            PF(bytes_sweep(L), lvl("residual", l).c_str(), "k_bcsr_residual<%s, %d, 0, 1, %d>", tname(), lprA, cy16 ? 1 : 0);
-            launch_sweep<0>(lprA, L, (const T*)L.r, (const T*)cur, L.res, (const T*)(omega_dev + l), s);
+            PF(bytes_sweep(L), lvl("residual", l).c_str(), "k_bcsr_residual<%s, %d, 0, 1, %d, %s>", tname(), lprA, cy16 ? 1 : 0, vname());
+            launch_sweep<0>(lprA, L, cv(L.r), (const V*)cur, v(L.res), (const T*)(omega_dev + l), s);
             if (l + 1 < nl) {
                 const int lpr = lanes_for((double)L.nnzP / std::max(1, L.n_agg));
                 const bool no_presmooth = dense_bottom && !dense_tail2 && l + 2 == nl;      // the dense bottom operator pre-smooths by itself (the factored level wants z1 = W r)
-                PF(bytes_transfer(L, 1), lvl("restrict from", l).c_str(), "k_restrict<%s, %d, 0, %d>", tname(), lpr, cy16 ? 1 : 0);
-                launch_restrict<0>(lpr, L, (const T*)L.res, (const T*)L.res, lv[l + 1].r, no_presmooth ? (const H*)nullptr : (const H*)lv[l + 1].Dinv, lv[l + 1].z, (const T*)(omega_dev + l + 1), s);
+                PF(bytes_transfer(L, 1), lvl("restrict from", l).c_str(), "k_restrict<%s, %d, 0, %d, %s, %s>", tname(), lpr, cy16 ? 1 : 0, vname(), vname());
+                launch_restrict<0>(lpr, L, cv(L.res), cv(L.res), v(lv[l + 1].r), no_presmooth ? (const H*)nullptr : (const H*)lv[l + 1].Dinv, v(lv[l + 1].z), (const T*)(omega_dev + l + 1), s);
             }
         }
         // iterate of level l after the down pass: L.z when nu is odd, L.z2 when even
-        auto down_iter = [&](DevLevel<T>& L, int nu) { return (nu % 2) ? L.z : L.z2; };
-        auto down_other = [&](DevLevel<T>& L, int nu) { return (nu % 2) ? L.z2 : L.z; };
+        auto down_iter = [&](DevLevel<T>& L, int nu) { return v((nu % 2) ? L.z : L.z2); };
+        auto down_other = [&](DevLevel<T>& L, int nu) { return v((nu % 2) ? L.z2 : L.z); };
         if (dense_tail2) {       // levels nl-2 and nl-1 at once: z2 = 2 z1 - W A z1 + G (E^T r), z1 = W r left by the restriction into nl-2
             DevLevel<T>& L = lv[nl - 2];
             const int n3 = L.n * 3, nd = lv[nl - 1].n * 3;
-            PF((double)n3 * nd * sizeof(float) + (double)(n3 + nd) * sizeof(T), lvl("t = E^T r of", nl - 2).c_str(), "k_rowdot_wg<%s>", tname());
-            hipLaunchKernelGGL((k_rowdot_wg<T>), dim3(nd), dim3(kBlock), 0, stream, nd, n3, (const float*)tail_Etf, (const T*)L.r, tail_t, s);
-            PF(bytes_sweep(L) + (double)n3 * nd * sizeof(float), lvl("cycles of", nl - 2).c_str(), "k_tail_up<%s, %d>", tname(), cy16 ? 1 : 0);
-            if (cy16) hipLaunchKernelGGL((k_tail_up<T, 1>), dim3(L.n), dim3(kBlock), 0, stream, L.n, (const int*)L.A_ptr, (const int*)L.A_col, (const uint32_t*)L.Apm, (const H*)L.Dinv, (const T*)(omega_dev + nl - 2), (const T*)L.z, nd, (const float*)tail_Gf, (const T*)tail_t, L.z2, s);
-            else hipLaunchKernelGGL((k_tail_up<T, 0>), dim3(L.n), dim3(kBlock), 0, stream, L.n, (const int*)L.A_ptr, (const int*)L.A_col, (const uint32_t*)L.Apm, (const H*)L.Dinv, (const T*)(omega_dev + nl - 2), (const T*)L.z, nd, (const float*)tail_Gf, (const T*)tail_t, L.z2, s);
+            PF((double)n3 * nd * sizeof(float) + (double)(n3 + nd) * cv_bytes(), lvl("t = E^T r of", nl - 2).c_str(), "k_rowdot_wg<%s, %s>", tname(), vname());
+            hipLaunchKernelGGL((k_rowdot_wg<T, V>), dim3(nd), dim3(kBlock), 0, stream, nd, n3, (const float*)tail_Etf, cv(L.r), v(tail_t), s);
+            PF(bytes_sweep(L) + (double)n3 * nd * sizeof(float), lvl("cycles of", nl - 2).c_str(), "k_tail_up<%s, %d, %s>", tname(), cy16 ? 1 : 0, vname());
+            if (cy16) hipLaunchKernelGGL((k_tail_up<T, 1, V>), dim3(L.n), dim3(kBlock), 0, stream, L.n, (const int*)L.A_ptr, (const int*)L.A_col, (const uint32_t*)L.Apm, (const H*)L.Dinv, (const T*)(omega_dev + nl - 2), cv(L.z), nd, (const float*)tail_Gf, cv(tail_t), v(L.z2), s);
+            else hipLaunchKernelGGL((k_tail_up<T, 0, V>), dim3(L.n), dim3(kBlock), 0, stream, L.n, (const int*)L.A_ptr, (const int*)L.A_col, (const uint32_t*)L.Apm, (const H*)L.Dinv, (const T*)(omega_dev + nl - 2), cv(L.z), nd, (const float*)tail_Gf, cv(tail_t), v(L.z2), s);
         } else if (dense_bottom) {      // z2 = B r: pre-sweep, coarse correction through the dense inverse and post-sweep of the last explicit level at once
             DevLevel<T>& L = lv[nl - 1];
             const int n3 = L.n * 3;
-            PF((double)n3 * n3 * sizeof(float) + 2.0 * n3 * sizeof(T), lvl("whole cycle of", nl - 1).c_str(), "k_bottom_apply<%s>", tname());
-            hipLaunchKernelGGL((k_bottom_apply<T>), dim3(grid_for(n3, 64)), dim3(kBlock), 0, stream, n3, n3, (const float*)bot_Bf, (const T*)L.r, L.z2, s);
+            PF((double)n3 * n3 * sizeof(float) + 2.0 * n3 * cv_bytes(), lvl("whole cycle of", nl - 1).c_str(), "k_bottom_apply<%s, %s>", tname(), vname());
+            hipLaunchKernelGGL((k_bottom_apply<T, V>), dim3(grid_for(n3, 64)), dim3(kBlock), 0, stream, n3, n3, (const float*)bot_Bf, cv(L.r), v(L.z2), s);
         } else if (nl > 1 && lv[nl - 1].n * 4 <= kDenseThreads) {   // bottom: restrict + dense inverse + prolong in one workgroup, on the last explicit level
             DevLevel<T>& L = lv[nl - 1];
-            PF(2.0 * L.nnzP * (9 * sizeof(H) + 4) + (double)nb_last * 3 * nb_last * 3 * sizeof(T) + L.n * 6.0 * sizeof(T), lvl("restrict + dense solve + prolong", nl - 1).c_str(), "k_coarse_tail<%s>", tname());
-            hipLaunchKernelGGL((k_coarse_tail<T>), dim3(1), dim3(kDenseThreads), 0, stream, L.n, L.n_agg, L.R_ptr, L.R_col, (const H*)L.Rv, L.P_ptr, L.P_col, (const H*)L.P,
-                               (const T*)L.res, (const T*)inv_last, down_iter(L, nu_at(nl - 1)), s);
+            PF(2.0 * L.nnzP * (9 * sizeof(H) + 4) + (double)nb_last * 3 * nb_last * 3 * sizeof(T) + L.n * 6.0 * cv_bytes(), lvl("restrict + dense solve + prolong", nl - 1).c_str(), "k_coarse_tail<%s, %s>", tname(), vname());
+            hipLaunchKernelGGL((k_coarse_tail<T, V>), dim3(1), dim3(kDenseThreads), 0, stream, L.n, L.n_agg, L.R_ptr, L.R_col, (const H*)L.Rv, L.P_ptr, L.P_col, (const H*)L.P,
+                               cv(L.res), (const T*)inv_last, down_iter(L, nu_at(nl - 1)), s);
         } else if (nl > 1) {   // a last explicit level too long for the one-workgroup kernel (4 lanes per row): the same three steps as launches
             DevLevel<T>& L = lv[nl - 1];
-            PF(bytes_transfer(L, 1), lvl("restrict from", nl - 1).c_str(), "k_restrict<%s, 8, 0, %d>", tname(), cy16 ? 1 : 0);
-            launch_restrict<0>(8, L, (const T*)L.res, (const T*)L.res, r_last, (const H*)nullptr, (T*)nullptr, (const T*)one_dev, s);
-            PF((double)nb_last * 3 * nb_last * 3 * sizeof(T), "dense solve", "k_dense_apply<%s>", tname());
-            hipLaunchKernelGGL((k_dense_apply<T>), dim3(1), dim3(kBlock), 0, stream, nb_last * 3, (const T*)inv_last, (const T*)r_last, z_last, s);
-            launch_prolong(L, z_last, down_iter(L, nu_at(nl - 1)), 3, s, nl - 1);
+            PF(bytes_transfer(L, 1), lvl("restrict from", nl - 1).c_str(), "k_restrict<%s, 8, 0, %d, %s, %s>", tname(), cy16 ? 1 : 0, vname(), vname());
+            launch_restrict<0>(8, L, cv(L.res), cv(L.res), v(r_last), (const H*)nullptr, (V*)nullptr, (const T*)one_dev, s);
+            PF((double)nb_last * 3 * nb_last * 3 * sizeof(T), "dense solve", "k_dense_apply<%s, %s>", tname(), vname());
+            hipLaunchKernelGGL((k_dense_apply<T, V>), dim3(1), dim3(kBlock), 0, stream, nb_last * 3, (const T*)inv_last, cv(r_last), v(z_last), s);
+            launch_prolong(L, cv(z_last), down_iter(L, nu_at(nl - 1)), 3, s, nl - 1);
         } else {        // only level 0 above the dense level: residual r - S z is restricted from (r, sbuf)
             DevLevel<T>& L = lv[0];
-            PF(bytes_transfer(L, res_fused ? 1 : 2), "restrict from L0", "k_restrict<%s, 8, %d, %d>", tname(), res_fused ? 0 : 1, cy16 ? 1 : 0);
-            if (res_fused) launch_restrict<0>(8, L, (const T*)sbuf, (const T*)sbuf, r_last, (const H*)nullptr, (T*)nullptr, (const T*)one_dev, s);
-            else launch_restrict<1>(8, L, (const T*)r, (const T*)sbuf, r_last, (const H*)nullptr, (T*)nullptr, (const T*)one_dev, s);
-            PF((double)nb_last * 3 * nb_last * 3 * sizeof(T), "dense solve", "k_dense_apply<%s>", tname());
-            hipLaunchKernelGGL((k_dense_apply<T>), dim3(1), dim3(kBlock), 0, stream, nb_last * 3, (const T*)inv_last, (const T*)r_last, z_last, s);
+            PF(bytes_transfer(L, res_fused ? 1 : 2, true), "restrict from L0", "k_restrict<%s, 8, %d, %d, %s, %s>", tname(), res_fused ? 0 : 1, cy16 ? 1 : 0, tname(), vname());
+            if (res_fused) launch_restrict<0>(8, L, (const T*)sbuf, (const T*)sbuf, v(r_last), (const H*)nullptr, (V*)nullptr, (const T*)one_dev, s);
+            else launch_restrict<1>(8, L, (const T*)r, (const T*)sbuf, v(r_last), (const H*)nullptr, (V*)nullptr, (const T*)one_dev, s);
+            PF((double)nb_last * 3 * nb_last * 3 * sizeof(T), "dense solve", "k_dense_apply<%s, %s>", tname(), vname());
+            hipLaunchKernelGGL((k_dense_apply<T, V>), dim3(1), dim3(kBlock), 0, stream, nb_last * 3, (const T*)inv_last, cv(r_last), v(z_last), s);
         }
         for (size_t l = nl - 1; l >= 1; --l) {
             DevLevel<T>& L = lv[l];
             if (l >= first_dense) continue;      // a dense level's result is in its z2 already
             const int nu = nu_at(l);
-            T* cur = down_iter(L, nu); T* oth = down_other(L, nu);
-            if (l + 1 < nl) launch_prolong(L, lv[l + 1].z2, cur, 3, s, l);
+            V* cur = down_iter(L, nu); V* oth = down_other(L, nu);
+            if (l + 1 < nl) launch_prolong(L, cv(lv[l + 1].z2), cur, 3, s, l);
             const int lprA = lanes_for_sweep((double)L.nnzA / std::max(1, L.n), L.n);
             for (int sw = 0; sw < nu; ++sw) {
-                PF(bytes_sweep(L), lvl("post-sweep", l).c_str(), "k_bcsr_residual<%s, %d, 1, 1, %d>", tname(), lprA, cy16 ? 1 : 0);
-                launch_sweep<1>(lprA, L, (const T*)L.r, (const T*)cur, oth, (const T*)(omega_dev + l), s);
+                PF(bytes_sweep(L), lvl("post-sweep", l).c_str(), "k_bcsr_residual<%s, %d, 1, 1, %d, %s>", tname(), lprA, cy16 ? 1 : 0, vname());
+                launch_sweep<1>(lprA, L, cv(L.r), (const V*)cur, oth, (const T*)(omega_dev + l), s);
                 std::swap(cur, oth);
             }
             // nu post-sweeps after nu-1 pre-swaps: the result sits in L.z2 for every nu (odd+odd / even+even swaps)
         }
-        launch_prolong(lv[0], nl > 1 ? (const T*)lv[1].z2 : (const T*)z_last, zc, kPoseRec, s, 0);
+        launch_prolong(lv[0], nl > 1 ? cv(lv[1].z2) : cv(z_last), zc, kPoseRec, s, 0);
         // level-0 post-smoothing zc += omega Minv (r - S zc): in the epilogue of the product's pose pass where that pass reads f32 copies and its
         // result needs no all-reduce (one shard), else a launch of its own
         const bool fuse_post = fuse_post_smooth && !explicit0 && low_cycle && !collective();

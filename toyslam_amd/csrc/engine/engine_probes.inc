@@ -1,5 +1,12 @@
 // engine/engine_probes.inc — part of `template <typename T> struct Engine` (tsgo_hip.hip includes it INSIDE the class body):
 // timing probes behind tsgo_cycle_probe / tsgo_profile_iteration / tsgo_time_kernel.
+    void probe_sweep(int lprA, DevLevel<T>& L, const T* omega) {      // one smoothing sweep on the level's own vectors, in their type
+        const CgState<T>* s0 = st[0];
+#ifdef TSGO_TESTING
+        if (cyc64) { launch_sweep<1>(lprA, L, (const T*)L.r, (const T*)L.z, (T*)L.z2, omega, s0); return; }
+#endif
+        launch_sweep<1>(lprA, L, (const CV<T>*)L.r, (const CV<T>*)L.z, (CV<T>*)L.z2, omega, s0);
+    }
     int cycle_probe(int reps, tsgo_cycle_level* out, int cap) override {
         if (!have_graph_data) return set_error(-3, "tsgo_cycle_probe: no graph set");
         HIP_OK(hipSetDevice(cfg.device));
@@ -14,7 +21,7 @@
                 const int m = pass == 0 ? 3 : reps;
                 HIP_OK(hipEventRecord(ev[0], stream));
                 for (int k = 0; k < m; ++k)
-                    launch_sweep<1>(lprA, L, (const T*)L.r, (const T*)L.z, L.z2, (const T*)(omega_dev + l), (const CgState<T>*)st[0]);
+                    probe_sweep(lprA, L, (const T*)(omega_dev + l));
                 HIP_OK(hipEventRecord(ev[1], stream));
                 HIP_OK(hipEventSynchronize(ev[1]));
                 if (pass == 1) { float ms = 0; HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1])); out[n].us_per_sweep = 1e3 * ms / m; }

@@ -17,3 +17,11 @@
 #define TSGO_RESEARCH_INT(name, dflt) (dflt)
 #define TSGO_RESEARCH_FLOAT(name, dflt) ((double)(dflt))
 #endif
+
+// TSGO_CYCLE_VEC64=1: the multigrid cycle's vectors below level 0 in the engine's own type (f64) instead of CycVec (f32) —
+// the A/B of that choice (tests/test_gpu_cycle_f32_vectors.py, tests/research/bench_with_lib.py).  Testing builds only.
+#ifdef TSGO_TESTING
+#define TSGO_CYCLE_VEC64() (TSGO_RESEARCH_INT("TSGO_CYCLE_VEC64", 0) != 0)
+#else
+#define TSGO_CYCLE_VEC64() false
+#endif

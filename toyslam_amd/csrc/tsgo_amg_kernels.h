@@ -22,6 +22,15 @@ template <typename T> struct Hier { using type = T; };
 template <typename T> struct Hier { using type = float; };
 #endif
 template <typename T> using HT = typename Hier<T>::type;
+// Vector type of the V-cycle below level 0 (the level vectors r, z, res, z2, the tail vector t, the bottom vectors): every operator
+// such a vector meets is stored in HT (f32 or packed halves), so f64 entries buy the preconditioner no accuracy; sums inside a block
+// row are accumulated in this type too.  The PCG itself (x, r, p, S p, its dot products and stopping rule) stays in T.
+#ifdef TSGO_HIER_F64
+template <typename T> struct CycVec { using type = T; };
+#else
+template <typename T> struct CycVec { using type = float; };
+#endif
+template <typename T> using CV = typename CycVec<T>::type;
 
 constexpr int kPairBlocksPerWave = 21;   // k_pair_gemm: three lanes per 3x3 output block
 constexpr int kDenseMax = 84;            // coarsest matrix is at most 84 x 84 (host/amg.h: kCoarsestMax * 3)
@@ -440,16 +449,17 @@ __device__ __forceinline__ int lpr_block(int xcd) { return xcd ? xcd_block() : (
 // MODE 0: out = r - A z.   MODE 1: out = z + omega Dinv (r - A z)  (smoothing sweep).
 // MODE 2: out = Dinv A z  (power iteration for the smoother's damping).
 // PM: A is the cycle-format copy (above; PK = its encoding); otherwise the block-indexed f32 / HT matrix.
-template <typename T, int LPR, int MODE, int PM = 1, int PK = 0>
+// V: the vector (and accumulation) type, T by default; the cycle's levels >= 1 run it in CV<T>.
+template <typename T, int LPR, int MODE, int PM = 1, int PK = 0, typename V = T>
 __global__ __launch_bounds__(kBlock) void k_bcsr_residual(int n, const int* __restrict__ ptr, const int* __restrict__ col,
-                                                          const void* __restrict__ Av, const T* __restrict__ r, const T* __restrict__ z,
-                                                          const HT<T>* __restrict__ Dinv, T* __restrict__ out,
+                                                          const void* __restrict__ Av, const V* __restrict__ r, const V* __restrict__ z,
+                                                          const HT<T>* __restrict__ Dinv, V* __restrict__ out,
                                                           const T* __restrict__ omega_ptr, const CgState<T>* __restrict__ st, int xcd = 0) {
     const int done = MODE != 2 ? st->done : 0;
     const int g = (lpr_block(xcd) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
     // LPR == 64: the row is wave-uniform, its bounds come through the scalar cache (one dependent round trip shorter)
     const int i = LPR == 64 ? __builtin_amdgcn_readfirstlane(g < n ? g : n - 1) : (g < n ? g : n - 1);
-    T s0 = 0, s1 = 0, s2 = 0;
+    V s0 = 0, s1 = 0, s2 = 0;
     int p0 = ptr[i];
     const int p1 = ptr[i + 1];
     issue_before_exit(p0);
@@ -457,7 +467,7 @@ __global__ __launch_bounds__(kBlock) void k_bcsr_residual(int n, const int* __re
     // What the row's epilogue needs (its right-hand side, its own entry of z, its diagonal inverse) depends on the row
     // alone: requested now, it arrives while the blocks are walked instead of adding a fourth dependent trip at the end.
     const bool head = g < n && sub == 0;
-    T ri0 = 0, ri1 = 0, ri2 = 0, zi0 = 0, zi1 = 0, zi2 = 0;
+    V ri0 = 0, ri1 = 0, ri2 = 0, zi0 = 0, zi1 = 0, zi2 = 0;
     HT<T> d[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (head) {
         if (MODE != 2) { ri0 = r[(size_t)i * 3]; ri1 = r[(size_t)i * 3 + 1]; ri2 = r[(size_t)i * 3 + 2]; }
@@ -473,28 +483,28 @@ __global__ __launch_bounds__(kBlock) void k_bcsr_residual(int n, const int* __re
     // two to five blocks — was measured in round 3: 78 instead of 62 VGPRs, six resident waves per SIMD instead of eight, and the
     // sweeps of levels 1-2 got slower, 7.7 -> 8.4 us and 7.9 -> 8.7 us.  One block per trip it stays.)
     for (int a = p0 + sub; a < p1; a += LPR) {
-        const T* v = z + (size_t)col[a] * 3;
-        T b[9];
-        if (PM) cy_load<T, PK>(base, len, (size_t)(a - p0), b);
+        const V* v = z + (size_t)col[a] * 3;
+        V b[9];
+        if (PM) cy_load<V, PK>(base, len, (size_t)(a - p0), b);
         else {
             const HT<T>* q = (const HT<T>*)Av + (size_t)a * 9;
 #pragma unroll
             for (int m = 0; m < 9; ++m) b[m] = q[m];
         }
-        const T v0 = v[0], v1 = v[1], v2 = v[2];
+        const V v0 = v[0], v1 = v[1], v2 = v[2];
         s0 += b[0] * v0 + b[1] * v1 + b[2] * v2; s1 += b[3] * v0 + b[4] * v1 + b[5] * v2; s2 += b[6] * v0 + b[7] * v1 + b[8] * v2;
     }
-    s0 = group_sum<T, LPR>(s0); s1 = group_sum<T, LPR>(s1); s2 = group_sum<T, LPR>(s2);
+    s0 = group_sum<V, LPR>(s0); s1 = group_sum<V, LPR>(s1); s2 = group_sum<V, LPR>(s2);
     if (head) {
         if (MODE == 2) {
             out[(size_t)i * 3] = d[0] * s0 + d[1] * s1 + d[2] * s2; out[(size_t)i * 3 + 1] = d[3] * s0 + d[4] * s1 + d[5] * s2;
             out[(size_t)i * 3 + 2] = d[6] * s0 + d[7] * s1 + d[8] * s2;
             return;
         }
-        const T e0 = ri0 - s0, e1 = ri1 - s1, e2 = ri2 - s2;
+        const V e0 = ri0 - s0, e1 = ri1 - s1, e2 = ri2 - s2;
         if (MODE == 0) { out[(size_t)i * 3] = e0; out[(size_t)i * 3 + 1] = e1; out[(size_t)i * 3 + 2] = e2; }
         else {
-            const T omega = *omega_ptr;
+            const V omega = (V)*omega_ptr;
             out[(size_t)i * 3] = zi0 + omega * (d[0] * e0 + d[1] * e1 + d[2] * e2);
             out[(size_t)i * 3 + 1] = zi1 + omega * (d[3] * e0 + d[4] * e1 + d[5] * e2);
             out[(size_t)i * 3 + 2] = zi2 + omega * (d[6] * e0 + d[7] * e1 + d[8] * e2);
@@ -530,24 +540,26 @@ __global__ __launch_bounds__(kBlock) void k_bcsr_apply(int n, const int* __restr
 
 // rc = P^T v over the rows of R = P^T, and (when dinv_next is given) the next level's pre-smoothing
 // z_next = Dinv_next rc in the same pass.  SUB: v = a - b (level 0: r - S z, never materialised).
-template <typename T, int LPR, int SUB, int PK = 0>
+// VI / VO: the fine (input) and coarse (output) vector types; sums in the wider of the two (level 0 -> 1: T in, CV<T> out).
+template <typename T, int LPR, int SUB, int PK = 0, typename VI = T, typename VO = T>
 __global__ __launch_bounds__(kBlock) void k_restrict(int n_agg, const int* __restrict__ rptr, const int* __restrict__ rcol,
-                                                     const uint32_t* __restrict__ Rv, const T* __restrict__ va,
-                                                     const T* __restrict__ vb, T* __restrict__ rc, const HT<T>* __restrict__ dinv_next,
-                                                     T* __restrict__ z_next, const T* __restrict__ omega_ptr, const CgState<T>* __restrict__ st, int xcd = 0) {
+                                                     const uint32_t* __restrict__ Rv, const VI* __restrict__ va,
+                                                     const VI* __restrict__ vb, VO* __restrict__ rc, const HT<T>* __restrict__ dinv_next,
+                                                     VO* __restrict__ z_next, const T* __restrict__ omega_ptr, const CgState<T>* __restrict__ st, int xcd = 0) {
+    using A = decltype(VI(0) + VO(0));
     const int done = st->done;
     const int g = (lpr_block(xcd) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
     const int a = g < n_agg ? g : n_agg - 1;
-    T s0 = 0, s1 = 0, s2 = 0;
+    A s0 = 0, s1 = 0, s2 = 0;
     int p0 = rptr[a];
     const int p1 = rptr[a + 1];
     issue_before_exit(p0);
     if (done) return;
     const bool head = g < n_agg && sub == 0;
     HT<T> dn[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // the next level's diagonal inverse: asked for before the walk, used after it
-    T omega = 0;
+    A omega = 0;
     if (head && dinv_next) {
-        omega = *omega_ptr;
+        omega = (A)*omega_ptr;
 #pragma unroll
         for (int m = 0; m < 9; ++m) dn[m] = dinv_next[(size_t)a * 9 + m];
     }
@@ -555,13 +567,13 @@ __global__ __launch_bounds__(kBlock) void k_restrict(int n_agg, const int* __res
     const uint32_t* base = Rv + (size_t)p0 * cy_words<PK>();          // cycle format
     for (int rb = p0 + sub; rb < p1; rb += LPR) {
         const size_t i = (size_t)rcol[rb] * 3;
-        T b[9];
-        cy_load<T, PK>(base, len, (size_t)(rb - p0), b);
-        T x0 = va[i], x1 = va[i + 1], x2 = va[i + 2];
+        A b[9];
+        cy_load<A, PK>(base, len, (size_t)(rb - p0), b);
+        A x0 = va[i], x1 = va[i + 1], x2 = va[i + 2];
         if (SUB) { x0 -= vb[i]; x1 -= vb[i + 1]; x2 -= vb[i + 2]; }
         s0 += b[0] * x0 + b[1] * x1 + b[2] * x2; s1 += b[3] * x0 + b[4] * x1 + b[5] * x2; s2 += b[6] * x0 + b[7] * x1 + b[8] * x2;
     }
-    s0 = group_sum<T, LPR>(s0); s1 = group_sum<T, LPR>(s1); s2 = group_sum<T, LPR>(s2);
+    s0 = group_sum<A, LPR>(s0); s1 = group_sum<A, LPR>(s1); s2 = group_sum<A, LPR>(s2);
     if (head) {
         rc[(size_t)a * 3] = s0; rc[(size_t)a * 3 + 1] = s1; rc[(size_t)a * 3 + 2] = s2;
         if (dinv_next) {
@@ -572,34 +584,36 @@ __global__ __launch_bounds__(kBlock) void k_restrict(int n_agg, const int* __res
     }
 }
 
-// z_i += sum_a P_ia e_a; z has row stride `zs` (3 on coarse levels, kPoseRec for zc)
-template <typename T, int LPR, int PK = 0>
+// z_i += sum_a P_ia e_a; z has row stride `zs` (3 on coarse levels, kPoseRec for zc).  VE / VZ: the coarse and fine vector types
+// (into level 0: CV<T> in, T out); sums in the wider of the two.
+template <typename T, int LPR, int PK = 0, typename VE = T, typename VZ = T>
 __global__ __launch_bounds__(kBlock) void k_prolong_add(int n, const int* __restrict__ pptr, const int* __restrict__ pcol,
-                                                        const uint32_t* __restrict__ P, const T* __restrict__ e, T* __restrict__ z, int zs,
+                                                        const uint32_t* __restrict__ P, const VE* __restrict__ e, VZ* __restrict__ z, int zs,
                                                         const CgState<T>* __restrict__ st, float* __restrict__ z32 = nullptr, int xcd = 0) {
+    using A = decltype(VE(0) + VZ(0));
     const int done = st->done;
     const int g = (lpr_block(xcd) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
     const int i = g < n ? g : n - 1;
-    T s0 = 0, s1 = 0, s2 = 0;
+    A s0 = 0, s1 = 0, s2 = 0;
     int p0 = pptr[i];
     const int p1 = pptr[i + 1];
     issue_before_exit(p0);
     if (done) return;
     const bool head = g < n && sub == 0;
-    T z0 = 0, z1 = 0, z2 = 0;                          // the entry this row adds to: read before the walk
+    A z0 = 0, z1 = 0, z2 = 0;                          // the entry this row adds to: read before the walk
     if (head) { z0 = z[(size_t)i * zs]; z1 = z[(size_t)i * zs + 1]; z2 = z[(size_t)i * zs + 2]; }
     const size_t len = (size_t)(p1 - p0);
     const uint32_t* base = P + (size_t)p0 * cy_words<PK>();           // cycle format
     for (int pb = p0 + sub; pb < p1; pb += LPR) {
-        const T* v = e + (size_t)pcol[pb] * 3;
-        T b[9];
-        cy_load<T, PK>(base, len, (size_t)(pb - p0), b);
-        const T v0 = v[0], v1 = v[1], v2 = v[2];
+        const VE* v = e + (size_t)pcol[pb] * 3;
+        A b[9];
+        cy_load<A, PK>(base, len, (size_t)(pb - p0), b);
+        const A v0 = v[0], v1 = v[1], v2 = v[2];
         s0 += b[0] * v0 + b[1] * v1 + b[2] * v2; s1 += b[3] * v0 + b[4] * v1 + b[5] * v2; s2 += b[6] * v0 + b[7] * v1 + b[8] * v2;
     }
-    s0 = group_sum<T, LPR>(s0); s1 = group_sum<T, LPR>(s1); s2 = group_sum<T, LPR>(s2);
+    s0 = group_sum<A, LPR>(s0); s1 = group_sum<A, LPR>(s1); s2 = group_sum<A, LPR>(s2);
     if (head) {
-        z[(size_t)i * zs] = z0 + s0; z[(size_t)i * zs + 1] = z1 + s1; z[(size_t)i * zs + 2] = z2 + s2;
+        z[(size_t)i * zs] = VZ(z0 + s0); z[(size_t)i * zs + 1] = VZ(z1 + s1); z[(size_t)i * zs + 2] = VZ(z2 + s2);
         if (z32) { float* q = z32 + (size_t)i * zs; q[0] = (float)(z0 + s0); q[1] = (float)(z1 + s1); q[2] = (float)(z2 + s2); }     // level 0: the pose records' f32 copy
     }
 }
@@ -607,11 +621,11 @@ __global__ __launch_bounds__(kBlock) void k_prolong_add(int n, const int* __rest
 // Bottom of the V-cycle in ONE workgroup of 1024 threads: restrict the last explicit level's residual
 // (n <= 224 rows) to the dense level (<= 28 aggregates, 32 lanes each), apply the dense inverse,
 // prolong the correction back (4 lanes per row).
-template <typename T>
+template <typename T, typename V = T>
 __global__ __launch_bounds__(kDenseThreads) void k_coarse_tail(int n, int n_agg, const int* __restrict__ rptr, const int* __restrict__ rcol,
                                                                const HT<T>* __restrict__ Rv, const int* __restrict__ pptr,
-                                                               const int* __restrict__ pcol, const HT<T>* __restrict__ P, const T* __restrict__ res,
-                                                               const T* __restrict__ inv, T* __restrict__ z, const CgState<T>* __restrict__ st) {
+                                                               const int* __restrict__ pcol, const HT<T>* __restrict__ P, const V* __restrict__ res,
+                                                               const T* __restrict__ inv, V* __restrict__ z, const CgState<T>* __restrict__ st) {
     const int done = st->done;
     __shared__ T rc[kDenseMax], zc_[kDenseMax];
     {
@@ -644,7 +658,7 @@ __global__ __launch_bounds__(kDenseThreads) void k_coarse_tail(int n, int n_agg,
                 s0 += b[0] * v[0] + b[1] * v[1] + b[2] * v[2]; s1 += b[3] * v[0] + b[4] * v[1] + b[5] * v[2]; s2 += b[6] * v[0] + b[7] * v[1] + b[8] * v[2];
             }
         s0 = group_sum<T, 4>(s0); s1 = group_sum<T, 4>(s1); s2 = group_sum<T, 4>(s2);
-        if (i < n && sub == 0) { z[(size_t)i * 3] += s0; z[(size_t)i * 3 + 1] += s1; z[(size_t)i * 3 + 2] += s2; }
+        if (i < n && sub == 0) { z[(size_t)i * 3] = V(z[(size_t)i * 3] + s0); z[(size_t)i * 3 + 1] = V(z[(size_t)i * 3 + 1] + s1); z[(size_t)i * 3 + 2] = V(z[(size_t)i * 3 + 2] + s2); }
     }
 }
 
@@ -725,19 +739,19 @@ __global__ __launch_bounds__(kBlock) void k_bottom_finish(int n3, const T* __res
 
 // z = B r for a dense f32 matrix B [n_rows x n_cols], one wavefront per row (every row a few coalesced passes): the last level's
 // whole cycle in one launch (B = the level's operator), or t = E^T r of the level above it (B = E^T, below)
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_bottom_apply(int n_rows, int n_cols, const float* __restrict__ Bf, const T* __restrict__ r, T* __restrict__ z, const CgState<T>* __restrict__ st) {
+template <typename T, typename V = T>
+__global__ __launch_bounds__(kBlock) void k_bottom_apply(int n_rows, int n_cols, const float* __restrict__ Bf, const V* __restrict__ r, V* __restrict__ z, const CgState<T>* __restrict__ st) {
     const int done = st->done;
     const int row = (blockIdx.x * kBlock + threadIdx.x) >> 6, lane = threadIdx.x & 63;
     const int rc = row < n_rows ? row : n_rows - 1;
     const float* b = Bf + (size_t)rc * n_cols;
-    T acc = 0;
+    V acc = 0;
     float b0 = lane < n_cols ? b[lane] : 0.f;
     issue_before_exit(b0);
     if (done) return;
-    if (lane < n_cols) acc = T(b0) * r[lane];
-    for (int c = lane + 64; c < n_cols; c += 64) acc += T(b[c]) * r[c];
-    acc = wave_sum<T>(acc);
+    if (lane < n_cols) acc = V(b0) * r[lane];
+    for (int c = lane + 64; c < n_cols; c += 64) acc += V(b[c]) * r[c];
+    acc = wave_sum<V>(acc);
     if (row < n_rows && lane == 0) z[row] = acc;
 }
 
@@ -836,35 +850,35 @@ __global__ __launch_bounds__(kBlock) void k_transpose_f32(int n3, int nd, const 
 
 // z = B r for a dense f32 matrix with LONG rows (n_cols in the thousands): one workgroup per row, every load of a thread issued
 // before its first use, block reduction.  (One wavefront per row, k_bottom_apply, walks such a row in 43 dependent trips: 21 us.)
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_rowdot_wg(int n_rows, int n_cols, const float* __restrict__ Bf, const T* __restrict__ r, T* __restrict__ z, const CgState<T>* __restrict__ st) {
-    __shared__ T red[kWavesPerBlock];
+template <typename T, typename V = T>
+__global__ __launch_bounds__(kBlock) void k_rowdot_wg(int n_rows, int n_cols, const float* __restrict__ Bf, const V* __restrict__ r, V* __restrict__ z, const CgState<T>* __restrict__ st) {
+    __shared__ V red[kWavesPerBlock];
     const int done = st->done;
     const int row = blockIdx.x;
     const float* b = Bf + (size_t)row * n_cols;
     constexpr int U = 12;                                    // 3 072 columns per trip: a level of <= 1 024 block rows is ONE trip
-    T acc = 0;
+    V acc = 0;
     float b0 = (int)threadIdx.x < n_cols ? b[threadIdx.x] : 0.f;
     issue_before_exit(b0);
     if (done) return;                                        // workgroup-uniform
     for (int c0 = threadIdx.x; c0 < n_cols; c0 += U * kBlock) {
-        float bv[U]; T rv[U];
+        float bv[U]; V rv[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) { const int c = c0 + u * kBlock; const bool in = c < n_cols; bv[u] = in ? b[c] : 0.f; rv[u] = in ? r[c] : T(0); }
+        for (int u = 0; u < U; ++u) { const int c = c0 + u * kBlock; const bool in = c < n_cols; bv[u] = in ? b[c] : 0.f; rv[u] = in ? r[c] : V(0); }
 #pragma unroll
-        for (int u = 0; u < U; ++u) acc += T(bv[u]) * rv[u];
+        for (int u = 0; u < U; ++u) acc += V(bv[u]) * rv[u];
     }
-    const T total = block_sum<T>(acc, red);
+    const V total = block_sum<V>(acc, red);
     if (threadIdx.x == 0) z[row] = total;
 }
 
 // z_i = 2 z1_i - omega D_i^-1 sum_j A_ij z1_j + sum_m G[3i..3i+2][m] t[m]: one WORKGROUP per block row (A in the cycle format): the
 // row's blocks a lane each, the three dense rows of G spread over all 256 threads
-template <typename T, int PK>
+template <typename T, int PK, typename V = T>
 __global__ __launch_bounds__(kBlock) void k_tail_up(int n, const int* __restrict__ ptr, const int* __restrict__ col, const uint32_t* __restrict__ Apm, const HT<T>* __restrict__ Dinv,
-                                                    const T* __restrict__ omega_ptr, const T* __restrict__ z1, int nd, const float* __restrict__ Gf, const T* __restrict__ t,
-                                                    T* __restrict__ z, const CgState<T>* __restrict__ st) {
-    __shared__ T red6[kWavesPerBlock * 6];
+                                                    const T* __restrict__ omega_ptr, const V* __restrict__ z1, int nd, const float* __restrict__ Gf, const V* __restrict__ t,
+                                                    V* __restrict__ z, const CgState<T>* __restrict__ st) {
+    __shared__ V red6[kWavesPerBlock * 6];
     const int done = st->done;
     const int i = blockIdx.x;
     int p0 = ptr[i];
@@ -873,45 +887,45 @@ __global__ __launch_bounds__(kBlock) void k_tail_up(int n, const int* __restrict
     if (done) return;                                        // workgroup-uniform
     // the dense part first: its operands depend on the arguments alone
     const float* g0 = Gf + (size_t)i * 3 * nd;
-    T d0 = 0, d1 = 0, d2 = 0;
-    for (int m = threadIdx.x; m < nd; m += kBlock) { const T tm = t[m]; d0 += T(g0[m]) * tm; d1 += T(g0[nd + m]) * tm; d2 += T(g0[2 * (size_t)nd + m]) * tm; }
-    T s0 = 0, s1 = 0, s2 = 0;
+    V d0 = 0, d1 = 0, d2 = 0;
+    for (int m = threadIdx.x; m < nd; m += kBlock) { const V tm = t[m]; d0 += V(g0[m]) * tm; d1 += V(g0[nd + m]) * tm; d2 += V(g0[2 * (size_t)nd + m]) * tm; }
+    V s0 = 0, s1 = 0, s2 = 0;
     const size_t len = (size_t)(p1 - p0);
     const uint32_t* base = Apm + (size_t)p0 * cy_words<PK>();
     for (int a = p0 + threadIdx.x; a < p1; a += kBlock) {
-        const T* v = z1 + (size_t)col[a] * 3;
-        T b[9];
-        cy_load<T, PK>(base, len, (size_t)(a - p0), b);
-        const T v0 = v[0], v1 = v[1], v2 = v[2];
+        const V* v = z1 + (size_t)col[a] * 3;
+        V b[9];
+        cy_load<V, PK>(base, len, (size_t)(a - p0), b);
+        const V v0 = v[0], v1 = v[1], v2 = v[2];
         s0 += b[0] * v0 + b[1] * v1 + b[2] * v2; s1 += b[3] * v0 + b[4] * v1 + b[5] * v2; s2 += b[6] * v0 + b[7] * v1 + b[8] * v2;
     }
     // six sums, ONE barrier: per-wave shuffles, then thread 0 adds the four waves' partials
-    s0 = wave_sum<T>(s0); s1 = wave_sum<T>(s1); s2 = wave_sum<T>(s2); d0 = wave_sum<T>(d0); d1 = wave_sum<T>(d1); d2 = wave_sum<T>(d2);
-    if ((threadIdx.x & 63) == 0) { T* q = red6 + (threadIdx.x >> 6) * 6; q[0] = s0; q[1] = s1; q[2] = s2; q[3] = d0; q[4] = d1; q[5] = d2; }
+    s0 = wave_sum<V>(s0); s1 = wave_sum<V>(s1); s2 = wave_sum<V>(s2); d0 = wave_sum<V>(d0); d1 = wave_sum<V>(d1); d2 = wave_sum<V>(d2);
+    if ((threadIdx.x & 63) == 0) { V* q = red6 + (threadIdx.x >> 6) * 6; q[0] = s0; q[1] = s1; q[2] = s2; q[3] = d0; q[4] = d1; q[5] = d2; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        T v[6];
+        V v[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) { v[k] = red6[k]; for (int wv = 1; wv < kWavesPerBlock; ++wv) v[k] += red6[wv * 6 + k]; }
-        const T w = *omega_ptr;
+        const V w = (V)*omega_ptr;
         const HT<T>* d = Dinv + (size_t)i * 9;
-        const T* zi = z1 + (size_t)i * 3;
-        z[(size_t)i * 3] = T(2) * zi[0] - w * (T(d[0]) * v[0] + T(d[1]) * v[1] + T(d[2]) * v[2]) + v[3];
-        z[(size_t)i * 3 + 1] = T(2) * zi[1] - w * (T(d[3]) * v[0] + T(d[4]) * v[1] + T(d[5]) * v[2]) + v[4];
-        z[(size_t)i * 3 + 2] = T(2) * zi[2] - w * (T(d[6]) * v[0] + T(d[7]) * v[1] + T(d[8]) * v[2]) + v[5];
+        const V* zi = z1 + (size_t)i * 3;
+        z[(size_t)i * 3] = V(2) * zi[0] - w * (V(d[0]) * v[0] + V(d[1]) * v[1] + V(d[2]) * v[2]) + v[3];
+        z[(size_t)i * 3 + 1] = V(2) * zi[1] - w * (V(d[3]) * v[0] + V(d[4]) * v[1] + V(d[5]) * v[2]) + v[4];
+        z[(size_t)i * 3 + 2] = V(2) * zi[2] - w * (V(d[6]) * v[0] + V(d[7]) * v[1] + V(d[8]) * v[2]) + v[5];
     }
 }
 
 // coarsest level alone (graphs with a single explicit level): z = inv r, single workgroup
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_dense_apply(int n, const T* __restrict__ inv, const T* __restrict__ r, T* __restrict__ z,
+template <typename T, typename V = T>
+__global__ __launch_bounds__(kBlock) void k_dense_apply(int n, const T* __restrict__ inv, const V* __restrict__ r, V* __restrict__ z,
                                                         const CgState<T>* __restrict__ st) {
     if (st->done) return;
     __shared__ T rv[kDenseMax];
     for (int j = threadIdx.x; j < n; j += kBlock) rv[j] = r[j];
     __syncthreads();
     const int i = threadIdx.x;
-    if (i < n) { T s = 0; for (int j = 0; j < n; ++j) s += inv[(size_t)i * n + j] * rv[j]; z[i] = s; }
+    if (i < n) { T s = 0; for (int j = 0; j < n; ++j) s += inv[(size_t)i * n + j] * rv[j]; z[i] = V(s); }
 }
 
 // level 0 smoothing with the symmetric 3x3 inverse blocks of the Schur diagonal (minv, 6 per pose):

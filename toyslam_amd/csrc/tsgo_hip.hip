@@ -199,7 +199,7 @@ template <typename T> struct DevLevel {      // device copy of one AmgLevel (hos
     T* rel = nullptr;
     H *A = nullptr, *Dinv = nullptr, *P = nullptr, *Tv = nullptr, *Rv = nullptr;
     uint32_t *Apm = nullptr, *Ppm = nullptr, *Rpm = nullptr;       // cycle format: the same blocks, plane-major within each row, f32 or packed half (tsgo_amg_kernels.h)
-    T *r = nullptr, *z = nullptr, *res = nullptr, *z2 = nullptr;
+    void *r = nullptr, *z = nullptr, *res = nullptr, *z2 = nullptr;      // cycle vectors: CV<T>, or T under Engine::cyc64 (launch_vcycle_v)
 };
 
 template <typename T> struct Engine : IEngine {
@@ -273,7 +273,8 @@ template <typename T> struct Engine : IEngine {
     int *last_ptr = nullptr, *last_col = nullptr; int nb_last = 0, nnz_last = 0;
     using H = HT<T>;
     H* A_last = nullptr;
-    T *inv_last = nullptr, *r_last = nullptr, *z_last = nullptr, *rzpart = nullptr, *fold_part = nullptr;
+    T *inv_last = nullptr, *rzpart = nullptr, *fold_part = nullptr;
+    void *r_last = nullptr, *z_last = nullptr;      // cycle vectors (as DevLevel::r)
     double ms_amg_symbolic = 0;
     T *omega_dev = nullptr, *one_dev = nullptr, *gscale_dev = nullptr, *pw_a = nullptr, *pw_b = nullptr, *rho_part = nullptr;
     T* h_rho = nullptr;                 // pinned
@@ -309,6 +310,11 @@ template <typename T> struct Engine : IEngine {
                                // until a solve on this structure shows that the graph is too ill-conditioned for 11-bit blocks (do_solve)
     int n_cycle_f32_switches = 0;
     size_t cyw() const { return cy16 ? (size_t)kCyWordsF16 : (size_t)kCyWordsF32; }
+    // the cycle's vectors below level 0 (DevLevel::r / z / res / z2, r_last / z_last, tail_t) hold CV<T>; cyc64 = T instead (testing builds:
+    // TSGO_CYCLE_VEC64, host/knobs.h).  Fixed for the handle's life: the buffers are sized by it.
+    bool cyc64 = false;
+    size_t cv_bytes() const { return cyc64 ? sizeof(T) : sizeof(CV<T>); }
+    int valloc(void** out, size_t n) { char* d = nullptr; if (int rc = dalloc(&d, n * cv_bytes())) return rc; *out = d; return 0; }
 
     // Environment, read ONCE per handle (tsgo_create).  Operational: verbosity / timing traces.  Research and test hooks
     // (TSGO_RESEARCH_ENV: only builds with -DTSGO_TESTING see them, host/knobs.h).
@@ -323,6 +329,7 @@ template <typename T> struct Engine : IEngine {
         stage_timing = getenv("TSGO_STAGE_TIMING") != nullptr;
         if (const char* e = TSGO_RESEARCH_ENV("TSGO_SWEEPS_LIST")) for (const char* q = e; *q;) { sweeps_list.push_back(std::max(1, std::min(4, atoi(q)))); while (*q && *q != ',') ++q; if (*q == ',') ++q; }
         explicit0 = c.cycle_level0 != 0;
+        cyc64 = TSGO_CYCLE_VEC64();
         cy16 = c.cycle_storage != 32;
         if (const char* e = TSGO_RESEARCH_ENV("TSGO_HOST_PRODUCTS")) device_products = atoi(e) == 0;
         if (const char* e = TSGO_RESEARCH_ENV("TSGO_SYM_DECLINE")) sym_decline = atoi(e);
