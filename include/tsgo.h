@@ -226,6 +226,26 @@ typedef struct tsgo_prof_entry {
 } tsgo_prof_entry;
 int tsgo_profile_iteration(tsgo_optimizer* opt, int32_t reps, tsgo_prof_entry* out, int32_t cap);
 
+/* Marginal covariances: the diagonal blocks of H^-1, H = the Gauss-Newton matrix of ONE linearisation at the handle's current
+ * estimates (Huber weights, the gauge term once per occurrence in the fixed list, tsgo_config.odom_jacobian, virtual landmark edges;
+ * NOT the rules = 1 damping).  Per queried vertex id, in query order, 9 doubles of cov_out: the 3x3 block of a pose, row-major, or the
+ * 2x2 block of a landmark in the leading 2x2 (the other five entries 0); each block is symmetrised, (S + S^T) / 2.  A pose's block is
+ * (S^-1)_ii of the reduced pose system S = Hpp - W D^-1 W^T, a landmark's D_l^-1 + Y_l^T S^-1 Y_l with Y_l = W_{:,l} D_l^-1: 3 k + 2 m
+ * right-hand sides of S for k poses and m landmarks, solved a batch of columns per launch chain by PCG on the device with the handle's
+ * preconditioner.  rel_tol <= 0: the handle's pcg_rel_tol; every column stops by that rule on its own.  Duplicate ids are allowed;
+ * n_ids == 0 returns 0 and does nothing.  The estimates are not changed, and nothing the next tsgo_optimize reads is (DESIGN.md
+ * section 11).  Errors (< 0, text in tsgo_last_error): a NULL handle, no graph set, an unknown id, a graph without a fixed vertex (H is
+ * singular), precision = 32, an edge-sharded handle (world > 1: not supported). */
+typedef struct tsgo_marginal_stats {
+    int32_t columns, batches, batch_width;       /* right-hand sides solved, launch chains run, columns per chain */
+    int32_t pcg_iters_max;  int64_t pcg_iters_total;
+    int32_t preconditioner;                      /* 1 multigrid, 0 block-Jacobi: what the batches ran */
+    int32_t fallbacks;                           /* batches repeated with block-Jacobi after a cycle breakdown */
+    double ms_total, ms_solve;
+} tsgo_marginal_stats;
+int tsgo_marginals(tsgo_optimizer* opt, const uint32_t* ids, int32_t n_ids, double rel_tol,
+                   double* cov_out, tsgo_marginal_stats* stats /* may be NULL */);
+
 const char* tsgo_last_error(void);
 
 /* ---- host-only: wire codec (libtsgo_host.so and libtsgo_hip.so) ---------------------------------

@@ -118,6 +118,14 @@ public:
     }
     const tsgo_stats& Stats() const { return stats; }
 
+    // Marginal covariances at the estimates of the last Optimize (tsgo_marginals): 9 doubles per id, row-major; a landmark's 2x2 block
+    // in the leading 2x2.  Throws on an error (unknown id, no fixed vertex, no graph yet, precision 32).
+    std::vector<double> Marginals(const std::vector<uint32_t>& ids) {
+        std::vector<double> cov(ids.size() * 9);
+        if (tsgo_marginals(handle, ids.data(), (int32_t)ids.size(), 0.0, cov.data(), nullptr)) throw std::runtime_error(tsgo_last_error());
+        return cov;
+    }
+
 private:
     unsigned iterations;
     tsgo_optimizer* handle = nullptr;

@@ -24,6 +24,12 @@ class tsgo_stats(C.Structure):
                 ("pcg_fallbacks", C.c_int32), ("trace_len", C.c_int32), ("chi2_last", C.c_double), ("history_carried", C.c_int32), ("graph_replay", C.c_int32)]
 
 
+class tsgo_marginal_stats(C.Structure):
+    _fields_ = [("columns", C.c_int32), ("batches", C.c_int32), ("batch_width", C.c_int32), ("pcg_iters_max", C.c_int32),
+                ("pcg_iters_total", C.c_int64), ("preconditioner", C.c_int32), ("fallbacks", C.c_int32),
+                ("ms_total", C.c_double), ("ms_solve", C.c_double)]
+
+
 class tsgo_cycle_level(C.Structure):
     _fields_ = [("rows", C.c_int64), ("blocks", C.c_int64), ("sweeps_per_cycle", C.c_int32), ("lanes_per_row", C.c_int32),
                 ("us_per_sweep", C.c_double), ("bytes_per_sweep", C.c_double)]
@@ -56,7 +62,8 @@ HOST_SYMBOLS = ["tsgo_default_config", "tsgo_last_error", "tsgo_wire_decode", "t
                 "tsgo_wire_encode_response", "tsgo_wire_encode_request", "tsgo_synth_create", "tsgo_synth_view",
                 "tsgo_synth_truth", "tsgo_synth_free", "tsgo_layout_probe", "tsgo_amg_probe", "tsgo_amg_probe_shard"]
 DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_graph", "tsgo_reset_history", "tsgo_optimize", "tsgo_get_vertices",
-                  "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration"]
+                  "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
+                  "tsgo_marginals"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
 
@@ -100,6 +107,7 @@ def _declare_device(L):
     L.tsgo_time_kernel.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.tsgo_cycle_probe.argtypes = [vp, C.c_int32, C.POINTER(tsgo_cycle_level), C.c_int32]
     L.tsgo_profile_iteration.argtypes = [vp, C.c_int32, C.POINTER(tsgo_prof_entry), C.c_int32]
+    L.tsgo_marginals.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.POINTER(tsgo_marginal_stats)]
 
 
 def _declare_testing(L):

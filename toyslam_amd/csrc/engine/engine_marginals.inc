@@ -1,0 +1,344 @@
+// engine/engine_marginals.inc — part of `template <typename T> struct Engine` (tsgo_hip.hip includes it INSIDE the class body):
+// tsgo_marginals.  The diagonal blocks of H^-1 for a list of vertices, from NV columns of S X = B at a time (tsgo_marginal_kernels.h):
+// a pose takes its three unit columns, a landmark the two columns of Y_l = W_{:,l} Dl^-1 (DESIGN.md section 11).
+//
+// State rule: the call linearises at the current estimates (lambda = 0) and builds a fresh hierarchy IN the handle's own buffers, so
+// before it touches anything it copies every byte of the handle's device slabs aside and afterwards copies them back (plus the two host
+// fields these launches write: lambda and the smoother damping per level).  Everything the next tsgo_optimize reads is then what it
+// was, bit for bit; no counter of the solver (n_lins, lin_count, hier_age, the warm-start history, cycle storage, hier_shift) is touched.
+    // Columns per launch chain (research: TSGO_MARGINAL_WIDTH = 1, 8 or 16).  Measured at config 3 (profiles/r06_marginals_timing.jsonl):
+    // under the multigrid cycle 16 columns solve 264 columns/s against 139 at 8 and 24 at 1; block-Jacobi batches (thousands of short
+    // iterations) run 0.19 ms per iteration at 8 columns and 0.47 at 16, so they take 8.
+    int marginal_width() const {
+        const int w = TSGO_RESEARCH_INT("TSGO_MARGINAL_WIDTH", amg_on ? 16 : 8);
+        return w <= 1 ? 1 : (w <= 8 ? 8 : 16);
+    }
+    static constexpr int kMbChunkMg = 4, kMbChunkBj = 32;      // iterations enqueued between two looks at the batch's state
+
+    struct MbBuf {
+        T *x = nullptr, *r = nullptr, *z = nullptr, *p = nullptr, *q = nullptr, *s0 = nullptr, *t = nullptr;
+        T *dpart = nullptr, *gpart = nullptr, *fd = nullptr, *fg = nullptr;
+        MbState<T>* st[2] = {nullptr, nullptr};
+        MbColumn *cols = nullptr, *items = nullptr;
+        double* out = nullptr;
+        int* zero = nullptr;
+        std::vector<T*> lb, lz, lz2, lres;      // per level >= 1: right-hand side, iterate (two), residual
+        T *b_last = nullptr, *z_last = nullptr;
+        std::vector<T*> lfinal;                 // where each level's post-smoothed iterate ended (mb_cycle)
+        int nbV = 0;
+    };
+
+    // ---- launches ----
+    template <int NV> void mb_lm(const T* v, T* t, const int* stop) {
+        if (tl.n_slices == 0) return;
+        switch (pr.by_lm.G) {
+            case 1: hipLaunchKernelGGL((k_mb_schur_lm<T, 1, NV>), dim3(nbL), dim3(kBlock), 0, stream, tl, v, (const T*)ps, (const T*)ninv, t, stop); break;
+            case 2: hipLaunchKernelGGL((k_mb_schur_lm<T, 2, NV>), dim3(nbL), dim3(kBlock), 0, stream, tl, v, (const T*)ps, (const T*)ninv, t, stop); break;
+            case 4: hipLaunchKernelGGL((k_mb_schur_lm<T, 4, NV>), dim3(nbL), dim3(kBlock), 0, stream, tl, v, (const T*)ps, (const T*)ninv, t, stop); break;
+            default: hipLaunchKernelGGL((k_mb_schur_lm<T, 8, NV>), dim3(nbL), dim3(kBlock), 0, stream, tl, v, (const T*)ps, (const T*)ninv, t, stop); break;
+        }
+    }
+    template <int NV, int MODE, int OJ> void mb_pose_oj(const T* v, const T* t, T* out, const T* rvec, T* dpart, const int* stop) {
+        switch (pr.by_pose.G) {
+            case 1: hipLaunchKernelGGL((k_mb_schur_pose<T, 1, OJ, NV, MODE>), dim3(nbP), dim3(kBlock), 0, stream, tp, to, v, t, (const T*)ps, (const T*)dp, out, rvec, dpart, stop); break;
+            case 2: hipLaunchKernelGGL((k_mb_schur_pose<T, 2, OJ, NV, MODE>), dim3(nbP), dim3(kBlock), 0, stream, tp, to, v, t, (const T*)ps, (const T*)dp, out, rvec, dpart, stop); break;
+            case 4: hipLaunchKernelGGL((k_mb_schur_pose<T, 4, OJ, NV, MODE>), dim3(nbP), dim3(kBlock), 0, stream, tp, to, v, t, (const T*)ps, (const T*)dp, out, rvec, dpart, stop); break;
+            default: hipLaunchKernelGGL((k_mb_schur_pose<T, 8, OJ, NV, MODE>), dim3(nbP), dim3(kBlock), 0, stream, tp, to, v, t, (const T*)ps, (const T*)dp, out, rvec, dpart, stop); break;
+        }
+    }
+    // S v (MODE 0: + partials of v^T S v; 2: without) or rvec - S v (MODE 1), all NV columns
+    template <int NV, int MODE> void mb_product(MbBuf& B, const T* v, T* out, const T* rvec, const int* stop) {
+        mb_lm<NV>(v, B.t, stop);
+        if (oj()) mb_pose_oj<NV, MODE, 1>(v, B.t, out, rvec, B.dpart, stop);
+        else mb_pose_oj<NV, MODE, 0>(v, B.t, out, rvec, B.dpart, stop);
+    }
+    template <int NV, int MODE> void mb_bsr(int n, const int* ptr, const int* col, const H* M, const T* x, const T* b, const H* dinv, const T* omega, T* out, const int* stop) {
+        hipLaunchKernelGGL((k_mb_bsr<T, NV, MODE>), dim3(grid_for(n * NV)), dim3(kBlock), 0, stream, n, ptr, col, M, x, b, dinv, omega, out, stop);
+    }
+    // z = V-cycle(r) on the handle's hierarchy, NV columns: level 0 with the implicit Schur passes and Minv (one sweep per side), the levels
+    // below with their block-indexed matrices (nu_at(l) block-Jacobi sweeps per side), the coarsest one through its dense inverse.  Same
+    // number of sweeps on both sides and R = P^T: a symmetric preconditioner.
+    template <int NV> void mb_cycle(MbBuf& B, const T* r, T* z, const int* stop) {
+        const int P = pr.P;
+        const size_t nl = lv.size();
+        const int gv = grid_for(P * NV);
+        hipLaunchKernelGGL((k_mb_smooth0<T, NV, 0>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)minv, (const T*)omega_dev, r, (const T*)nullptr, z, stop);
+        mb_product<NV, 1>(B, z, B.s0, r, stop);
+        mb_bsr<NV, 2>(lv[0].n_agg, lv[0].R_ptr, lv[0].R_col, (const H*)lv[0].Rv, B.s0, nullptr, nullptr, nullptr, nl > 1 ? B.lb[1] : B.b_last, stop);
+        for (size_t l = 1; l < nl; ++l) {
+            DevLevel<T>& L = lv[l];
+            const int nu = nu_at(l);
+            T* cur = B.lz[l]; T* oth = B.lz2[l];
+            mb_bsr<NV, 1>(L.n, L.A_ptr, L.A_col, (const H*)L.A, nullptr, B.lb[l], (const H*)L.Dinv, omega_dev + l, cur, stop);
+            for (int sw = 1; sw < nu; ++sw) { mb_bsr<NV, 1>(L.n, L.A_ptr, L.A_col, (const H*)L.A, cur, B.lb[l], (const H*)L.Dinv, omega_dev + l, oth, stop); std::swap(cur, oth); }
+            mb_bsr<NV, 0>(L.n, L.A_ptr, L.A_col, (const H*)L.A, cur, B.lb[l], nullptr, nullptr, B.lres[l], stop);
+            mb_bsr<NV, 2>(L.n_agg, L.R_ptr, L.R_col, (const H*)L.Rv, B.lres[l], nullptr, nullptr, nullptr, l + 1 < nl ? B.lb[l + 1] : B.b_last, stop);
+            B.lfinal[l] = cur;
+        }
+        hipLaunchKernelGGL((k_mb_dense<T, NV>), dim3(grid_for(nb_last * NV)), dim3(kBlock), 0, stream, nb_last, (const T*)inv_last, (const T*)B.b_last, B.z_last, stop);
+        for (size_t l = nl - 1; l >= 1; --l) {
+            DevLevel<T>& L = lv[l];
+            const int nu = nu_at(l);
+            T* cur = B.lfinal[l]; T* oth = cur == B.lz[l] ? B.lz2[l] : B.lz[l];
+            mb_bsr<NV, 3>(L.n, L.P_ptr, L.P_col, (const H*)L.P, l + 1 < nl ? B.lfinal[l + 1] : B.z_last, nullptr, nullptr, nullptr, cur, stop);
+            for (int sw = 0; sw < nu; ++sw) { mb_bsr<NV, 1>(L.n, L.A_ptr, L.A_col, (const H*)L.A, cur, B.lb[l], (const H*)L.Dinv, omega_dev + l, oth, stop); std::swap(cur, oth); }
+            B.lfinal[l] = cur;
+        }
+        mb_bsr<NV, 3>(lv[0].n, lv[0].P_ptr, lv[0].P_col, (const H*)lv[0].P, nl > 1 ? B.lfinal[1] : B.z_last, nullptr, nullptr, nullptr, z, stop);
+        mb_product<NV, 2>(B, z, B.s0, nullptr, stop);
+        hipLaunchKernelGGL((k_mb_smooth0<T, NV, 1>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)minv, (const T*)omega_dev, r, (const T*)B.s0, z, stop);
+    }
+
+    // PCG on one batch (columns already in B.cols): X = S^-1 B, column by column.  out: the largest / summed iterations, and whether
+    // any column broke down (1) or ran out of iterations (2).
+    template <int NV> int mb_solve(MbBuf& B, bool mg, double tol, int* it_max, int64_t* it_sum, int* fail_out) {
+        const int P = pr.P;
+        const size_t vb = (size_t)P * NV * 3 * sizeof(T);
+        HIP_OK(hipMemsetAsync(B.x, 0, vb, stream));
+        HIP_OK(hipMemsetAsync(B.r, 0, vb, stream));
+        hipLaunchKernelGGL((k_mb_rhs<T, NV>), dim3(1), dim3(64), 0, stream, tl, pr.by_lm.G, (const T*)ps, (const T*)lmrec, (const MbColumn*)B.cols, B.r);
+        const int gv = grid_for(P * NV);
+        if (mg) {
+            mb_cycle<NV>(B, B.r, B.z, B.zero);
+            hipLaunchKernelGGL((k_mb_dots<T, NV, 0>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.r, B.z, (const T*)minv, B.gpart, (const int*)B.zero);
+        } else hipLaunchKernelGGL((k_mb_dots<T, NV, 1>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.r, B.z, (const T*)minv, B.gpart, (const int*)B.zero);
+        hipLaunchKernelGGL((k_mb_fold<T>), dim3(1), dim3(kBlock), 0, stream, gv, 2 * NV, (const T*)B.gpart, B.fg, (const int*)B.zero);
+        hipLaunchKernelGGL((k_mb_start<T, NV>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.fg, (const T*)B.z, B.p, B.st[0]);
+        const T tol2 = (T)(tol * tol);
+        const int chunk = mg ? kMbChunkMg : kMbChunkBj;
+        MbState<T> hs;
+        int launched = 0;
+        for (;;) {
+            for (int j = 0; j < chunk; ++j, ++launched) {
+                const int s = launched & 1;
+                const int* stop = reinterpret_cast<const int*>(B.st[s]);      // MbState::all_done
+                mb_product<NV, 0>(B, B.p, B.q, nullptr, stop);
+                hipLaunchKernelGGL((k_mb_fold<T>), dim3(1), dim3(kBlock), 0, stream, nbP, NV, (const T*)B.dpart, B.fd, stop);
+                hipLaunchKernelGGL((k_mb_alpha<T, NV>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.fd, (const MbState<T>*)B.st[s], (const T*)B.p, (const T*)B.q, B.x, B.r);
+                if (mg) {
+                    mb_cycle<NV>(B, B.r, B.z, stop);
+                    hipLaunchKernelGGL((k_mb_dots<T, NV, 0>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.r, B.z, (const T*)minv, B.gpart, stop);
+                } else hipLaunchKernelGGL((k_mb_dots<T, NV, 1>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.r, B.z, (const T*)minv, B.gpart, stop);
+                hipLaunchKernelGGL((k_mb_fold<T>), dim3(1), dim3(kBlock), 0, stream, gv, 2 * NV, (const T*)B.gpart, B.fg, stop);
+                hipLaunchKernelGGL((k_mb_beta<T, NV>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.fd, (const T*)B.fg, (const MbState<T>*)B.st[s], B.st[s ^ 1],
+                                   (const T*)B.z, B.p, tol2, cfg.pcg_max_iters);
+            }
+            HIP_OK(hipMemcpyAsync(&hs, B.st[launched & 1], sizeof(hs), hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            if (hs.all_done) break;
+            if (launched > cfg.pcg_max_iters + 2 * chunk) return set_error(-20, "tsgo_marginals: PCG did not terminate");
+        }
+        int imax = 0, fail = 0; int64_t isum = 0;
+        for (int c = 0; c < NV; ++c) { imax = std::max(imax, hs.col[c].iters); isum += hs.col[c].iters; fail = std::max(fail, hs.col[c].fail); }
+        *it_max = imax; *it_sum = isum; *fail_out = fail;
+        return 0;
+    }
+
+    int mb_alloc(MbBuf& B, int NV, char** base) {
+        const int P = pr.P;
+        B.nbV = grid_for(P * NV);
+        std::vector<std::pair<void**, size_t>> want;
+        const size_t pv = (size_t)P * NV * 3 * sizeof(T);
+        for (T** v : {&B.x, &B.r, &B.z, &B.p, &B.q, &B.s0}) want.push_back({(void**)v, pv});
+        want.push_back({(void**)&B.t, (size_t)std::max(pr.L, 1) * NV * 2 * sizeof(T)});
+        want.push_back({(void**)&B.dpart, (size_t)nbP * NV * sizeof(T)});
+        want.push_back({(void**)&B.gpart, (size_t)B.nbV * 2 * NV * sizeof(T)});
+        want.push_back({(void**)&B.fd, (size_t)NV * sizeof(T)});
+        want.push_back({(void**)&B.fg, (size_t)2 * NV * sizeof(T)});
+        want.push_back({(void**)&B.st[0], sizeof(MbState<T>)});
+        want.push_back({(void**)&B.st[1], sizeof(MbState<T>)});
+        want.push_back({(void**)&B.cols, (size_t)kMbMaxWidth * sizeof(MbColumn)});
+        want.push_back({(void**)&B.items, (size_t)kMbMaxWidth * sizeof(MbColumn)});
+        want.push_back({(void**)&B.out, (size_t)kMbMaxWidth * 9 * sizeof(double)});
+        want.push_back({(void**)&B.zero, 4 * sizeof(int)});
+        const size_t nl = amg_on ? lv.size() : 0;
+        B.lb.assign(nl, nullptr); B.lz.assign(nl, nullptr); B.lz2.assign(nl, nullptr); B.lres.assign(nl, nullptr); B.lfinal.assign(nl, nullptr);
+        for (size_t l = 1; l < nl; ++l) {
+            const size_t lvb = (size_t)lv[l].n * NV * 3 * sizeof(T);
+            for (T** v : {&B.lb[l], &B.lz[l], &B.lz2[l], &B.lres[l]}) want.push_back({(void**)v, lvb});
+        }
+        if (amg_on) {
+            want.push_back({(void**)&B.b_last, (size_t)nb_last * NV * 3 * sizeof(T)});
+            want.push_back({(void**)&B.z_last, (size_t)nb_last * NV * 3 * sizeof(T)});
+        }
+        size_t total = 0;
+        for (auto& w : want) total += (w.second + 255) & ~size_t(255);
+        HIP_OK(hipMalloc((void**)base, total));
+        size_t off = 0;
+        for (auto& w : want) { *w.first = *base + off; off += (w.second + 255) & ~size_t(255); }
+        HIP_OK(hipMemsetAsync(*base, 0, total, stream));
+        return 0;
+    }
+
+    struct MbQuery { int kind, idx; };
+    // the batches of one query list: queries are packed whole (3 columns a pose, 2 a landmark) into batches of NV columns
+    template <int NV> int mb_run(const std::vector<MbQuery>& qs, double tol, double* cov, tsgo_marginal_stats& s) {
+        MbBuf B; char* base = nullptr;
+        struct Free { char*& b; ~Free() { if (b) (void)hipFree(b); } } fr{base};
+        if (int rc = mb_alloc(B, NV, &base)) return rc;
+        s.batch_width = NV;
+        s.preconditioner = amg_on ? 1 : 0;
+        float ms = 0;
+        size_t q0 = 0;
+        while (q0 < qs.size()) {
+            std::vector<MbColumn> cols(kMbMaxWidth, MbColumn{-1, 0, 0, 0}), items;
+            int nc = 0; size_t q1 = q0;
+            while (q1 < qs.size()) {
+                const int need = qs[q1].kind == 0 ? 3 : 2;
+                if (nc + need > NV && nc > 0) break;
+                if (need > NV) {      // width 1: one column per batch, a query over several batches
+                    break;
+                }
+                items.push_back(MbColumn{qs[q1].kind, qs[q1].idx, nc, 0});
+                for (int k = 0; k < need; ++k) cols[nc + k] = MbColumn{qs[q1].kind, qs[q1].idx, k, 0};
+                nc += need; ++q1;
+            }
+            if (q1 == q0) return mb_run_narrow<NV>(B, qs, q0, tol, cov, s);      // NV < 3: columns one by one
+            HIP_OK(hipMemcpyAsync(B.cols, cols.data(), cols.size() * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
+            HIP_OK(hipMemcpyAsync(B.items, items.data(), items.size() * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
+            if (int rc = mb_batch<NV>(B, tol, s, &ms)) return rc;
+            std::vector<double> o(items.size() * 9);
+            hipLaunchKernelGGL((k_mb_extract<T, NV>), dim3(1), dim3(64), 0, stream, tl, pr.by_lm.G, (int)items.size(), (const T*)ps, (const T*)lmrec, (const MbColumn*)B.items, (const T*)B.x, B.out);
+            HIP_OK(hipMemcpyAsync(o.data(), B.out, o.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            for (size_t k = 0; k < items.size(); ++k) mb_store(o.data() + 9 * k, cov + 9 * (q0 + k));
+            s.columns += nc;
+            q0 = q1;
+        }
+        s.ms_solve = ms;
+        return 0;
+    }
+    static void mb_store(const double* m, double* out) {      // (Sigma + Sigma^T) / 2
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) out[3 * a + b] = 0.5 * (m[3 * a + b] + m[3 * b + a]);
+    }
+    // one batch: the handle's preconditioner, repeated with block-Jacobi after a breakdown of the cycle
+    template <int NV> int mb_batch(MbBuf& B, double tol, tsgo_marginal_stats& s, float* ms_acc) {
+        HIP_OK(hipEventRecord(ev[0], stream));
+        int imax = 0, fail = 0; int64_t isum = 0;
+        if (int rc = mb_solve<NV>(B, amg_on, tol, &imax, &isum, &fail)) return rc;
+        ++s.batches;
+        s.pcg_iters_max = std::max(s.pcg_iters_max, imax); s.pcg_iters_total += isum;
+        if (fail == 1 && amg_on) {
+            ++s.fallbacks; s.preconditioner = 0;
+            if (int rc = mb_solve<NV>(B, false, tol, &imax, &isum, &fail)) return rc;
+            ++s.batches;
+            s.pcg_iters_max = std::max(s.pcg_iters_max, imax); s.pcg_iters_total += isum;
+        }
+        HIP_OK(hipEventRecord(ev[1], stream));
+        HIP_OK(hipEventSynchronize(ev[1]));
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        *ms_acc += ms;
+        if (fail == 1) return set_error(-21, "tsgo_marginals: PCG breakdown");
+        if (fail != 0) return set_error(-22, "tsgo_marginals: PCG did not converge within pcg_max_iters");
+        return 0;
+    }
+    // width 1 (the research baseline): a query's columns in batches of their own; the read-out gathers them from three / two solves
+    template <int NV> int mb_run_narrow(MbBuf& B, const std::vector<MbQuery>& qs, size_t q0, double tol, double* cov, tsgo_marginal_stats& s) {
+        float ms = 0;
+        const int P = pr.P;
+        std::vector<T> xall;
+        for (size_t q = q0; q < qs.size(); ++q) {
+            const int need = qs[q].kind == 0 ? 3 : 2;
+            // X columns of this query, gathered on the host into a [P][need][3] block, then read out with the same kernel
+            xall.assign((size_t)P * need * 3, T(0));
+            std::vector<T> col((size_t)P * NV * 3);
+            for (int k = 0; k < need; ++k) {
+                std::vector<MbColumn> cols(kMbMaxWidth, MbColumn{-1, 0, 0, 0});
+                cols[0] = MbColumn{qs[q].kind, qs[q].idx, k, 0};
+                HIP_OK(hipMemcpyAsync(B.cols, cols.data(), cols.size() * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
+                if (int rc = mb_batch<NV>(B, tol, s, &ms)) return rc;
+                HIP_OK(hipMemcpyAsync(col.data(), B.x, col.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
+                HIP_OK(hipStreamSynchronize(stream));
+                for (int i = 0; i < P; ++i) for (int m = 0; m < 3; ++m) xall[((size_t)i * need + k) * 3 + m] = col[(size_t)i * NV * 3 + m];
+                s.columns += 1;
+            }
+            T* xd = nullptr;
+            HIP_OK(hipMalloc((void**)&xd, xall.size() * sizeof(T)));
+            struct FreeX { T* p; ~FreeX() { (void)hipFree(p); } } fx{xd};
+            HIP_OK(hipMemcpyAsync(xd, xall.data(), xall.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+            MbColumn it{qs[q].kind, qs[q].idx, 0, 0};
+            HIP_OK(hipMemcpyAsync(B.items, &it, sizeof(it), hipMemcpyHostToDevice, stream));
+            double o[9];
+            if (need == 3) hipLaunchKernelGGL((k_mb_extract<T, 3>), dim3(1), dim3(64), 0, stream, tl, pr.by_lm.G, 1, (const T*)ps, (const T*)lmrec, (const MbColumn*)B.items, (const T*)xd, B.out);
+            else hipLaunchKernelGGL((k_mb_extract<T, 2>), dim3(1), dim3(64), 0, stream, tl, pr.by_lm.G, 1, (const T*)ps, (const T*)lmrec, (const MbColumn*)B.items, (const T*)xd, B.out);
+            HIP_OK(hipMemcpyAsync(o, B.out, sizeof(o), hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            mb_store(o, cov + 9 * q);
+        }
+        s.ms_solve += ms;
+        return 0;
+    }
+
+    // the whole call between the snapshot and the restore
+    int mb_compute(const std::vector<MbQuery>& qs, double tol, double* cov, tsgo_marginal_stats& s) {
+        // ONE linearisation at the current estimates, without damping, and a hierarchy built for it
+        lambda = 0;
+        launch_lin();
+        launch_finalize();
+        if (amg_on) {
+            if (int rc = launch_amg_setup()) return rc;
+            if (int rc = estimate_damping()) return rc;
+            if (int rc = launch_bottom_setup()) return rc;
+        }
+        switch (marginal_width()) {
+            case 1: return mb_run<1>(qs, tol, cov, s);
+            case 16: return mb_run<16>(qs, tol, cov, s);
+            default: return mb_run<8>(qs, tol, cov, s);
+        }
+    }
+
+    int marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, tsgo_marginal_stats* st_out) override {
+        const auto wall0 = std::chrono::steady_clock::now();
+        tsgo_marginal_stats s; std::memset(&s, 0, sizeof(s));
+        if (sizeof(T) != 8) return set_error(-1, "tsgo_marginals: needs precision = 64 (with the gauge, cond(H) is about 2e7: f32 marginals would be noise)");
+        if (collective()) return set_error(-1, "tsgo_marginals: edge-sharded handles (world > 1) are not supported");
+        if (!have_graph_data) return set_error(-3, "tsgo_marginals: no graph set");
+        if (n_ids < 0 || (n_ids > 0 && (!ids || !cov))) return set_error(-1, "tsgo_marginals: bad argument");
+        if (n_ids == 0) { if (st_out) *st_out = s; return 0; }
+        bool fixed = false;
+        for (double g : pr.gauge_p) fixed |= g > 0;
+        for (double g : pr.gauge_l) fixed |= g > 0;
+        if (!fixed) return set_error(-1, "tsgo_marginals: marginals need a fixed vertex (without one H is singular)");
+        std::vector<MbQuery> qs((size_t)n_ids);
+        {
+            std::unordered_map<uint32_t, int> pos; pos.reserve(structure.v_id.size() * 2);
+            for (size_t v = 0; v < structure.v_id.size(); ++v) pos.emplace(structure.v_id[v], (int)v);
+            std::vector<MbQuery> of_vertex((size_t)pr.n_vertices, MbQuery{-1, 0});
+            for (int i = 0; i < pr.P; ++i) of_vertex[(size_t)pr.pose_vertex[i]] = MbQuery{0, i};
+            for (int l = 0; l < pr.L; ++l) of_vertex[(size_t)pr.lm_vertex[l]] = MbQuery{1, l};
+            for (int k = 0; k < n_ids; ++k) {
+                auto it = pos.find(ids[k]);
+                if (it == pos.end() || of_vertex[(size_t)it->second].kind < 0) return set_error(-1, "tsgo_marginals: unknown vertex id " + std::to_string(ids[k]));
+                qs[(size_t)k] = of_vertex[(size_t)it->second];
+            }
+        }
+        HIP_OK(hipSetDevice(cfg.device));
+        const double tol = rel_tol > 0 ? rel_tol : cfg.pcg_rel_tol;
+        // snapshot of every device byte the handle owns (see the top of this file)
+        size_t total = 0;
+        for (const Slab& sl : slabs) total += sl.used;
+        char* snap = nullptr;
+        HIP_OK(hipMalloc((void**)&snap, std::max<size_t>(total, 1)));
+        {
+            size_t off = 0;
+            for (const Slab& sl : slabs) { if (sl.used) { const hipError_t e = hipMemcpyAsync(snap + off, sl.base, sl.used, hipMemcpyDeviceToDevice, stream); if (e != hipSuccess) { (void)hipFree(snap); HIP_OK(e); } } off += sl.used; }
+        }
+        const double lambda0 = lambda;
+        const std::vector<double> omega0 = omega_host;
+        const int rc = mb_compute(qs, tol, cov, s);
+        lambda = lambda0; omega_host = omega0;
+        const std::string err = rc ? std::string(tsgo_last_error()) : std::string();
+        {
+            size_t off = 0;
+            for (const Slab& sl : slabs) { if (sl.used) { const hipError_t e = hipMemcpyAsync(sl.base, snap + off, sl.used, hipMemcpyDeviceToDevice, stream); if (e != hipSuccess) { (void)hipFree(snap); HIP_OK(e); } } off += sl.used; }
+        }
+        const hipError_t es = hipStreamSynchronize(stream);
+        (void)hipFree(snap);
+        HIP_OK(es);
+        if (rc) return set_error(rc, err);
+        s.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+        if (st_out) *st_out = s;
+        return 0;
+    }

@@ -1,6 +1,6 @@
 // tsgo_hip.hip — device side of the C ABI in include/tsgo.h: buffers, launches, the Gauss-Newton
 // loop with the reference's stop rules (remote/optimizer/OptimizerCpu.h:80-180), hipGraph replay of
-// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h.
+// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h.
 //
 // One translation unit; the engine class is laid out over this file and engine/*.inc (each included inside the class body):
 //   this file                      members, configuration / environment (host/knobs.h), device slabs and upload helpers; the C ABI at the end
@@ -10,6 +10,7 @@
 //   engine/engine_collective.inc   the all-reduces of an edge-sharded run
 //   engine/engine_solve.inc        the Gauss-Newton loop, the PCG drivers, read-outs
 //   engine/engine_probes.inc       timing probes (bench.py)
+//   engine/engine_marginals.inc    tsgo_marginals: batched PCG for diagonal blocks of H^-1
 //
 // There is NO CPU fallback in this file: every entry point that computes needs a gfx950 device and
 // returns an error otherwise.
@@ -42,6 +43,7 @@
 #include "host/problem.h"
 #include "tsgo_amg_kernels.h"
 #include "tsgo_kernels.h"
+#include "tsgo_marginal_kernels.h"
 #include "tsgo_sym_kernels.h"
 
 namespace {
@@ -152,6 +154,7 @@ struct IEngine {
     virtual int comm_selftest(int* ranks_out) = 0;
     virtual int comm_time_allreduce(int64_t n, int reps, double* us) = 0;
     virtual void reset_history() = 0;
+    virtual int marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, tsgo_marginal_stats* st) = 0;
     ncclComm_t comm = nullptr;
     tsgo_local_group* lgroup = nullptr;      // in-process stand-in for the communicator (tests on a one-GPU box; always null outside TSGO_TESTING builds)
 };
@@ -425,6 +428,7 @@ template <typename T> struct Engine : IEngine {
 #include "engine/engine_collective.inc"
 #include "engine/engine_solve.inc"
 #include "engine/engine_probes.inc"
+#include "engine/engine_marginals.inc"
 };
 
 }  // namespace
@@ -512,6 +516,10 @@ int tsgo_comm_init_local(tsgo_optimizer* o, tsgo_local_group* g) {
     return 0;
 }
 #endif
+int tsgo_marginals(tsgo_optimizer* o, const uint32_t* ids, int32_t n_ids, double rel_tol, double* cov_out, tsgo_marginal_stats* stats) {
+    if (!o) return tsgo::set_error(-1, "tsgo_marginals: null handle");
+    return o->eng->marginals(ids, n_ids, rel_tol, cov_out, stats);
+}
 void tsgo_reset_history(tsgo_optimizer* o) {
     if (o && o->eng) o->eng->reset_history();
 }

@@ -105,6 +105,16 @@ class HipOptimizer:
                    "tsgo_solve_step")
         return dict(delta=d, chi2=chi.value, cg_iters=it.value)
 
+    def marginals(self, ids, rel_tol=0.0):
+        """Marginal covariances (diagonal blocks of H^-1 at the current estimates) of the vertices `ids`, in order: cov[k] is the 3x3
+        block of a pose, or the 2x2 block of a landmark in cov[k, :2, :2] (zeros elsewhere).  rel_tol <= 0: the handle's pcg_rel_tol."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
+        cov = np.zeros((len(ids), 3, 3))
+        st = _lib.tsgo_marginal_stats()
+        _lib.check(self.lib, self.lib.tsgo_marginals(self.h, ids.ctypes.data if len(ids) else None, len(ids), float(rel_tol),
+                                                      cov.ctypes.data, C.byref(st)), "tsgo_marginals")
+        return cov, {f: getattr(st, f) for f, _t in st._fields_}
+
     def time_kernel(self, which, reps=50):
         us = C.c_double(); nbytes = C.c_double()
         _lib.check(self.lib, self.lib.tsgo_time_kernel(self.h, which, reps, C.byref(us), C.byref(nbytes)),
