@@ -246,6 +246,17 @@ typedef struct tsgo_marginal_stats {
 int tsgo_marginals(tsgo_optimizer* opt, const uint32_t* ids, int32_t n_ids, double rel_tol,
                    double* cov_out, tsgo_marginal_stats* stats /* may be NULL */);
 
+/* Joint marginal covariance: the whole block of H^-1 (the same H as tsgo_marginals) over the queried vertices, cross blocks included
+ * (pose-pose, pose-landmark, landmark-landmark).  Rows and columns are compact and in query order: a pose takes 3, a landmark 2, no
+ * padding, so D = 3 (pose ids) + 2 (landmark ids).  cov_out is D x D doubles, row-major, symmetrised (C + C^T) / 2.  Two calls: with
+ * cov_out == NULL the call writes D to *dim_out and solves nothing; then with cov_cap >= D * D (entries, not bytes).  dim_out may be
+ * NULL when cov_out is not; if given it always receives D once the ids are resolved.  Duplicate ids give repeated rows; n_ids == 0
+ * gives D = 0 and returns 0.  It solves the D columns of the query (3 unit columns per pose, the 2 columns of Y_l per landmark) a batch
+ * at a time; every batch but the last is full.  The state rule of tsgo_marginals holds: nothing the next tsgo_optimize reads changes.
+ * Errors (< 0): those of tsgo_marginals, cov_cap < D * D, and D > 8192 (a 512 MB result). */
+int tsgo_joint_marginals(tsgo_optimizer* opt, const uint32_t* ids, int32_t n_ids, double rel_tol,
+                         double* cov_out, int64_t cov_cap, int32_t* dim_out, tsgo_marginal_stats* stats /* may be NULL */);
+
 const char* tsgo_last_error(void);
 
 /* ---- host-only: wire codec (libtsgo_host.so and libtsgo_hip.so) ---------------------------------

@@ -126,6 +126,18 @@ public:
         return cov;
     }
 
+    // Joint marginal covariance of the vertices `ids` (tsgo_joint_marginals): D x D doubles, row-major, rows and columns in query order,
+    // 3 per pose and 2 per landmark; *dim (if given) receives D.  Throws on an error (those of Marginals, and D > 8192).
+    std::vector<double> JointMarginals(const std::vector<uint32_t>& ids, int* dim = nullptr) {
+        int32_t d = 0;
+        if (tsgo_joint_marginals(handle, ids.data(), (int32_t)ids.size(), 0.0, nullptr, 0, &d, nullptr)) throw std::runtime_error(tsgo_last_error());
+        std::vector<double> cov((size_t)d * (size_t)d);
+        if (d > 0 && tsgo_joint_marginals(handle, ids.data(), (int32_t)ids.size(), 0.0, cov.data(), (int64_t)cov.size(), &d, nullptr))
+            throw std::runtime_error(tsgo_last_error());
+        if (dim) *dim = d;
+        return cov;
+    }
+
 private:
     unsigned iterations;
     tsgo_optimizer* handle = nullptr;

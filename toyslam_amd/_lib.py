@@ -63,7 +63,7 @@ HOST_SYMBOLS = ["tsgo_default_config", "tsgo_last_error", "tsgo_wire_decode", "t
                 "tsgo_synth_truth", "tsgo_synth_free", "tsgo_layout_probe", "tsgo_amg_probe", "tsgo_amg_probe_shard"]
 DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_graph", "tsgo_reset_history", "tsgo_optimize", "tsgo_get_vertices",
                   "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
-                  "tsgo_marginals"]
+                  "tsgo_marginals", "tsgo_joint_marginals"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
 
@@ -108,6 +108,7 @@ def _declare_device(L):
     L.tsgo_cycle_probe.argtypes = [vp, C.c_int32, C.POINTER(tsgo_cycle_level), C.c_int32]
     L.tsgo_profile_iteration.argtypes = [vp, C.c_int32, C.POINTER(tsgo_prof_entry), C.c_int32]
     L.tsgo_marginals.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.POINTER(tsgo_marginal_stats)]
+    L.tsgo_joint_marginals.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.c_int64, C.POINTER(C.c_int32), C.POINTER(tsgo_marginal_stats)]
 
 
 def _declare_testing(L):

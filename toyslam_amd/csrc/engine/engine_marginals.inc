@@ -1,6 +1,7 @@
 // engine/engine_marginals.inc — part of `template <typename T> struct Engine` (tsgo_hip.hip includes it INSIDE the class body):
-// tsgo_marginals.  The diagonal blocks of H^-1 for a list of vertices, from NV columns of S X = B at a time (tsgo_marginal_kernels.h):
-// a pose takes its three unit columns, a landmark the two columns of Y_l = W_{:,l} Dl^-1 (DESIGN.md section 11).
+// tsgo_marginals and tsgo_joint_marginals.  The diagonal blocks (or the whole joint block) of H^-1 for a list of vertices, from NV columns
+// of S X = B at a time (tsgo_marginal_kernels.h): a pose takes its three unit columns, a landmark the two columns of Y_l = W_{:,l} Dl^-1
+// (DESIGN.md section 11).
 //
 // State rule: the call linearises at the current estimates (lambda = 0) and builds a fresh hierarchy IN the handle's own buffers, so
 // before it touches anything it copies every byte of the handle's device slabs aside and afterwards copies them back (plus the two host
@@ -271,9 +272,8 @@
         return 0;
     }
 
-    // the whole call between the snapshot and the restore
-    int mb_compute(const std::vector<MbQuery>& qs, double tol, double* cov, tsgo_marginal_stats& s) {
-        // ONE linearisation at the current estimates, without damping, and a hierarchy built for it
+    // ONE linearisation at the current estimates, without damping, and a hierarchy built for it (both entry points)
+    int mb_prepare() {
         lambda = 0;
         launch_lin();
         launch_finalize();
@@ -282,6 +282,12 @@
             if (int rc = estimate_damping()) return rc;
             if (int rc = launch_bottom_setup()) return rc;
         }
+        return 0;
+    }
+
+    // the whole call between the snapshot and the restore
+    int mb_compute(const std::vector<MbQuery>& qs, double tol, double* cov, tsgo_marginal_stats& s) {
+        if (int rc = mb_prepare()) return rc;
         switch (marginal_width()) {
             case 1: return mb_run<1>(qs, tol, cov, s);
             case 16: return mb_run<16>(qs, tol, cov, s);
@@ -289,34 +295,38 @@
         }
     }
 
-    int marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, tsgo_marginal_stats* st_out) override {
-        const auto wall0 = std::chrono::steady_clock::now();
-        tsgo_marginal_stats s; std::memset(&s, 0, sizeof(s));
-        if (sizeof(T) != 8) return set_error(-1, "tsgo_marginals: needs precision = 64 (with the gauge, cond(H) is about 2e7: f32 marginals would be noise)");
-        if (collective()) return set_error(-1, "tsgo_marginals: edge-sharded handles (world > 1) are not supported");
-        if (!have_graph_data) return set_error(-3, "tsgo_marginals: no graph set");
-        if (n_ids < 0 || (n_ids > 0 && (!ids || !cov))) return set_error(-1, "tsgo_marginals: bad argument");
-        if (n_ids == 0) { if (st_out) *st_out = s; return 0; }
+    // The shell both entry points share.  mb_queries: the handle's checks and the id -> (pose | landmark, index) map (`name` prefixes
+    // the errors; out_null: the caller's output pointer is missing where it is required).  n_ids == 0 returns 0 with qs empty before
+    // the fixed-vertex check.
+    int mb_queries(const char* name, const uint32_t* ids, int n_ids, bool out_null, std::vector<MbQuery>& qs) {
+        const std::string nm(name);
+        qs.clear();
+        if (sizeof(T) != 8) return set_error(-1, nm + ": needs precision = 64 (with the gauge, cond(H) is about 2e7: f32 marginals would be noise)");
+        if (collective()) return set_error(-1, nm + ": edge-sharded handles (world > 1) are not supported");
+        if (!have_graph_data) return set_error(-3, nm + ": no graph set");
+        if (n_ids < 0 || (n_ids > 0 && (!ids || out_null))) return set_error(-1, nm + ": bad argument");
+        if (n_ids == 0) return 0;
         bool fixed = false;
         for (double g : pr.gauge_p) fixed |= g > 0;
         for (double g : pr.gauge_l) fixed |= g > 0;
-        if (!fixed) return set_error(-1, "tsgo_marginals: marginals need a fixed vertex (without one H is singular)");
-        std::vector<MbQuery> qs((size_t)n_ids);
-        {
-            std::unordered_map<uint32_t, int> pos; pos.reserve(structure.v_id.size() * 2);
-            for (size_t v = 0; v < structure.v_id.size(); ++v) pos.emplace(structure.v_id[v], (int)v);
-            std::vector<MbQuery> of_vertex((size_t)pr.n_vertices, MbQuery{-1, 0});
-            for (int i = 0; i < pr.P; ++i) of_vertex[(size_t)pr.pose_vertex[i]] = MbQuery{0, i};
-            for (int l = 0; l < pr.L; ++l) of_vertex[(size_t)pr.lm_vertex[l]] = MbQuery{1, l};
-            for (int k = 0; k < n_ids; ++k) {
-                auto it = pos.find(ids[k]);
-                if (it == pos.end() || of_vertex[(size_t)it->second].kind < 0) return set_error(-1, "tsgo_marginals: unknown vertex id " + std::to_string(ids[k]));
-                qs[(size_t)k] = of_vertex[(size_t)it->second];
-            }
+        if (!fixed) return set_error(-1, nm + ": marginals need a fixed vertex (without one H is singular)");
+        qs.resize((size_t)n_ids);
+        std::unordered_map<uint32_t, int> pos; pos.reserve(structure.v_id.size() * 2);
+        for (size_t v = 0; v < structure.v_id.size(); ++v) pos.emplace(structure.v_id[v], (int)v);
+        std::vector<MbQuery> of_vertex((size_t)pr.n_vertices, MbQuery{-1, 0});
+        for (int i = 0; i < pr.P; ++i) of_vertex[(size_t)pr.pose_vertex[i]] = MbQuery{0, i};
+        for (int l = 0; l < pr.L; ++l) of_vertex[(size_t)pr.lm_vertex[l]] = MbQuery{1, l};
+        for (int k = 0; k < n_ids; ++k) {
+            auto it = pos.find(ids[k]);
+            if (it == pos.end() || of_vertex[(size_t)it->second].kind < 0) { qs.clear(); return set_error(-1, nm + ": unknown vertex id " + std::to_string(ids[k])); }
+            qs[(size_t)k] = of_vertex[(size_t)it->second];
         }
+        return 0;
+    }
+    // mb_guarded: run(), a callable of the prepared handle, between the snapshot of every device byte the handle owns and its restore
+    // (see the top of this file)
+    template <typename F> int mb_guarded(F&& run) {
         HIP_OK(hipSetDevice(cfg.device));
-        const double tol = rel_tol > 0 ? rel_tol : cfg.pcg_rel_tol;
-        // snapshot of every device byte the handle owns (see the top of this file)
         size_t total = 0;
         for (const Slab& sl : slabs) total += sl.used;
         char* snap = nullptr;
@@ -327,7 +337,7 @@
         }
         const double lambda0 = lambda;
         const std::vector<double> omega0 = omega_host;
-        const int rc = mb_compute(qs, tol, cov, s);
+        const int rc = run();
         lambda = lambda0; omega_host = omega0;
         const std::string err = rc ? std::string(tsgo_last_error()) : std::string();
         {
@@ -338,6 +348,99 @@
         (void)hipFree(snap);
         HIP_OK(es);
         if (rc) return set_error(rc, err);
+        return 0;
+    }
+
+    int marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, tsgo_marginal_stats* st_out) override {
+        const auto wall0 = std::chrono::steady_clock::now();
+        tsgo_marginal_stats s; std::memset(&s, 0, sizeof(s));
+        std::vector<MbQuery> qs;
+        if (int rc = mb_queries("tsgo_marginals", ids, n_ids, !cov, qs)) return rc;
+        if (n_ids == 0) { if (st_out) *st_out = s; return 0; }
+        const double tol = rel_tol > 0 ? rel_tol : cfg.pcg_rel_tol;
+        if (int rc = mb_guarded([&] { return mb_compute(qs, tol, cov, s); })) return rc;
+        s.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+        if (st_out) *st_out = s;
+        return 0;
+    }
+
+    // ---- tsgo_joint_marginals: the whole D x D block of H^-1 over the queried vertices (DESIGN.md section 11) ----
+    static constexpr int64_t kJointMaxDim = 8192;      // D x D doubles: 512 MB
+    // Every query column in order (3 a pose, 2 a landmark: row = column = its place in the compact D), NV per batch: every batch but the
+    // last is full, and a query's columns may straddle two batches.  After each batch k_mb_joint writes the [D][NV] slice of the result
+    // (one host synchronisation), which lands in columns j0 .. j0 + nc of cov.  At the end cov = (C + C^T) / 2.
+    template <int NV> int mb_run_joint(const std::vector<MbQuery>& qs, int D, double tol, double* cov, tsgo_marginal_stats& s) {
+        MbBuf B; char* base = nullptr; char* jbase = nullptr;
+        struct Free { char*& b; ~Free() { if (b) (void)hipFree(b); } } fr{base}, fj{jbase};
+        if (int rc = mb_alloc(B, NV, &base)) return rc;
+        const size_t nq = qs.size();
+        std::vector<MbColumn> items(nq), all;
+        all.reserve((size_t)D);
+        for (size_t q = 0; q < nq; ++q) {
+            items[q] = MbColumn{qs[q].kind, qs[q].idx, (int)all.size(), 0};
+            const int need = qs[q].kind == 0 ? 3 : 2;
+            for (int k = 0; k < need; ++k) all.push_back(MbColumn{qs[q].kind, qs[q].idx, k, 0});
+        }
+        const size_t items_b = (nq * sizeof(MbColumn) + 255) & ~size_t(255);
+        HIP_OK(hipMalloc((void**)&jbase, items_b + (size_t)D * NV * sizeof(double)));
+        MbColumn* items_d = reinterpret_cast<MbColumn*>(jbase);
+        double* out_d = reinterpret_cast<double*>(jbase + items_b);
+        HIP_OK(hipMemcpyAsync(items_d, items.data(), nq * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
+        s.batch_width = NV;
+        s.preconditioner = amg_on ? 1 : 0;
+        float ms = 0;
+        std::vector<double> o((size_t)D * NV);
+        for (int j0 = 0; j0 < D; j0 += NV) {
+            const int nc = std::min(NV, D - j0);
+            std::vector<MbColumn> cols(kMbMaxWidth, MbColumn{-1, 0, 0, 0});
+            std::copy(all.begin() + j0, all.begin() + j0 + nc, cols.begin());
+            HIP_OK(hipMemcpyAsync(B.cols, cols.data(), cols.size() * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
+            if (int rc = mb_batch<NV>(B, tol, s, &ms)) return rc;
+            hipLaunchKernelGGL((k_mb_joint<T, NV>), dim3((unsigned)nq), dim3(64), 0, stream, tl, pr.by_lm.G, (const T*)ps, (const T*)lmrec,
+                               (const MbColumn*)items_d, (const MbColumn*)B.cols, (const T*)B.x, out_d);
+            HIP_OK(hipGetLastError());
+            HIP_OK(hipMemcpyAsync(o.data(), out_d, o.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            for (int r = 0; r < D; ++r)
+                for (int c = 0; c < nc; ++c) cov[(size_t)r * D + j0 + c] = o[(size_t)r * NV + c];
+            s.columns += nc;
+        }
+        for (int r = 0; r < D; ++r)
+            for (int c = 0; c < r; ++c) {
+                const double v = 0.5 * (cov[(size_t)r * D + c] + cov[(size_t)c * D + r]);
+                cov[(size_t)r * D + c] = v; cov[(size_t)c * D + r] = v;
+            }
+        s.ms_solve = ms;
+        return 0;
+    }
+
+    int joint_marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, int64_t cov_cap, int* dim_out, tsgo_marginal_stats* st_out) override {
+        const auto wall0 = std::chrono::steady_clock::now();
+        tsgo_marginal_stats s; std::memset(&s, 0, sizeof(s));
+        std::vector<MbQuery> qs;
+        if (int rc = mb_queries("tsgo_joint_marginals", ids, n_ids, false, qs)) return rc;
+        int64_t D = 0;
+        for (const MbQuery& q : qs) D += q.kind == 0 ? 3 : 2;
+        if (dim_out) *dim_out = (int)std::min<int64_t>(D, INT32_MAX);
+        if (D > kJointMaxDim) return set_error(-1, "tsgo_joint_marginals: D = " + std::to_string(D) + " rows exceed " + std::to_string(kJointMaxDim));
+        if (!cov) {
+            if (!dim_out) return set_error(-1, "tsgo_joint_marginals: bad argument (cov_out and dim_out both NULL)");
+            if (st_out) *st_out = s;
+            return 0;
+        }
+        if (cov_cap < D * D) return set_error(-1, "tsgo_joint_marginals: cov_cap " + std::to_string(cov_cap) + " is below D^2 = " + std::to_string(D * D));
+        if (D == 0) { if (st_out) *st_out = s; return 0; }
+        const double tol = rel_tol > 0 ? rel_tol : cfg.pcg_rel_tol;
+        const int Di = (int)D;
+        const int rc = mb_guarded([&]() -> int {
+            if (int r = mb_prepare()) return r;
+            switch (marginal_width()) {
+                case 1: return mb_run_joint<1>(qs, Di, tol, cov, s);
+                case 16: return mb_run_joint<16>(qs, Di, tol, cov, s);
+                default: return mb_run_joint<8>(qs, Di, tol, cov, s);
+            }
+        });
+        if (rc) return rc;
         s.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
         if (st_out) *st_out = s;
         return 0;

@@ -10,7 +10,7 @@
 //   engine/engine_collective.inc   the all-reduces of an edge-sharded run
 //   engine/engine_solve.inc        the Gauss-Newton loop, the PCG drivers, read-outs
 //   engine/engine_probes.inc       timing probes (bench.py)
-//   engine/engine_marginals.inc    tsgo_marginals: batched PCG for diagonal blocks of H^-1
+//   engine/engine_marginals.inc    tsgo_marginals, tsgo_joint_marginals: batched PCG for blocks of H^-1
 //
 // There is NO CPU fallback in this file: every entry point that computes needs a gfx950 device and
 // returns an error otherwise.
@@ -155,6 +155,7 @@ struct IEngine {
     virtual int comm_time_allreduce(int64_t n, int reps, double* us) = 0;
     virtual void reset_history() = 0;
     virtual int marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, tsgo_marginal_stats* st) = 0;
+    virtual int joint_marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, int64_t cov_cap, int* dim_out, tsgo_marginal_stats* st) = 0;
     ncclComm_t comm = nullptr;
     tsgo_local_group* lgroup = nullptr;      // in-process stand-in for the communicator (tests on a one-GPU box; always null outside TSGO_TESTING builds)
 };
@@ -519,6 +520,11 @@ int tsgo_comm_init_local(tsgo_optimizer* o, tsgo_local_group* g) {
 int tsgo_marginals(tsgo_optimizer* o, const uint32_t* ids, int32_t n_ids, double rel_tol, double* cov_out, tsgo_marginal_stats* stats) {
     if (!o) return tsgo::set_error(-1, "tsgo_marginals: null handle");
     return o->eng->marginals(ids, n_ids, rel_tol, cov_out, stats);
+}
+int tsgo_joint_marginals(tsgo_optimizer* o, const uint32_t* ids, int32_t n_ids, double rel_tol, double* cov_out, int64_t cov_cap, int32_t* dim_out,
+                         tsgo_marginal_stats* stats) {
+    if (!o) return tsgo::set_error(-1, "tsgo_joint_marginals: null handle");
+    return o->eng->joint_marginals(ids, n_ids, rel_tol, cov_out, cov_cap, dim_out, stats);
 }
 void tsgo_reset_history(tsgo_optimizer* o) {
     if (o && o->eng) o->eng->reset_history();

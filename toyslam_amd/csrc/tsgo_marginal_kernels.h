@@ -442,4 +442,59 @@ __global__ __launch_bounds__(64) void k_mb_extract(Table<T> tb, int G, int n_ite
     o[0] = (double)(dv[0] + s00); o[1] = (double)(dv[1] + s01); o[3] = (double)(dv[1] + s10); o[4] = (double)(dv[2] + s11);
 }
 
+// Sign of a pose-landmark cross block (tsgo_joint_marginals).  H^-1 = [[S^-1, -S^-1 Y], [-Y^T S^-1, D^-1 + Y^T S^-1 Y]] with
+// Y = W D^-1; lm_y_block builds Y_l = W_{:,l} Dl^-1 with the W of H itself, so a pose row against a landmark column, and a landmark
+// row against a pose column, take -1 (checked against the dense inverse of the oracle's H: tests/test_gpu_joint_marginals.py).
+constexpr int kMbCrossSign = -1;
+
+// The joint marginal's rows against the NV columns of one batch: out[r][c] = Sigma[r][column c of the batch] (f64, unsymmetrised) for
+// every row r of the query list.  items[q] = (kind, idx, first row of query q).  One wavefront per query:
+//   pose i:      rows = X[i][c] (a gather; lane = (row, column));
+//   landmark l:  rows = Y_l^T X[.][c] over the landmark's slots in the landmark-major table, plus Dl^-1 on the columns of l itself.
+//                Lane = (part, row, column): part p takes every (64 / 2 NV)-th slot row from the p-th, and the parts are folded in
+//                order through LDS.
+// No atomics: a repeated call gives the same bits.  Padding columns (kind -1) give 0.
+template <typename T, int NV>
+__global__ __launch_bounds__(64) void k_mb_joint(Table<T> tb, int G, const T* __restrict__ ps, const T* __restrict__ lmrec,
+                                                 const MbColumn* __restrict__ items, const MbColumn* __restrict__ cols, const T* __restrict__ x,
+                                                 double* __restrict__ out) {
+    constexpr int kPairs = 2 * NV, kParts = 64 / kPairs;      // NV in {1, 8, 16}: kPairs divides 64
+    __shared__ T red[64];
+    const MbColumn it = items[blockIdx.x];
+    const int lane = threadIdx.x;
+    double* o = out + (size_t)it.comp * NV;
+    if (it.kind == 0) {      // workgroup-uniform
+        if (lane < 3 * NV) {
+            const int a = lane / NV, c = lane % NV;
+            const int kind = cols[c].kind;
+            const T v = x[((size_t)it.idx * NV + c) * 3 + a];
+            o[(size_t)a * NV + c] = kind < 0 ? 0.0 : (double)(kind == 1 ? T(kMbCrossSign) * v : v);
+        }
+        return;
+    }
+    const int pair = lane % kPairs, part = lane / kPairs, a = pair / NV, c = pair % NV;
+    const int l = it.idx, vps = 64 / G, slice = l / vps;
+    const T* dv = lmrec + (size_t)l * kLmRec + 2;
+    T s = 0;
+    for (uint32_t row = tb.row_off[slice] + part; row < tb.row_off[slice + 1]; row += kParts)
+        for (int g = 0; g < G; ++g) {
+            const size_t k = (size_t)row * 64 + (size_t)((l % vps) * G + g);
+            uint32_t i; T y[3][2];
+            lm_y_block<T>(tb, ps, k, dv, i, y);
+            const T* xi = x + ((size_t)i * NV + c) * 3;
+            const T y0 = a ? y[0][1] : y[0][0], y1 = a ? y[1][1] : y[1][0], y2 = a ? y[2][1] : y[2][0];
+            s += y0 * xi[0] + y1 * xi[1] + y2 * xi[2];
+        }
+    red[lane] = s;
+    __syncthreads();
+    if (part != 0) return;
+    T acc = 0;
+    for (int q = 0; q < kParts; ++q) acc += red[q * kPairs + pair];
+    const MbColumn q = cols[c];
+    double v = 0;
+    if (q.kind == 0) v = (double)(T(kMbCrossSign) * acc);
+    else if (q.kind == 1) v = (double)(q.idx == l ? acc + dv[a == q.comp ? 2 * a : 1] : acc);      // Dl^-1 = (ixx ixy; ixy iyy)
+    o[(size_t)a * NV + c] = v;
+}
+
 }  // namespace tsgo

@@ -45,6 +45,7 @@ class HipOptimizer:
         _lib.check(self.lib, self.lib.tsgo_create(C.byref(cfg), C.byref(self.h)), "tsgo_create")
         self.n_vertices = 0
         self._v_in = None
+        self._ids_types = None
 
     @staticmethod
     def _use_graphs(v):
@@ -72,6 +73,7 @@ class HipOptimizer:
         cg = g.c_struct()
         _lib.check(self.lib, self.lib.tsgo_set_graph(self.h, C.byref(cg)), "tsgo_set_graph")
         self.n_vertices = len(g.v_id)
+        self._ids_types = (g.v_id, g.v_type)      # joint_marginals: the row count of each queried id
         self._v_in = g.v_pos.copy() if self.cfg.world > 1 else None    # a shard returns its own landmarks; the others keep their input
 
     def reset_history(self):
@@ -114,6 +116,27 @@ class HipOptimizer:
         _lib.check(self.lib, self.lib.tsgo_marginals(self.h, ids.ctypes.data if len(ids) else None, len(ids), float(rel_tol),
                                                       cov.ctypes.data, C.byref(st)), "tsgo_marginals")
         return cov, {f: getattr(st, f) for f, _t in st._fields_}
+
+    def joint_marginals(self, ids, rel_tol=0.0):
+        """Joint marginal covariance of the vertices `ids` (the block of H^-1 over them, cross blocks included): cov (D, D), rows and
+        columns in query order, 3 per pose and 2 per landmark; offsets (len(ids) + 1,): the rows of ids[k] are offsets[k]:offsets[k + 1].
+        rel_tol <= 0: the handle's pcg_rel_tol."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1))
+        idp = ids.ctypes.data if len(ids) else None
+        dim = C.c_int32()
+        _lib.check(self.lib, self.lib.tsgo_joint_marginals(self.h, idp, len(ids), float(rel_tol), None, 0, C.byref(dim), None),
+                   "tsgo_joint_marginals")
+        D = dim.value
+        v_id, v_type = self._ids_types
+        order = np.argsort(v_id, kind="stable")
+        dims = np.where(v_type[order[np.searchsorted(v_id, ids, sorter=order)]] == 0, 3, 2) if len(ids) else np.zeros(0, np.int64)
+        offsets = np.concatenate([[0], np.cumsum(dims)]).astype(np.int64)
+        assert offsets[-1] == D, (offsets[-1], D)
+        cov = np.zeros((D, D))
+        st = _lib.tsgo_marginal_stats()
+        _lib.check(self.lib, self.lib.tsgo_joint_marginals(self.h, idp, len(ids), float(rel_tol), cov.ctypes.data if D else None, D * D,
+                                                            C.byref(dim), C.byref(st)), "tsgo_joint_marginals")
+        return cov, offsets, {f: getattr(st, f) for f, _t in st._fields_}
 
     def time_kernel(self, which, reps=50):
         us = C.c_double(); nbytes = C.c_double()
