@@ -30,11 +30,18 @@ extern "C" {
  *            (README.md:53 "Further development: ... Virtual Meas."; the reference keeps a sketch commented out,
  *            python/optimizer/edges2d.py:83-121): two Se2 vertices that observed the same physical point, no landmark vertex;
  *            residual e = T1 p1 - T2 p2 (2), Jacobians [I | dR1/dth p1] and -[I | dR2/dth p2], 2 x 2 diagonal information
+ *            3 = POSE PRIOR and 4 = LANDMARK PRIOR, behind this ABI only too: unary edges (id2 must equal id1) that pull one vertex
+ *            toward an absolute measurement m in the world frame (a GNSS fix, a surveyed point, a soft anchor); any number of them may
+ *            sit on one vertex (summed in input order), also on a fixed one.  Pose prior on an Se2 vertex: e_t = R_m^T (t - t_m),
+ *            e_th = atan2(sin(th - m_th), cos(th - m_th)) (the ODOM residual of an edge whose first pose is held at the origin),
+ *            J = blockdiag(R_m^T, 1): H_pp += [[R_m diag(a0, a1) R_m^T, 0], [0, a2]], b_p -= J^T Omega_w e.  Landmark prior on a Point2
+ *            vertex: e = l - m, J = I: D_l += Omega_w, b_l -= Omega_w e.  Omega_w = Huber weight (delta 1.5) * diag(w), chi^2 += rho as
+ *            for every edge; independent of odom_jacobian; damped and (at a fixed vertex) zeroed with the rest under rules = 1
  *   e_meas : 9 doubles per edge: ODOM = the 3x3 measurement row-major (EdgeSe2.h); LM = (range,
  *            bearing, 0...) (EdgeSe2Point2d.h:34-35); virtual landmark = (range1, bearing1, range2, bearing2, 0...): the point
- *            as seen from id1 and from id2
+ *            as seen from id1 and from id2; pose prior = (mx, my, m_theta, 0...); landmark prior = (mx, my, 0...)
  *   e_inf  : 3 doubles per edge: the diagonal of the information matrix (the wire format carries
- *            nothing else, DeserializeGraph.h:123-147); LM uses the first two
+ *            nothing else, DeserializeGraph.h:123-147); LM, virtual landmark and landmark prior use the first two
  *   fixed  : vertex ids given to FixVertex; a repeated id adds the gauge term once per occurrence
  *            (OptimizerCpu.h:132-138 iterates the vector) */
 typedef struct tsgo_graph {
@@ -234,8 +241,9 @@ int tsgo_profile_iteration(tsgo_optimizer* opt, int32_t reps, tsgo_prof_entry* o
  * right-hand sides of S for k poses and m landmarks, solved a batch of columns per launch chain by PCG on the device with the handle's
  * preconditioner.  rel_tol <= 0: the handle's pcg_rel_tol; every column stops by that rule on its own.  Duplicate ids are allowed;
  * n_ids == 0 returns 0 and does nothing.  The estimates are not changed, and nothing the next tsgo_optimize reads is (DESIGN.md
- * section 11).  Errors (< 0, text in tsgo_last_error): a NULL handle, no graph set, an unknown id, a graph without a fixed vertex (H is
- * singular), precision = 32, an edge-sharded handle (world > 1: not supported). */
+ * section 11).  H includes the prior edges (types 3, 4): a graph anchored by a pose prior with w0, w1, w2 > 0 instead of a fixed vertex
+ * gives covariances in the world frame.  Errors (< 0, text in tsgo_last_error): a NULL handle, no graph set, an unknown id, a graph with
+ * neither a fixed vertex nor such a pose prior (H is singular), precision = 32, an edge-sharded handle (world > 1: not supported). */
 typedef struct tsgo_marginal_stats {
     int32_t columns, batches, batch_width;       /* right-hand sides solved, launch chains run, columns per chain */
     int32_t pcg_iters_max;  int64_t pcg_iters_total;

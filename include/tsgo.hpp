@@ -27,7 +27,8 @@
 namespace tsgo {
 
 enum class VertexType : uint32_t { Se2 = 0, Point2 = 1 };
-enum class EdgeType : uint32_t { Se2 = 0, Se2Point2 = 1, Se2VirtualPoint2 = 2 };      // 2: behind the C ABI only (include/tsgo.h), not in the reference's enum
+// 2, 3, 4: behind the C ABI only (include/tsgo.h), not in the reference's enum
+enum class EdgeType : uint32_t { Se2 = 0, Se2Point2 = 1, Se2VirtualPoint2 = 2, Se2Prior = 3, Point2Prior = 4 };
 
 class Graph {
 public:
@@ -56,6 +57,16 @@ public:
     void AddEdgeVirtualLandmark(unsigned id_pose_1, unsigned id_pose_2, double range1, double bearing1, double range2, double bearing2, double w0, double w1) {
         const double m[9] = {range1, bearing1, range2, bearing2, 0, 0, 0, 0, 0};
         push_edge(EdgeType::Se2VirtualPoint2, id_pose_1, id_pose_2, m, w0, w1, 0.0);
+    }
+    // Pose prior (edge type 3): an absolute measurement (x, y, theta) of pose `id` in the world frame, information = diag(w0, w1, w2).
+    void AddEdgePosePrior(unsigned id, double x, double y, double theta, double w0, double w1, double w2) {
+        const double m[9] = {x, y, theta, 0, 0, 0, 0, 0, 0};
+        push_edge(EdgeType::Se2Prior, id, id, m, w0, w1, w2);
+    }
+    // Landmark prior (edge type 4): an absolute position (x, y) of landmark `id`, information = diag(w0, w1).
+    void AddEdgeLandmarkPrior(unsigned id, double x, double y, double w0, double w1) {
+        const double m[9] = {x, y, 0, 0, 0, 0, 0, 0, 0};
+        push_edge(EdgeType::Point2Prior, id, id, m, w0, w1, 0.0);
     }
     // generic form, same argument meaning as Functions::CreateEdge(type, id1, id2, meas, inf)
     // (DeserializeGraphFuncCpu.h:27-38): meas = 9 doubles row-major (ODOM) or (range, bearing, 0...) (LM)

@@ -105,6 +105,38 @@
         return 0;       // the caller synchronises the stream before the staging buffer is touched again
     }
 
+    // the prior records (edge types 3, 4) in T, from the measurements and weights of THIS request: by set_graph and by every refill
+    int stage_priors(const tsgo_graph& g) {
+        if (!pr.has_priors) return 0;
+        const size_t np = pr.prior_p_edge.size(), nl = pr.prior_l_edge.size();
+        std::vector<T> rec(np * PRI_POSE_REC + nl * PRI_LM_REC);
+        double v[PRI_POSE_REC];
+        for (size_t k = 0; k < np; ++k) {
+            const size_t e = pr.prior_p_edge[k];
+            prior_static(3, g.e_meas + 9 * e, g.e_inf + 3 * e, v);
+            for (int m = 0; m < PRI_POSE_REC; ++m) rec[k * PRI_POSE_REC + m] = (T)v[m];
+        }
+        for (size_t k = 0; k < nl; ++k) {
+            const size_t e = pr.prior_l_edge[k];
+            prior_static(4, g.e_meas + 9 * e, g.e_inf + 3 * e, v);
+            for (int m = 0; m < PRI_LM_REC; ++m) rec[np * PRI_POSE_REC + k * PRI_LM_REC + m] = (T)v[m];
+        }
+        if (np) { if (int rc = copy_sync(pri_p, rec.data(), np * PRI_POSE_REC * sizeof(T), hipMemcpyHostToDevice)) return rc; }
+        if (nl) { if (int rc = copy_sync(pri_l, rec.data() + np * PRI_POSE_REC, nl * PRI_LM_REC * sizeof(T), hipMemcpyHostToDevice)) return rc; }
+        return 0;
+    }
+    // a pose prior with three positive weights anchors the graph to the world frame as a fixed vertex does (tsgo_marginals)
+    std::vector<double> pri_p_w;        // (w0, w1, w2) of every pose prior record of the current request
+    void keep_prior_weights(const tsgo_graph& g) {
+        pri_p_w.clear();
+        for (uint32_t e : pr.prior_p_edge) pri_p_w.insert(pri_p_w.end(), g.e_inf + 3 * (size_t)e, g.e_inf + 3 * (size_t)e + 3);
+    }
+    bool has_full_pose_prior() const {
+        for (size_t k = 0; k + 2 < pri_p_w.size(); k += 3)
+            if (pri_p_w[k] > 0 && pri_p_w[k + 1] > 0 && pri_p_w[k + 2] > 0) return true;
+        return false;
+    }
+
     // solver state a fresh engine starts from: whatever was learnt on the previous graph must not leak into this one
     int reset_solver_state() {
         have_prev = false; n_prev = 0; n_tested = 0; carried = false; predicted_cg = 0; n_decided = 0; n_slow_seen = 0; n_host_slow = 0; ref_us_per_iter = 0; n_paced_slow = 0; std::fill(iters_by_age, iters_by_age + kAgeSlots, 0); lin_count = 0; n_lins = 0; hier_age = -1; iters_fresh = 0; iters_last = 0;
@@ -204,6 +236,8 @@
         }
         hier_shift = hier_shift_cfg;      // (... and a hierarchy whose diagonal was raised after a breakdown starts unraised again, do_solve)
         if (int rc = stage_values(g, true)) return rc;
+        if (int rc = stage_priors(g)) return rc;
+        keep_prior_weights(g);
         if (amg_on) {           // the rigid-mode lever arms follow the new estimates (host/amg.h: refresh_amg_geometry)
             refresh_amg_geometry(pr.pose_xyt, amg);
             HIP_OK(hipStreamSynchronize(stream));
@@ -263,6 +297,16 @@
         nbP = 8 * (((tp.n_slices + kWavesPerBlock - 1) / kWavesPerBlock + 7) / 8);
         nbL = 8 * (((tl.n_slices + kWavesPerBlock - 1) / kWavesPerBlock + 7) / 8);
         nbC = (P + kBlock - 1) / kBlock;
+        pri_p_off = pri_l_off = nullptr; pri_p = pri_l = pri_lchi = nullptr;
+        if (pr.has_priors) {
+            if (int rc = upload_u32m(&pri_p_off, pr.prior_p_off)) return rc;
+            if (int rc = upload_u32m(&pri_l_off, pr.prior_l_off)) return rc;
+            if (int rc = dalloc(&pri_p, pr.prior_p_edge.size() * PRI_POSE_REC)) return rc;
+            if (int rc = dalloc(&pri_l, pr.prior_l_edge.size() * PRI_LM_REC)) return rc;
+            if (int rc = dalloc(&pri_lchi, (size_t)std::max(nbL, 1))) return rc;
+            if (int rc = stage_priors(g)) return rc;
+        }
+        keep_prior_weights(g);
         if (int rc = dalloc(&part, (size_t)P * 18 + nbP)) return rc;
         if (int rc = dalloc(&dp, (size_t)P * 6)) return rc;
         if (int rc = dalloc(&minv, (size_t)P * 6)) return rc;

@@ -37,14 +37,26 @@
     bool oj() const { return cfg.odom_jacobian == 1 || pr.has_vlm; }
     int odom_analytic_flag() const { return cfg.odom_jacobian == 1 ? 1 : 0; }
     double step_scale() const { return py_rules() ? cfg.lr : kStepScale; }
+    // a graph with priors (edge types 3, 4) takes the PRI = 1 instantiations; one without launches exactly what it did before priors existed
+    PriorArgs<T> pose_prior_args() const { return PriorArgs<T>{pri_p_off, pri_p, pri_lchi, tl.n_slices > 0 ? nbL : 0}; }
+    PriorArgs<T> lm_prior_args() const { return PriorArgs<T>{pri_l_off, pri_l, pri_lchi, 0}; }
     void launch_lin() {
-        const int zf = py_rules() ? 1 : 0;
-        if (tl.n_slices > 0) LAUNCH_G(pr.by_lm.G, k_lin_lm, nbL, stream, tl, ps, lmrec, gauge_l, ninv, (T)lambda, zf);
-        if (oj()) LAUNCH_GM(pr.by_pose.G, k_lin_pose, 1, nbP, stream, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf, odom_analytic_flag());
-        else LAUNCH_G(pr.by_pose.G, k_lin_pose, nbP, stream, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf);
+        launch_lin_lm();
+        launch_lin_pose_only();
     }
-    void launch_lin_pose_only() {       // tsgo_time_kernel
+    void launch_lin_lm() {              // (tsgo_time_kernel too)
         const int zf = py_rules() ? 1 : 0;
+        if (tl.n_slices == 0) return;
+        if (pr.has_priors) LAUNCH_GM(pr.by_lm.G, k_lin_lm, 1, nbL, stream, tl, ps, lmrec, gauge_l, ninv, (T)lambda, zf, lm_prior_args());
+        else LAUNCH_G(pr.by_lm.G, k_lin_lm, nbL, stream, tl, ps, lmrec, gauge_l, ninv, (T)lambda, zf);
+    }
+    void launch_lin_pose_only() {       // (tsgo_time_kernel too)
+        const int zf = py_rules() ? 1 : 0;
+        if (pr.has_priors) {
+            if (oj()) LAUNCH_GML(pr.by_pose.G, k_lin_pose, 1, 1, nbP, stream, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf, odom_analytic_flag(), pose_prior_args());
+            else LAUNCH_GML(pr.by_pose.G, k_lin_pose, 0, 1, nbP, stream, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf, 0, pose_prior_args());
+            return;
+        }
         if (oj()) LAUNCH_GM(pr.by_pose.G, k_lin_pose, 1, nbP, stream, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf, odom_analytic_flag());
         else LAUNCH_G(pr.by_pose.G, k_lin_pose, nbP, stream, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf);
     }

@@ -309,6 +309,7 @@
         bool fixed = false;
         for (double g : pr.gauge_p) fixed |= g > 0;
         for (double g : pr.gauge_l) fixed |= g > 0;
+        fixed |= has_full_pose_prior();      // a pose prior on every axis anchors H to the world frame
         if (!fixed) return set_error(-1, nm + ": marginals need a fixed vertex (without one H is singular)");
         qs.resize((size_t)n_ids);
         std::unordered_map<uint32_t, int> pos; pos.reserve(structure.v_id.size() * 2);

@@ -118,6 +118,9 @@ extern "C" int tsgo_wire_decode_into(tsgo_wire_graph* w, const uint8_t* payload,
         if (i % kChunk == 0) e_start[i / kChunk] = off;
         if (!need(20)) return fail("truncated in edge " + std::to_string(i));
         const uint32_t type = rd_u32(payload + off), rows = rd_u32(payload + off + 12), cols = rd_u32(payload + off + 16);   // :61-70
+        if (type >= 2 && type <= 4)
+            return fail("edge type " + std::to_string(type) + (type == 2 ? " (virtual landmark measurement)" : type == 3 ? " (pose prior)" : " (landmark prior)") +
+                        " exists behind the C ABI only: the wire format carries ODOM (0) and LM (1) edges");
         if (type > 1) return fail("unknown edge type " + std::to_string(type));                          // :93-95
         size_t n_meas;
         if (rows == 0) n_meas = type == 0 ? 3 : 2;                                                       // :74-91
@@ -280,7 +283,7 @@ extern "C" int64_t tsgo_wire_encode_request(const tsgo_graph* g, uint8_t* buf, s
         if (g->e_type[e] > 1)
             return tsgo::set_error(-2, "tsgo_wire_encode_request: edge " + std::to_string(e) + " has type " + std::to_string(g->e_type[e]) +
                                            "; the wire format carries ODOM (0) and LM (1) edges only (remote/serialization/DeserializeGraph.h:93-95 throws on any other): "
-                                           "virtual landmark measurements exist behind the C ABI only");
+                                           "virtual landmark measurements (2) and pose / landmark priors (3, 4) exist behind the C ABI only");
     Writer o{buf, cap};
     o.u32(0);                                                           // graph_to_bytes.py:67 length prefix
     o.u32((uint32_t)g->n_vertices);                                     // :44

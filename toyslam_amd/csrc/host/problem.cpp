@@ -42,6 +42,15 @@ bool invert3(const double* m, double* out) {
     return true;
 }
 
+void prior_static(uint32_t type, const double* meas, const double* inf, double* out) {
+    if (type == 3) {
+        out[PRI_MX] = meas[0]; out[PRI_MY] = meas[1]; out[PRI_C] = std::cos(meas[2]); out[PRI_S] = std::sin(meas[2]);
+        out[PRI_W0] = inf[0]; out[PRI_W1] = inf[1]; out[PRI_W2] = inf[2]; out[7] = 0;
+    } else {
+        out[PRL_MX] = meas[0]; out[PRL_MY] = meas[1]; out[PRL_W0] = inf[0]; out[PRL_W1] = inf[1];
+    }
+}
+
 void lm_static(const double* meas, const double* inf, double* out4) {
     out4[LM_ZX] = meas[0] * std::cos(meas[1]); out4[LM_ZY] = meas[0] * std::sin(meas[1]);   // EdgeSe2Point2d.h:34-35
     out4[LM_W0] = inf[0]; out4[LM_W1] = inf[1];
@@ -173,6 +182,11 @@ std::string build_problem(const tsgo_graph& g, const BuildOptions& opt, Problem&
             if (g.v_type[ev1[e]] != 0 || g.v_type[ev2[e]] != 0) return "virtual-landmark edge " + std::to_string(e) + " must join two Se2 vertices";
             ++deg_pose_od[cls[ev1[e]]]; ++deg_pose_od[cls[ev2[e]]];
             ++pr.n_vlm_edges_total; pr.has_vlm = true;
+        } else if (t == 3 || t == 4) {      // unary prior: applied in the epilogues of the linearisation (no slot, no pattern)
+            const char* what = t == 3 ? "pose prior edge " : "landmark prior edge ";
+            if (g.e_ids[2 * (size_t)e] != g.e_ids[2 * (size_t)e + 1]) return what + std::to_string(e) + " must give the same vertex id twice";
+            if (g.v_type[ev1[e]] != (t == 3 ? 0u : 1u)) return what + std::to_string(e) + (t == 3 ? " must sit on an Se2 vertex" : " must sit on a Point2 vertex");
+            ++pr.n_prior_edges_total; pr.has_priors = true;
         } else return "unknown edge type " + std::to_string(t);
     }
 
@@ -233,6 +247,34 @@ std::string build_problem(const tsgo_graph& g, const BuildOptions& opt, Problem&
         }
     }
 
+    // ---- prior records: per internal vertex of this shard, in input order ------------------------------------------------------
+    if (pr.has_priors) {
+        pr.prior_p_off.assign((size_t)P + 1, 0u); pr.prior_l_off.assign((size_t)L + 1, 0u);
+        auto owner = [&](int e, int& v) -> std::vector<uint32_t>* {      // the CSR this prior goes to, or null when another shard owns the vertex
+            const int c = cls[ev1[e]];
+            if (g.e_type[e] == 3) { v = pose_internal[c]; return v >= pr.pose_first && v < pr.pose_last ? &pr.prior_p_off : nullptr; }
+            if (c < pr.lm_first || c >= pr.lm_last) return nullptr;
+            v = lm_internal[c - pr.lm_first]; return &pr.prior_l_off;
+        };
+        for (int e = 0; e < nE; ++e) {
+            if (g.e_type[e] < 3) continue;
+            int v = 0;
+            if (std::vector<uint32_t>* off = owner(e, v)) ++(*off)[(size_t)v + 1];
+        }
+        for (int i = 0; i < P; ++i) pr.prior_p_off[(size_t)i + 1] += pr.prior_p_off[(size_t)i];
+        for (int i = 0; i < L; ++i) pr.prior_l_off[(size_t)i + 1] += pr.prior_l_off[(size_t)i];
+        pr.prior_p_edge.assign(pr.prior_p_off[(size_t)P], 0u); pr.prior_l_edge.assign(pr.prior_l_off[(size_t)L], 0u);
+        std::vector<uint32_t> fill_p(pr.prior_p_off.begin(), pr.prior_p_off.end() - 1), fill_l(pr.prior_l_off.begin(), pr.prior_l_off.end() - 1);
+        for (int e = 0; e < nE; ++e) {
+            if (g.e_type[e] < 3) continue;
+            int v = 0;
+            std::vector<uint32_t>* off = owner(e, v);
+            if (!off) continue;
+            if (off == &pr.prior_p_off) pr.prior_p_edge[fill_p[(size_t)v]++] = (uint32_t)e;
+            else pr.prior_l_edge[fill_l[(size_t)v]++] = (uint32_t)e;
+        }
+    }
+
     lap("numbering, windows, state");
     // ---- per-vertex degrees in internal numbering (owned edges only) ---------------------------------
     // The k-th edge of a vertex IN INPUT ORDER takes the vertex's k-th slot (the order fixes every summation order on the
@@ -251,7 +293,7 @@ std::string build_problem(const tsgo_graph& g, const BuildOptions& opt, Problem&
                     const int cl = cls[ev2[e]];
                     if (cl < pr.lm_first || cl >= pr.lm_last) continue;
                     ++kp[pose_internal[cls[ev1[e]]]]; ++kl[lm_internal[cl - pr.lm_first]]; ++n_lm_chunk[c];
-                } else {
+                } else if (g.e_type[e] <= 2) {
                     const int p1 = pose_internal[cls[ev1[e]]], p2 = pose_internal[cls[ev2[e]]];
                     if (p1 >= pr.pose_first && p1 < pr.pose_last) ++ko[p1];
                     if (p2 >= pr.pose_first && p2 < pr.pose_last) ++ko[p2];
@@ -313,7 +355,7 @@ std::string build_problem(const tsgo_graph& g, const BuildOptions& opt, Problem&
                             for (int k = 0; k < 9; ++k) pr.odom.plane(k)[so] = v9[k];
                         }
                     }
-                } else {
+                } else if (g.e_type[e] == 0) {
                     double inv[9];
                     if (!invert3(m, inv)) { int seen = bad_edge.load(); while (e < seen && !bad_edge.compare_exchange_weak(seen, e)) {} continue; }
                     const int p1 = pose_internal[cls[ev1[e]]], p2 = pose_internal[cls[ev2[e]]];

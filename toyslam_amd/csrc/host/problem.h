@@ -49,6 +49,10 @@ struct SellTable {
 // its OWN pose and of the neighbour in mi[0..3] (pox, poy, pnx, pny) and its two weights in w[0..1].
 enum { LM_ZX = 0, LM_ZY, LM_W0, LM_W1, LM_PLANES };
 enum { OD_MI0 = 0, OD_W0 = 6, OD_PLANES = 9 };
+// Prior records (edge types 3 and 4), per vertex in internal order behind a CSR of offsets, in input order within a vertex.
+// Pose prior: (mx, my, cos m_theta, sin m_theta, w0, w1, w2, 0); landmark prior: (mx, my, w0, w1).
+enum { PRI_MX = 0, PRI_MY, PRI_C, PRI_S, PRI_W0, PRI_W1, PRI_W2, PRI_POSE_REC = 8 };
+enum { PRL_MX = 0, PRL_MY, PRL_W0, PRL_W1, PRI_LM_REC = 4 };
 
 struct Problem {
     int rank = 0, world = 1;
@@ -68,6 +72,11 @@ struct Problem {
     int n_vertices = 0;                 // of the input graph
     bool has_vlm = false;               // the graph holds virtual landmark measurements (edge type 2): pose-pose slots in general form (tsgo_math.h)
     int64_t n_vlm_edges_total = 0;
+    // unary priors (edge types 3 and 4): records of the poses / landmarks THIS shard owns (pose_first..pose_last, the owned landmarks),
+    // offsets per internal vertex (P + 1 / L + 1 entries) and the input edge of every record; empty when the graph has none
+    bool has_priors = false;            // the WHOLE graph holds a prior (every shard takes the same kernel instantiations)
+    int64_t n_prior_edges_total = 0;
+    std::vector<uint32_t> prior_p_off, prior_p_edge, prior_l_off, prior_l_edge;
     bool odom_analytic = false;         // analytic ODOM Jacobians (tsgo_config.odom_jacobian): odometry then couples heading to translation,
                                         // so every pose an edge touches carries a lever arm in the multigrid coarse space (host/amg.cpp)
 };
@@ -92,5 +101,7 @@ void lm_static(const double* meas, const double* inf, double* out4);
 // ... and the nine static plane values of a virtual-landmark slot at the edge's first (side = 0) or second endpoint:
 // meas = (r1, phi1, r2, phi2), inf = (w0, w1, .)
 void vlm_static(const double* meas, const double* inf, int side, double* out9);
+// ... and the record of a pose prior (edge type 3, PRI_POSE_REC values) or of a landmark prior (type 4, PRI_LM_REC values)
+void prior_static(uint32_t type, const double* meas, const double* inf, double* out);
 
 }  // namespace tsgo

@@ -246,6 +246,9 @@ template <typename T> struct Engine : IEngine {
     // device
     T *ps = nullptr, *theta = nullptr, *lmrec = nullptr, *gauge_p = nullptr, *gauge_l = nullptr;
     Table<T> tp{}, tl{}, to{};
+    // unary priors (Problem::prior_*; null when the graph has none): CSR offsets, records in T, the landmark priors' chi^2 partials (nbL)
+    uint32_t *pri_p_off = nullptr, *pri_l_off = nullptr;
+    T *pri_p = nullptr, *pri_l = nullptr, *pri_lchi = nullptr;
     T *part = nullptr, *dp = nullptr, *minv = nullptr, *r = nullptr, *p = nullptr, *q = nullptr, *x = nullptr, *zc = nullptr;
     float *zc32 = nullptr, *tvec32 = nullptr;      // f32 copies of the gathered records, read by the two products inside the multigrid cycle
     T *sbuf = nullptr, *tvec = nullptr, *ninv = nullptr, *dl = nullptr, *gpart[2] = {nullptr, nullptr}, *npart = nullptr;

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "host/problem.h"      // record layouts of the prior CSR (PRI_*, PRL_*)
 #include "tsgo_math.h"
 
 namespace tsgo {
@@ -126,24 +127,51 @@ template <typename T> __device__ __forceinline__ void iter_gate_body(const GateA
             ((unsigned long long)(unsigned)g.seq << 32) | ((unsigned long long)(done_now ? 1u : 0u) << 31) | ((unsigned long long)((unsigned)fail_now & 7u) << 28) | (unsigned long long)((unsigned)iters & 0x0fffffffu);
 }
 
+// Unary priors (edge types 3 and 4, include/tsgo.h), folded in by the lane that writes a vertex's result, in input order, in the world
+// frame; records behind a CSR of offsets per internal vertex (host/problem.h: PRI_*, PRL_*).  lm_chi / n_lm_chi: the per-workgroup chi^2
+// partials of the landmark priors (k_lin_lm<.., 1>), which workgroup 0 of k_lin_pose<.., .., 1> adds to its own partial in a fixed order.
+template <typename T> struct PriorArgs { const uint32_t* off; const T* rec; T* lm_chi; int n_lm_chi; };
+
+// Pose prior (type 3): e_t = R_m^T (t - t_m), e_th = wrap(th - m_th); J = blockdiag(R_m^T, 1).  With a = Huber weight * (w0, w1, w2):
+// H_pp += [[R_m diag(a0, a1) R_m^T, 0], [0, a2]] (h00 h01 h11 h22), b_p -= J^T diag(a) e (b0 b1 b2); returns rho.
+template <typename T> __device__ __forceinline__ T pose_prior_fold(const T* q, T x, T y, T c, T s, T& h00, T& h01, T& h11, T& h22, T& b0, T& b1, T& b2) {
+    const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C), w01 = ld2<T>(q + PRI_W0);
+    const T w2 = q[PRI_W2];
+    const T cm = cs.x, sm = cs.y, dx = x - m01.x, dy = y - m01.y;
+    const T e0 = cm * dx + sm * dy, e1 = cm * dy - sm * dx;
+    const T et = atan2(s * cm - c * sm, c * cm + s * sm);
+    T rho, hw;
+    huber<T>(w01.x * e0 * e0 + w01.y * e1 * e1 + w2 * et * et, rho, hw);
+    const T a0 = hw * w01.x, a1 = hw * w01.y, a2 = hw * w2;
+    h00 += a0 * cm * cm + a1 * sm * sm; h01 += (a0 - a1) * cm * sm; h11 += a0 * sm * sm + a1 * cm * cm; h22 += a2;
+    const T f0 = a0 * e0, f1 = a1 * e1;
+    b0 -= cm * f0 - sm * f1; b1 -= sm * f0 + cm * f1; b2 -= a2 * et;
+    return rho;
+}
+
 // ------------------------------------------------------------------------------------------------
 // K1 lin_lm: per landmark — landmark-side linearisation of its LM edges.
 //   reads : slot planes zx zy w0 w1 + pose index (coalesced), pose state ps[i] = (x,y,c,s) (gather)
 //   writes: slot planes a0 a1 ppx ppy (lm-major copy), lmrec[l][2..6] = Dl^-1, u
-template <typename T, int G>
+// PRI = 1: the landmark priors (type 4: D_l += Omega_w, b_l -= Omega_w (l - m)) before the inverse, and one chi^2 partial of them per
+// workgroup into pa.lm_chi (every wave reaches the workgroup sum: none leaves early)
+template <typename T, int G, int PRI = 0>
 __global__ __launch_bounds__(kBlock) void k_lin_lm(Table<T> tb, const T* __restrict__ ps, T* __restrict__ lmrec,
-                                                   const T* __restrict__ gauge_l, T* __restrict__ ninv, T lambda, int zero_fixed) {
+                                                   const T* __restrict__ gauge_l, T* __restrict__ ninv, T lambda, int zero_fixed,
+                                                   const PriorArgs<T> pa = PriorArgs<T>{nullptr, nullptr, nullptr, 0}) {
     const int slice = (tb.xcd ? xcd_block() : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
-    if (slice >= tb.n_slices) return;
+    const bool live = slice < tb.n_slices;
+    if (!PRI && !live) return;
     const int lane = threadIdx.x & 63;
     constexpr int VPS = 64 / G;
     const int l = slice * VPS + lane / G;
-    const bool valid = l < tb.n_vertices;
+    const bool valid = l < tb.n_vertices;      // (false on every lane of a wave past the last slice)
     const int lc = valid ? l : tb.n_vertices - 1;
     const T lx = lmrec[(size_t)lc * kLmRec], ly = lmrec[(size_t)lc * kLmRec + 1];
     T dxx = 0, dxy = 0, dyy = 0, g0 = 0, g1 = 0;
+    T chi = 0;
     const size_t S = tb.slots;
-    const uint32_t r0 = tb.row_off[slice], r1 = tb.row_off[slice + 1];
+    const uint32_t r0 = live ? tb.row_off[slice] : 0u, r1 = live ? tb.row_off[slice + 1] : 0u;
     for (uint32_t row = r0; row < r1; ++row) {
         const size_t k = (size_t)row * 64 + lane;
         const uint32_t i = tb.idx[k];
@@ -164,6 +192,18 @@ __global__ __launch_bounds__(kBlock) void k_lin_lm(Table<T> tb, const T* __restr
     if (valid && (lane % G) == 0) {
         // lambda: the LM-style damping of the reference's Python optimizer (H + lambda I, graph_optimizer.py:42), 0 under the
         // cpu/eigen rules; zero_fixed: that optimizer also zeroes b at fixed vertices (:150), OptimizerCpu.h does not
+        if constexpr (PRI != 0) {
+            for (uint32_t k = pa.off[l]; k < pa.off[l + 1]; ++k) {
+                const T* q = pa.rec + (size_t)k * PRI_LM_REC;
+                const auto m = ld2<T>(q + PRL_MX), w = ld2<T>(q + PRL_W0);
+                const T e0 = lx - m.x, e1 = ly - m.y;
+                T rho, hw;
+                huber<T>(w.x * e0 * e0 + w.y * e1 * e1, rho, hw);
+                const T a0 = hw * w.x, a1 = hw * w.y;
+                dxx += a0; dyy += a1; g0 -= a0 * e0; g1 -= a1 * e1;
+                chi += rho;
+            }
+        }
         const T ga = gauge_l[l];
         if (zero_fixed && ga > T(0)) { g0 = 0; g1 = 0; }
         T ixx, ixy, iyy;
@@ -174,6 +214,11 @@ __global__ __launch_bounds__(kBlock) void k_lin_lm(Table<T> tb, const T* __restr
         T* nq = ninv + (size_t)l * kNinvRec;
         nq[0] = ixx; nq[1] = ixy; nq[2] = iyy;
     }
+    if constexpr (PRI != 0) {
+        __shared__ T red[kWavesPerBlock];
+        const T total = block_sum<T>(chi, red);
+        if (threadIdx.x == 0) pa.lm_chi[blockIdx.x] = total;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -183,11 +228,14 @@ __global__ __launch_bounds__(kBlock) void k_lin_lm(Table<T> tb, const T* __restr
 // OJ = 1: pose-pose slots in GENERAL form (tsgo_math.h: eight dynamic planes per slot, the slot's own row block of the Hessian) — what
 // analytic ODOM Jacobians (odom_analytic, tsgo_config.odom_jacobian) and virtual landmark measurements (edge type 2, kVlmMask) need;
 // ODOM edges under the reference's constant Jacobians are written in that form too when the graph holds the other kind.
-template <typename T, int G, int OJ = 0>
+// PRI = 1: the pose priors (type 3, pose_prior_fold) of the pose in the epilogue, before a fixed pose's gradient is zeroed, and the landmark
+// priors' chi^2 partials (pa.lm_chi, left by k_lin_lm<.., 1>) in workgroup 0's partial.  The host lists only the priors of owned poses.
+template <typename T, int G, int OJ = 0, int PRI = 0>
 __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, const T* __restrict__ ps,
                                                      const T* __restrict__ lmrec, const T* __restrict__ gauge_p,
                                                      int pose_first, int pose_last, T* __restrict__ part,
-                                                     T* __restrict__ chi_part, T lambda, int zero_fixed, int odom_analytic = 0) {
+                                                     T* __restrict__ chi_part, T lambda, int zero_fixed, int odom_analytic = 0,
+                                                     const PriorArgs<T> pa = PriorArgs<T>{nullptr, nullptr, nullptr, 0}) {
     __shared__ T red[kWavesPerBlock];
     const int slice = (tb.xcd ? xcd_block() : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
     const bool live = slice < tb.n_slices;
@@ -300,6 +348,12 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, c
             o[0] = c * c * sA0 + s * s * sA1 + od0 + ga; o[1] = c * s * (sA0 - sA1) + od01; o[3] = s * s * sA0 + c * c * sA1 + od1 + ga;
             o[2] = -(c * sAv0 - s * sAv1) + od02; o[4] = -(s * sAv0 + c * sAv1) + od12; o[5] = sVV + od2 + ga;
             o[6] = c * ge0 - s * ge1 + og0; o[7] = s * ge0 + c * ge1 + og1; o[8] = -get + og2;
+            if constexpr (PRI != 0) {
+                T h00 = 0, h01 = 0, h11 = 0, h22 = 0, b0 = 0, b1 = 0, b2 = 0;
+                for (uint32_t k = pa.off[i]; k < pa.off[i + 1]; ++k)
+                    chi += pose_prior_fold<T>(pa.rec + (size_t)k * PRI_POSE_REC, x0, y0, c, s, h00, h01, h11, h22, b0, b1, b2);
+                o[0] += h00; o[1] += h01; o[3] += h11; o[5] += h22; o[6] += b0; o[7] += b1; o[8] += b2;
+            }
             if (fixed_here) { o[6] = 0; o[7] = 0; o[8] = 0; }
             o[9] = c * c * K00 - 2 * c * s * K01 + s * s * K11;
             o[10] = c * s * (K00 - K11) + (c * c - s * s) * K01;
@@ -307,6 +361,9 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, c
             o[11] = -(c * Kv0 - s * Kv1); o[13] = -(s * Kv0 + c * Kv1); o[14] = vKv;
             o[15] = -(c * wu0 - s * wu1); o[16] = -(s * wu0 + c * wu1); o[17] = wut;
         }
+    }
+    if constexpr (PRI != 0) {
+        if (blockIdx.x == 0) for (int k = threadIdx.x; k < pa.n_lm_chi; k += kBlock) chi += pa.lm_chi[k];
     }
     const T total = block_sum<T>(chi, red);
     if (threadIdx.x == 0) chi_part[blockIdx.x] = total;

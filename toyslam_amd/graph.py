@@ -1,7 +1,8 @@
 """The OptGraph model on the Python host side.
 
 Two views of the same thing:
-  * OptGraph / VertexPose2d / Vertex2d / EdgeOdometry2d / EdgeLandmark2d (+ EdgeVirtualLandmark2d, the reference's commented-out sketch) — same names, constructor
+  * OptGraph / VertexPose2d / Vertex2d / EdgeOdometry2d / EdgeLandmark2d (+ EdgeVirtualLandmark2d, the reference's commented-out sketch,
+    and the unary priors EdgePosePrior2d / EdgeLandmarkPrior2d, this package's own) — same names, constructor
     arguments and get_type()/get_dims() values as the reference's python/optimizer/opt_graph.py:1-31,
     vertices.py:18-46 and edges2d.py:14-81, so code written against those keeps working;
   * GraphArrays — the structure-of-arrays form the C ABI takes (include/tsgo.h, struct tsgo_graph).
@@ -82,6 +83,42 @@ class EdgeVirtualLandmark2d:
         return self.id_1 if index == 0 else self.id_2
 
 
+class EdgePosePrior2d:
+    """Pose prior (edge type 3, include/tsgo.h): an absolute measurement of one pose in the world frame (a GNSS fix, a soft anchor).
+    measurement: (x, y, theta) or a 3x3 homogeneous transform; information: 3 x 3 (its diagonal is used, as for every other edge).
+    Unary: get_id(0) == get_id(1) == id.  Behind the C ABI only: remote.graph_to_bytes refuses it."""
+
+    def __init__(self, id, measurement, information):
+        self.id_1 = self.id_2 = id
+        m = np.asarray(measurement, dtype=np.float64)
+        if m.shape == (3, 3):
+            m = np.array([m[0, 2], m[1, 2], np.arctan2(m[1, 0], m[0, 0])])
+        self.measurement = m.reshape(-1)[:3]
+        self.information = np.asarray(information, dtype=np.float64)
+
+    def get_type(self):
+        return 3
+
+    def get_id(self, index):
+        return self.id_1
+
+
+class EdgeLandmarkPrior2d:
+    """Landmark prior (edge type 4, include/tsgo.h): an absolute (x, y) of one landmark (a surveyed point); information 2 x 2
+    (its diagonal is used).  Unary: get_id(0) == get_id(1) == id.  Behind the C ABI only."""
+
+    def __init__(self, id, measurement, information):
+        self.id_1 = self.id_2 = id
+        self.measurement = np.asarray(measurement, dtype=np.float64).reshape(-1)[:2]
+        self.information = np.asarray(information, dtype=np.float64)
+
+    def get_type(self):
+        return 4
+
+    def get_id(self, index):
+        return self.id_1
+
+
 class OptGraph:
     """Container the optimizers consume: id -> vertex (insertion-ordered), a list of edges, the set of gauge-fixed ids.
 
@@ -151,7 +188,8 @@ class tsgo_graph(C.Structure):
 
 class GraphArrays:
     """SoA form of an OptGraph (struct tsgo_graph).  v_pos: (x, y, theta) / (x, y, 0); e_meas: 3x3
-    row-major for ODOM, (range, bearing, 0..) for LM; e_inf: information diagonal (3 slots)."""
+    row-major for ODOM, (range, bearing, 0..) for LM, (x, y, theta, 0..) / (x, y, 0..) for a pose / landmark prior; e_inf: information
+    diagonal (3 slots)."""
 
     def __init__(self, v_id, v_type, v_pos, e_type, e_ids, e_meas, e_inf, fixed):
         self.v_id = np.ascontiguousarray(v_id, np.uint32)
@@ -225,6 +263,8 @@ class GraphArrays:
                 m[:] = meas.reshape(-1); w[:] = np.diag(inf)
             elif e.get_type() == 2:
                 m[:4] = meas.reshape(-1)[:4]; w[:2] = np.diag(inf)[:2]
+            elif e.get_type() == 3:
+                m[:3] = meas.reshape(-1)[:3]; w[:] = np.diag(inf)[:3]
             else:
                 m[:2] = meas.reshape(-1)[:2]; w[:2] = np.diag(inf)[:2]
             etype.append(e.get_type()); eids.append([e.id_1, e.id_2]); emeas.append(m); einf.append(w)
