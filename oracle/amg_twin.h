@@ -1,6 +1,7 @@
 // amg_twin.h — TEST INFRASTRUCTURE: scalar CPU twin of the device-side numeric multigrid
 // (toyslam_amd/csrc/tsgo_amg_kernels.h), operating on the product's symbolic hierarchy (host/amg.h).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -37,9 +38,17 @@ struct Hierarchy {
     int n_last = 0;
     std::vector<std::vector<double>> r, z, res, z2;     // per level work vectors (3 per node), level 0 unused for r
     std::vector<double> omega;                          // smoother damping per level (power-iteration estimate)
+    // Deliberate defects, for the sensitivity checks of the operator tests (oracle_twin_perturb; all off by default): the smoother
+    // damping of every level scaled, extra sweeps per side on the coarse levels, and the self block of one level-0 prolongator row
+    // transposed before the Galerkin products are formed from it.
+    double pert_omega = 1.0; int pert_nu = 0; int pert_transpose_row = -1;
+
+    std::vector<int> sweeps_list;                       // TSGO_SWEEPS_LIST, as the engine reads it (tsgo_hip.hip: nu_at): sweeps per side on levels 1, 2, ...
 
     void alloc(const AmgSym& s) {
         sym = &s;
+        sweeps_list.clear();
+        if (const char* e = getenv("TSGO_SWEEPS_LIST")) for (const char* q = e; *q;) { sweeps_list.push_back(std::max(1, std::min(4, atoi(q)))); while (*q && *q != ',') ++q; if (*q == ',') ++q; }
         const size_t nl = s.levels.size();
         A.resize(nl); Dinv.resize(nl); P.resize(nl); T.resize(nl); r.resize(nl + 1); z.resize(nl + 1); res.resize(nl + 1); z2.resize(nl + 1);
         for (size_t l = 0; l < nl; ++l) {
@@ -78,6 +87,9 @@ struct Hierarchy {
                     const bool dead = dd[0] == 0 && dd[4] == 0 && dd[8] == 0;       // vertex without edges: keep it out of the coarse space
                     if (L.p_self[pb] && !dead) { o[0] += 1; o[4] += 1; o[8] += 1; o[2] += -L.rel[2 * (size_t)i + 1]; o[5] += L.rel[2 * (size_t)i]; }
                 }
+            if (l == 0 && pert_transpose_row >= 0 && pert_transpose_row < L.n)
+                for (int pb = L.P.ptr[pert_transpose_row]; pb < L.P.ptr[pert_transpose_row + 1]; ++pb)
+                    if (L.p_self[pb]) { double* o = &P[l][(size_t)pb * 9]; std::swap(o[1], o[3]); std::swap(o[2], o[6]); std::swap(o[5], o[7]); }
             // T = A P
             for (int tb = 0; tb < L.T.nnz(); ++tb) {
                 double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -115,6 +127,7 @@ struct Hierarchy {
                 v.swap(u);
             }
             if (nk > 0 && nk1 > 0) omega[l] = std::min(1.0, 1.6 / (1.05 * std::sqrt(nk / nk1)));
+            omega[l] *= pert_omega;
             if (getenv("TSGO_TWIN_RHO")) std::fprintf(stderr, "[twin] level %zu: n = %d, blocks/row = %.1f, rho ~ %.3f, omega = %.3f\n", l, L.n, (double)L.A.nnz() / L.n, std::sqrt(nk / nk1), omega[l]);
         }
         // coarsest: dense inverse by Gauss-Jordan (SPD, no pivoting needed; partial pivoting kept for safety)
@@ -192,7 +205,7 @@ struct Hierarchy {
         }
         const AmgLevel& L = sym->levels[l];
         static const int nu_env = getenv("TSGO_TWIN_NU") ? atoi(getenv("TSGO_TWIN_NU")) : 0;
-        const int nu = nu_env ? nu_env : tsgo::sweeps_per_side((size_t)l, L.n);
+        const int nu = (nu_env ? nu_env : (sweeps_list.empty() ? tsgo::sweeps_per_side((size_t)l, L.n) : sweeps_list[std::min(l - 1, sweeps_list.size() - 1)])) + pert_nu;
         static const int gam = getenv("TSGO_TWIN_GAMMA") ? atoi(getenv("TSGO_TWIN_GAMMA")) : 1;
         dinv_apply(Dinv[l], r[l], z[l], L.n, false, omega[l]);
         for (int s = 1; s < nu; ++s) {

@@ -69,6 +69,8 @@ def lib():
         L.oracle_sparse_optimize.argtypes = _GRAPH + [f64p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                                       ALLREDUCE_FN, C.c_void_p, f64p, i32p, i32p, i32p, f64p,
                                                       f64p, f64p, C.c_int, C.c_double]
+        L.oracle_twin_precond.argtypes = _GRAPH + [C.c_int, C.c_int, C.c_int, C.c_int, f64p, f64p, C.c_void_p, C.c_void_p, f64p, i32p]
+        L.oracle_twin_perturb.argtypes = [C.c_double, C.c_int, C.c_int]; L.oracle_twin_perturb.restype = None
         L.oracle_set_threads.argtypes = [C.c_int]
         L.oracle_set_threads.restype = None
         L.oracle_set_threads(default_threads())
@@ -211,3 +213,63 @@ def sparse_optimize(g, iterations, pcg_tol=1e-12, max_cg=100000, rank=0, world=1
     n = int(ir[0])
     return dict(v_pos=out, chi2=chi2[:n].copy(), iters=n, stop=STOP[int(sr[0])], delta_norm=float(dn[0]),
                 cg_iters=cg[:n].copy(), seconds_linearize=float(tl[0]), seconds_solve=float(ts[0]))
+
+
+def schur_dense(g, diag_add=None, with_magnitude=False):
+    """The reduced pose system as a dense f64 matrix: S = Hpp - Hpl Hll^-1 Hlp from the dense restatement's H, rows and columns in
+    the order of the graph's pose vertices (3 per pose).  Follows set_odom_jacobian like every other entry point.  diag_add: (V, 3, 3)
+    blocks added to the vertices' diagonal blocks of H first (the dense restatement knows edge types 0-2: the caller restates priors).
+    with_magnitude: also |Hpp| + |Hpl| |Hll^-1| |Hlp|, the size of the terms a product that never forms S sums (>= |S| entry by entry)."""
+    H, _b, _err, idx = linearize(g)
+    pose = np.where(g.v_type == 0)[0]; lm = np.where(g.v_type == 1)[0]
+    if diag_add is not None:
+        for v in range(len(g.v_id)):
+            m = 3 if g.v_type[v] == 0 else 2
+            H[idx[v]:idx[v] + m, idx[v]:idx[v] + m] += diag_add[v][:m, :m]
+    ip = (idx[pose][:, None] + np.arange(3)[None, :]).reshape(-1)
+    il = (idx[lm][:, None] + np.arange(2)[None, :]).reshape(-1)
+    S = H[np.ix_(ip, ip)].copy()
+    mag = np.abs(S)
+    if len(il):
+        Hpl = H[np.ix_(ip, il)]
+        Hll = H[np.ix_(il, il)]
+        k = np.arange(len(lm))
+        blocks = Hll.reshape(len(lm), 2, len(lm), 2)[k, :, k, :]          # landmarks couple to poses only: Hll is block diagonal
+        assert np.isclose(np.abs(Hll).sum(), np.abs(blocks).sum(), rtol=1e-12)
+        inv = np.linalg.pinv(blocks, hermitian=True)                      # (a landmark without edges has a zero block and adds nothing)
+        S -= np.einsum("plx,lxy,qly->pq", Hpl.reshape(len(ip), len(lm), 2), inv, Hpl.reshape(len(ip), len(lm), 2), optimize=True)
+        a = np.abs(Hpl).reshape(len(ip), len(lm), 2)
+        mag += np.einsum("plx,lxy,qly->pq", a, np.abs(inv), a, optimize=True)
+    S = 0.5 * (S + S.T)
+    return (S, 0.5 * (mag + mag.T)) if with_magnitude else S
+
+
+PERTURBATIONS = ("omega", "nu", "transpose")
+
+
+def twin_precond(g, R, precond="amg", lanes_per_pose=0, lanes_per_lm=0, perturb=None, transpose_pose=0):
+    """The sparse twin's preconditioner on the columns of R (3 P rows in the order of the graph's pose vertices), f64 throughout:
+    level-0 pre-smoothing, the cycle of the coarse levels, prolongation and level-0 post-smoothing ("amg"), or the inverse diagonal
+    blocks of S ("jacobi").  The hierarchy is the one host/amg.h builds under the process's TSGO_AGG* / TSGO_SWEEPS_LIST variables and
+    the given layout options; set_cycle_level0 and set_odom_jacobian apply.  perturb: None, or one deliberate defect — "omega" (the
+    smoother damping of every level times 1.05), "nu" (one more sweep per side on the coarse levels), "transpose" (the self block of
+    the level-0 prolongator row of pose `transpose_pose` transposed).
+    Returns (Z, info): info = dict(rows=[block rows per level, the dense one last], checksum, omega=[damping per level],
+    sweeping_levels=coarse levels that run sweeps, agg_min / agg_max=the smallest / largest level-0 aggregate,
+    agg_extremes=a pose of each, agg=the level-0 aggregate of every pose)."""
+    R = np.asarray(R, np.float64)
+    cols = np.ascontiguousarray(R.reshape(R.shape[0], -1).T)
+    Z = np.zeros_like(cols)
+    info = np.zeros(14, np.int64); ck = C.c_uint64(); om = np.zeros(8); agg = np.zeros(max(R.shape[0] // 3, 1), np.int32)
+    L = lib()
+    L.oracle_twin_perturb(*{None: (1.0, 0, -1), "omega": (1.05, 0, -1), "nu": (1.0, 1, -1), "transpose": (1.0, 0, int(transpose_pose))}[perturb])
+    try:
+        rc = L.oracle_twin_precond(*g.args(), PRECOND[precond], int(lanes_per_pose), int(lanes_per_lm), cols.shape[0], cols, Z,
+                                   info.ctypes.data, C.addressof(ck), om, agg)
+    finally:
+        L.oracle_twin_perturb(1.0, 0, -1)
+    if rc:
+        raise RuntimeError("oracle_twin_precond rc=%d" % rc)
+    n = int(info[0])
+    return np.ascontiguousarray(Z.T).reshape(R.shape), dict(rows=[int(v) for v in info[1:1 + n]], checksum=int(ck.value), omega=om[:max(n - 1, 0)].copy(),
+                                                           sweeping_levels=int(info[9]), agg_max=int(info[10]), agg_min=int(info[13]), agg_extremes=(int(info[11]), int(info[12])), agg=agg)

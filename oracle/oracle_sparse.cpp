@@ -30,6 +30,7 @@
 #include "host/problem.h"
 #include "tsgo_math.h"
 
+static double g_pert_omega = 1.0; static int g_pert_nu = 0, g_pert_transpose_pose = -1;      // oracle_twin_perturb
 static int g_cycle_level0 = 0;     // oracle_set_cycle_level0: 0 implicit Schur products inside the multigrid cycle, 1 the explicit level-0 matrix
 extern "C" int oracle_get_odom_jacobian(void);      // oracle_dense.cpp: 0 = the reference's constants, 1 = analytic (extension)
 
@@ -46,6 +47,8 @@ struct Twin {
     std::vector<double> pa, la;                     // 4 planes each: a0, a1, ppx, ppy (pose-major / lm-major)
     std::vector<double> oa;                         // 3 planes (odom)
     std::vector<double> dlinv, u, t;                // per landmark: 3, 2, 2
+    std::vector<double> pri_p, pri_l;               // unary priors (edge types 3, 4): records behind pr.prior_p_off / prior_l_off (host/problem.h)
+    double chi_lm_prior = 0;                        // chi^2 of the landmark priors (lin_lm), added to the total by lin_pose
     std::vector<double> part;                       // per pose 18: Dp(6) g(3) Sd(6) Wu(3); + 1 chi2 at the end
     std::vector<double> dp, minv, r, z, p, q, x, s; // per pose
     double chi2 = 0;
@@ -63,8 +66,8 @@ struct Twin {
 
     void allreduce(double* b, int64_t n) { if (hook && pr.world > 1) hook(b, n, hook_ctx); }
 
-    std::string init(const tsgo_graph& g, int rank, int world) {
-        tsgo::BuildOptions bo; bo.rank = rank; bo.world = world; bo.lanes_per_pose = 1; bo.lanes_per_lm = 1;
+    std::string init(const tsgo_graph& g, int rank, int world, int lanes_per_pose = 1, int lanes_per_lm = 1) {
+        tsgo::BuildOptions bo; bo.rank = rank; bo.world = world; bo.lanes_per_pose = lanes_per_pose; bo.lanes_per_lm = lanes_per_lm;
         std::string e = tsgo::build_problem(g, bo, pr);
         if (!e.empty()) return e;
         P = pr.P; L = pr.L;
@@ -73,6 +76,11 @@ struct Twin {
             th[i] = pr.pose_xyt[3 * (size_t)i + 2];
             ps[4 * (size_t)i] = pr.pose_xyt[3 * (size_t)i]; ps[4 * (size_t)i + 1] = pr.pose_xyt[3 * (size_t)i + 1];
             ps[4 * (size_t)i + 2] = std::cos(th[i]); ps[4 * (size_t)i + 3] = std::sin(th[i]);
+        }
+        if (pr.has_priors) {
+            pri_p.assign(pr.prior_p_edge.size() * tsgo::PRI_POSE_REC, 0); pri_l.assign(pr.prior_l_edge.size() * tsgo::PRI_LM_REC, 0);
+            for (size_t k = 0; k < pr.prior_p_edge.size(); ++k) { const size_t e = pr.prior_p_edge[k]; tsgo::prior_static(3, g.e_meas + 9 * e, g.e_inf + 3 * e, &pri_p[k * tsgo::PRI_POSE_REC]); }
+            for (size_t k = 0; k < pr.prior_l_edge.size(); ++k) { const size_t e = pr.prior_l_edge[k]; tsgo::prior_static(4, g.e_meas + 9 * e, g.e_inf + 3 * e, &pri_l[k * tsgo::PRI_LM_REC]); }
         }
         analytic = oracle_get_odom_jacobian() != 0;
         pr.odom_analytic = analytic;
@@ -197,7 +205,8 @@ struct Twin {
     // K1: landmark side of the linearisation (B^T W B, B^T W e), block inverse, u = Dl^-1 g_l
     void lin_lm() {
         const tsgo::SellTable& tb = pr.by_lm; const size_t S = tb.slots();
-        #pragma omp parallel for schedule(static)
+        double chi_pr = 0;
+        #pragma omp parallel for schedule(static) reduction(+ : chi_pr)
         for (int l = 0; l < L; ++l) {
             double dxx = pr.gauge_l[l] + lambda, dxy = 0, dyy = pr.gauge_l[l] + lambda, g0 = 0, g1 = 0;
             const double lx = ls[2 * (size_t)l], ly = ls[2 * (size_t)l + 1];
@@ -211,11 +220,20 @@ struct Twin {
                 const double f0 = o.a0 * o.e0, f1 = o.a1 * o.e1;          // g_l = -B^T W e = -R (f0, f1)
                 g0 -= c * f0 - sn * f1; g1 -= sn * f0 + c * f1;
             });
+            if (pr.has_priors)      // landmark priors (type 4, as k_lin_lm<.., 1>): D_l += Omega_w, g_l -= Omega_w (l - m)
+                for (uint32_t k = pr.prior_l_off[l]; k < pr.prior_l_off[l + 1]; ++k) {
+                    const double* q = &pri_l[(size_t)k * tsgo::PRI_LM_REC];
+                    const double e0 = lx - q[tsgo::PRL_MX], e1 = ly - q[tsgo::PRL_MY];
+                    double rho, hw; tsgo::huber<double>(q[tsgo::PRL_W0] * e0 * e0 + q[tsgo::PRL_W1] * e1 * e1, rho, hw);
+                    const double a0 = hw * q[tsgo::PRL_W0], a1 = hw * q[tsgo::PRL_W1];
+                    dxx += a0; dyy += a1; g0 -= a0 * e0; g1 -= a1 * e1; chi_pr += rho;
+                }
             if (zero_fixed && pr.gauge_l[l] > 0) { g0 = 0; g1 = 0; }
             double ixx, ixy, iyy; tsgo::inv_sym2(dxx, dxy, dyy, ixx, ixy, iyy);
             dlinv[3 * (size_t)l] = ixx; dlinv[3 * (size_t)l + 1] = ixy; dlinv[3 * (size_t)l + 2] = iyy;
             u[2 * (size_t)l] = ixx * g0 + ixy * g1; u[2 * (size_t)l + 1] = ixy * g0 + iyy * g1;
         }
+        chi_lm_prior = chi_pr;
     }
 
     // K2: pose side (A^T W A, A^T W e, Schur diagonal W Dl^-1 W^T, W u), ODOM rows, chi^2
@@ -300,9 +318,21 @@ struct Twin {
                 }
                 if (!second) chi += o.rho;
             });
+            if (pr.has_priors)      // pose priors (type 3, as pose_prior_fold): e_t = R_m^T (t - t_m), e_th = wrap(th - m_th), J = blockdiag(R_m^T, 1)
+                for (uint32_t k = pr.prior_p_off[i]; k < pr.prior_p_off[i + 1]; ++k) {
+                    const double* q = &pri_p[(size_t)k * tsgo::PRI_POSE_REC];
+                    const double cm = q[tsgo::PRI_C], sm = q[tsgo::PRI_S], dx = x0 - q[tsgo::PRI_MX], dy = y0 - q[tsgo::PRI_MY];
+                    const double e0 = cm * dx + sm * dy, e1 = cm * dy - sm * dx, et = std::atan2(sn * cm - c * sm, c * cm + sn * sm);
+                    double rho, hw; tsgo::huber<double>(q[tsgo::PRI_W0] * e0 * e0 + q[tsgo::PRI_W1] * e1 * e1 + q[tsgo::PRI_W2] * et * et, rho, hw);
+                    const double a0 = hw * q[tsgo::PRI_W0], a1 = hw * q[tsgo::PRI_W1], a2 = hw * q[tsgo::PRI_W2];
+                    o18[0] += a0 * cm * cm + a1 * sm * sm; o18[1] += (a0 - a1) * cm * sm; o18[3] += a0 * sm * sm + a1 * cm * cm; o18[5] += a2;
+                    const double f0 = a0 * e0, f1 = a1 * e1;
+                    o18[6] -= cm * f0 - sm * f1; o18[7] -= sm * f0 + cm * f1; o18[8] -= a2 * et;
+                    chi += rho;
+                }
             if (zero_fixed && pr.gauge_p[i] > 0) { o18[6] = 0; o18[7] = 0; o18[8] = 0; }
         }
-        part[(size_t)P * 18] = chi;
+        part[(size_t)P * 18] = chi + chi_lm_prior;      // (every shard adds the priors of the landmarks it owns)
     }
 
     // K3: M = Dp + gauge - Sd, M^-1, reduced rhs, CG start vectors.  Returns gamma0 = r^T M^-1 r.
@@ -592,6 +622,65 @@ extern "C" {
 // OpenMP threads used by the twin's loops (a GPU box exposes far more logical CPUs than its share).
 void oracle_set_threads(int n) { omp_set_num_threads(n < 1 ? 1 : n); }
 void oracle_set_cycle_level0(int explicit_matrix) { g_cycle_level0 = explicit_matrix ? 1 : 0; }
+
+// Deliberate defects of the twin's cycle for oracle_twin_precond (sensitivity checks; 1, 0, -1 = none): the smoother damping of every
+// level times omega_scale, nu_add more sweeps per side on the coarse levels, the self block of the level-0 prolongator row of the
+// transpose_pose-th pose (graph order) transposed.
+void oracle_twin_perturb(double omega_scale, int nu_add, int transpose_pose) { g_pert_omega = omega_scale; g_pert_nu = nu_add; g_pert_transpose_pose = transpose_pose; }
+
+// The twin's preconditioner as an operator, f64 throughout: Z = M^-1 R for n_cols columns of 3 P doubles each, in the order of the
+// graph's POSE vertices.  precond 1: level-0 pre-smoothing, Hierarchy::cycle(1), prolongation, level-0 post-smoothing on one
+// linearisation at the given state, with a hierarchy built for it; 0: the inverse 3x3 diagonal blocks of S.  lanes_*: the layout
+// options of the handle it is compared with (0 = the builder's choice; the checksum covers the slot tables).
+// info_out[0] = levels n, [1 .. n] = their block rows (the dense level last), [9] = levels whose nu_add counts (coarse levels that
+// run sweeps), [10] / [13] = the size of the largest / smallest aggregate of level 0, [12] / [11] = a pose of it (graph order); checksum_out: tsgo_amg_info.checksum of the hierarchy; omega_out[8];
+// agg_out[P]: the level-0 aggregate of every pose (graph order).
+int oracle_twin_precond(GRAPH_ARGS, int precond, int lanes_per_pose, int lanes_per_lm, int n_cols, const double* R, double* Z,
+                        int64_t* info_out, uint64_t* checksum_out, double* omega_out, int32_t* agg_out) {
+    Twin tw;
+    const tsgo_graph g = make_view(GRAPH_PASS);
+    if (!tw.init(g, 0, 1, lanes_per_pose, lanes_per_lm).empty()) return -2;
+    if (precond == 1 && !tw.enable_amg(g).empty()) return -5;
+    const int P = tw.P;
+    std::vector<int> rank_of_vertex((size_t)nV, -1), of_graph((size_t)P);
+    { std::vector<char> is_pose((size_t)nV, 0); for (int i = 0; i < P; ++i) is_pose[(size_t)tw.pr.pose_vertex[i]] = 1;
+      int k = 0; for (int v = 0; v < nV; ++v) if (is_pose[(size_t)v]) rank_of_vertex[(size_t)v] = k++; }
+    for (int i = 0; i < P; ++i) of_graph[(size_t)i] = rank_of_vertex[(size_t)tw.pr.pose_vertex[i]];
+    if (precond == 1) {
+        tw.hier.pert_omega = g_pert_omega; tw.hier.pert_nu = g_pert_nu; tw.hier.pert_transpose_row = -1;
+        for (int i = 0; i < P; ++i) if (of_graph[(size_t)i] == g_pert_transpose_pose) tw.hier.pert_transpose_row = i;
+    }
+    tw.linearize();
+    if (info_out) {
+        for (int k = 0; k < 14; ++k) info_out[k] = 0;
+        int n = 0;
+        if (precond == 1) {
+            for (const auto& L : tw.amg.levels) if (n < 8) info_out[1 + n++] = L.n;
+            if (n < 8) info_out[1 + n++] = tw.amg.A_last.n_rows;
+            info_out[9] = tw.amg.levels.empty() ? 0 : (int64_t)tw.amg.levels.size() - 1;
+            if (!tw.amg.levels.empty()) {
+                const auto& L0 = tw.amg.levels[0];
+                std::vector<int> cnt(L0.n_agg, 0); for (int a : L0.agg) ++cnt[a];
+                int amin = 0, amax = 0;
+                for (int a = 0; a < L0.n_agg; ++a) { if (cnt[a] < cnt[amin]) amin = a; if (cnt[a] > cnt[amax]) amax = a; }
+                info_out[10] = cnt.empty() ? 0 : cnt[amax]; info_out[13] = cnt.empty() ? 0 : cnt[amin];
+                for (int i = P - 1; i >= 0; --i) { if (L0.agg[i] == amin) info_out[11] = of_graph[(size_t)i]; if (L0.agg[i] == amax) info_out[12] = of_graph[(size_t)i]; }
+            }
+        }
+        info_out[0] = n;
+    }
+    if (agg_out) for (int i = 0; i < P; ++i) agg_out[(size_t)of_graph[(size_t)i]] = precond == 1 && !tw.amg.levels.empty() ? tw.amg.levels[0].agg[i] : -1;
+    if (checksum_out) *checksum_out = precond == 1 ? tsgo::amg_checksum(tw.pr, tw.amg) : 0;
+    if (omega_out) for (int l = 0; l < 8; ++l) omega_out[l] = precond == 1 && (size_t)l < tw.hier.omega.size() ? tw.hier.omega[l] : 0.0;
+    for (int c = 0; c < n_cols; ++c) {
+        const double* rin = R + (size_t)c * 3 * P; double* zo = Z + (size_t)c * 3 * P;
+        for (int i = 0; i < P; ++i) for (int k = 0; k < 3; ++k) tw.r[3 * (size_t)i + k] = rin[3 * (size_t)of_graph[i] + k];
+        if (precond == 1) tw.amg_apply();
+        else for (int i = 0; i < P; ++i) tsgo::sym3_mul(&tw.minv[6 * (size_t)i], tw.r[3 * (size_t)i], tw.r[3 * (size_t)i + 1], tw.r[3 * (size_t)i + 2], tw.z[3 * (size_t)i], tw.z[3 * (size_t)i + 1], tw.z[3 * (size_t)i + 2]);
+        for (int i = 0; i < P; ++i) for (int k = 0; k < 3; ++k) zo[3 * (size_t)of_graph[i] + k] = tw.z[3 * (size_t)i + k];
+    }
+    return 0;
+}
 
 // One Gauss-Newton step at the given state: delta (3 per vertex, graph order; landmarks of other
 // shards are left 0), chi2, PCG iterations.  hook/ctx: all-reduce(sum) over shards, may be NULL.

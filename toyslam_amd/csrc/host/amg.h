@@ -152,4 +152,26 @@ std::string build_amg_sharded(const tsgo_graph& g, const Problem& local, AmgSym&
 // every level from pose_xyt (3 per pose, internal numbering), exactly as build_amg does.
 void refresh_amg_geometry(const std::vector<double>& pose_xyt, AmgSym& amg);
 
+// FNV-1a over every slot table, numbering, pattern and gather list, in order (tsgo_amg_info.checksum): equal checksums = the same
+// layout and the same symbolic hierarchy, whoever built them (tsgo_amg_probe; the CPU twin reports the one of the hierarchy it runs on)
+struct AmgFnv {
+    uint64_t h = 1469598103934665603ull;
+    void bytes(const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } }
+    template <typename V> void vec(const V& v) { const uint64_t n = v.size(); bytes(&n, sizeof(n)); if (n) bytes(v.data(), n * sizeof(v[0])); }
+    void table(const SellTable& t) { vec(t.row_off); vec(t.idx); vec(t.edge); }
+    void csr(const BlockCsr& m) { vec(m.ptr); vec(m.col); }
+    void pairs(const PairList& p) { vec(p.ptr); vec(p.x); vec(p.y); }
+};
+inline uint64_t amg_checksum(const Problem& pr, const AmgSym& amg) {
+    AmgFnv f;
+    f.table(pr.by_pose); f.table(pr.by_lm); f.table(pr.odom); f.vec(pr.pose_vertex); f.vec(pr.lm_vertex); f.vec(pr.gauge_p); f.vec(pr.gauge_l);
+    f.vec(amg.order); f.vec(amg.schur.ptr); f.vec(amg.schur.slot_i); f.vec(amg.schur.slot_k); f.vec(amg.schur.od_ptr); f.vec(amg.schur.od_slot);
+    for (const auto& L : amg.levels) {
+        f.csr(L.A); f.vec(L.diag); f.vec(L.agg); f.vec(L.rel); f.vec(L.rig); f.csr(L.P); f.vec(L.p_self); f.pairs(L.p_src); f.csr(L.R); f.vec(L.r_to_p);
+        f.csr(L.T); f.pairs(L.t_src); f.pairs(L.a_src); f.vec(L.a_mirror);
+    }
+    f.csr(amg.A_last); f.vec(amg.diag_last);
+    return f.h;
+}
+
 }  // namespace tsgo

@@ -11,6 +11,7 @@
 //   engine/engine_solve.inc        the Gauss-Newton loop, the PCG drivers, read-outs
 //   engine/engine_probes.inc       timing probes (bench.py)
 //   engine/engine_marginals.inc    tsgo_marginals, tsgo_joint_marginals: batched PCG for blocks of H^-1
+//   engine/engine_testing.inc      tsgo_testing_apply (TSGO_TESTING builds only): the operators PCG applies, read out column by column
 //
 // There is NO CPU fallback in this file: every entry point that computes needs a gfx950 device and
 // returns an error otherwise.
@@ -156,6 +157,9 @@ struct IEngine {
     virtual void reset_history() = 0;
     virtual int marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, tsgo_marginal_stats* st) = 0;
     virtual int joint_marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, int64_t cov_cap, int* dim_out, tsgo_marginal_stats* st) = 0;
+#ifdef TSGO_TESTING
+    virtual int testing_apply(int which, const double* in, double* out, int n_cols) = 0;
+#endif
     ncclComm_t comm = nullptr;
     tsgo_local_group* lgroup = nullptr;      // in-process stand-in for the communicator (tests on a one-GPU box; always null outside TSGO_TESTING builds)
 };
@@ -433,6 +437,9 @@ template <typename T> struct Engine : IEngine {
 #include "engine/engine_solve.inc"
 #include "engine/engine_probes.inc"
 #include "engine/engine_marginals.inc"
+#ifdef TSGO_TESTING
+#include "engine/engine_testing.inc"
+#endif
 };
 
 }  // namespace
@@ -518,6 +525,10 @@ int tsgo_comm_init_local(tsgo_optimizer* o, tsgo_local_group* g) {
     if (o->cfg.world != g->world || o->cfg.rank < 0 || o->cfg.rank >= g->world) return tsgo::set_error(-1, "tsgo_comm_init_local: the handle's rank / world do not fit the group");
     o->eng->lgroup = g;
     return 0;
+}
+int tsgo_testing_apply(tsgo_optimizer* o, int32_t which, const double* in, double* out, int32_t n_cols) {
+    if (!o) return tsgo::set_error(-1, "tsgo_testing_apply: null handle");
+    return o->eng->testing_apply(which, in, out, n_cols);
 }
 #endif
 int tsgo_marginals(tsgo_optimizer* o, const uint32_t* ids, int32_t n_ids, double rel_tol, double* cov_out, tsgo_marginal_stats* stats) {

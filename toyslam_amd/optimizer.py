@@ -159,6 +159,15 @@ class HipOptimizer:
         return [dict(name=arr[k].name.decode(), where=arr[k].where.decode(), launches=arr[k].launches_per_iteration, us=arr[k].us, bytes=arr[k].bytes)
                 for k in range(n)]
 
+    def testing_apply(self, which, x):
+        """tsgo_testing_apply (testing=True handles): the operator `which` on the columns of x, shape (3 P,) or (3 P, n) in the order of
+        the graph's pose vertices; returns the same shape.  0 / 1: S x by PCG's / the cycle's product, 2: M^-1 x, 3: the batched cycle."""
+        x = np.asarray(x, np.float64)
+        cols = np.ascontiguousarray(x.reshape(x.shape[0], -1).T)      # one column per row: what the C side walks
+        out = np.zeros_like(cols)
+        _lib.check(self.lib, self.lib.tsgo_testing_apply(self.h, int(which), cols.ctypes.data, out.ctypes.data, cols.shape[0]), "tsgo_testing_apply")
+        return np.ascontiguousarray(out.T).reshape(x.shape)
+
     def comm_init_local(self, group):
         """group: a handle from local_group(world) shared by the handles of this process (one thread each)."""
         _lib.check(self.lib, self.lib.tsgo_comm_init_local(self.h, group), "tsgo_comm_init_local")
