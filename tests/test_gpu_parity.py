@@ -83,10 +83,13 @@ def test_lanes_per_vertex_variants_agree_with_dense(lanes):
     try:
         o.set_graph(g)
         r = o.solve_step()
+        names = "\n".join(e["name"] for e in o.profile_iteration(2))
     finally:
         o.close()
     assert abs(r["chi2"] - err) <= 1e-12 * err
     assert np.abs(r["delta"] - d_ref).max() <= 1e-8 * np.abs(d_ref).max()
+    # every arm of the lanes-per-vertex dispatch (8: the arm every other value falls through to) under the name of what it launched
+    assert "k_schur_pose<double, %d," % lanes[0] in names and "k_schur_lm<double, %d," % lanes[1] in names, names
 
 
 @pytest.mark.parametrize("precond", ["amg", "jacobi"])

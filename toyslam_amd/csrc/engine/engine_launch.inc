@@ -3,17 +3,24 @@
     // ---- in-situ profiler (tsgo_profile_iteration): an event before every launch of an eagerly launched iteration ----
     struct ProfMark { hipEvent_t e; char name[64]; char where[32]; double bytes; };
     std::vector<ProfMark> prof; size_t prof_n = 0; bool prof_on = false;
-    static const char* tname() { return sizeof(T) == 8 ? "double" : "float"; }
-    // name: the kernel symbol as rocprofv3 prints it, without arguments (printf-style), e.g. "k_schur_lm<double, 4, 0, 1>"
-    // PF(...): the arguments (byte models, labels) are evaluated only while a profile is being taken
+    template <typename U> static const char* tname_of() { return sizeof(U) == 8 ? "double" : "float"; }      // (every vector type is one of the two)
+    static const char* tname() { return tname_of<T>(); }
+    // PF(bytes, where, kernel, template arguments ...): a mark in front of a launch.  The name is the kernel symbol as rocprofv3 prints it, e.g.
+    // "k_schur_lm<double, 4, 0, 1>" (kernel_name(), tsgo_hip.hip), formatted from the template arguments of the launch next to it.
+    // The arguments (byte models, labels, names) are evaluated only while a profile is being taken
 #define PF(...) do { if (prof_on) pf(__VA_ARGS__); } while (0)
-    void pf(double bytes, const char* where, const char* fmt, ...) __attribute__((format(printf, 4, 5))) {
+    template <typename... A> void pf(double bytes, const char* where, const char* kernel, const A&... targs) {
         if (!prof_on) return;
         if (prof_n == prof.size()) { ProfMark m{}; if (hipEventCreate(&m.e) != hipSuccess) { prof_on = false; return; } prof.push_back(m); }
         ProfMark& m = prof[prof_n++];
-        va_list ap; va_start(ap, fmt); std::vsnprintf(m.name, sizeof(m.name), fmt, ap); va_end(ap);
+        std::snprintf(m.name, sizeof(m.name), "%s", kernel_name(kernel, targs...).c_str());
         std::snprintf(m.where, sizeof(m.where), "%s", where); m.bytes = bytes;
         (void)hipEventRecord(m.e, stream);
+    }
+    // a kernel on the engine's stream, kBlock threads per workgroup.  Every argument is listed: a kernel's default arguments do not travel
+    // with its address
+    template <typename... P, typename... A> void launch(void (*kernel)(P...), int grid, A&&... args) {
+        kernel<<<dim3(grid), dim3(kBlock), 0, stream>>>(std::forward<A>(args)...);
     }
     std::string lvl(const char* role, size_t l) const { return std::string(role) + " L" + std::to_string(l); }
     // algorithmic bytes of the table kernels (DESIGN.md section 4) and of the block-row kernels of the cycle
@@ -26,7 +33,6 @@
     double bytes_transfer(const DevLevel<T>& L, int vecs_fine, bool fine_is_l0 = false) const {
         return (double)L.nnzP * (4.0 * cyw() + 4) + (double)L.n * 3 * (fine_is_l0 ? sizeof(T) : cv_bytes()) * vecs_fine + (double)L.n_agg * (3 * cv_bytes() + 4);
     }
-    const char* vname() const { return cv_bytes() == 8 ? "double" : "float"; }      // the cycle vectors' type in the kernel names
 
     // ---- launches --------------------------------------------------------------------------------
     // damping of the current linearisation (rules = 1, graph_optimizer.py:24-43; 0 under the cpu/eigen rules) and the step the update takes
@@ -40,6 +46,8 @@
     // a graph with priors (edge types 3, 4) takes the PRI = 1 instantiations; one without launches exactly what it did before priors existed
     PriorArgs<T> pose_prior_args() const { return PriorArgs<T>{pri_p_off, pri_p, pri_lchi, tl.n_slices > 0 ? nbL : 0}; }
     PriorArgs<T> lm_prior_args() const { return PriorArgs<T>{pri_l_off, pri_l, pri_lchi, 0}; }
+    static PriorArgs<T> no_priors() { return PriorArgs<T>{nullptr, nullptr, nullptr, 0}; }
+    static GateArgs<T> no_gate() { return GateArgs<T>{nullptr, nullptr, nullptr, 0, T(0), nullptr, 0}; }
     void launch_lin() {
         launch_lin_lm();
         launch_lin_pose_only();
@@ -47,18 +55,16 @@
     void launch_lin_lm() {              // (tsgo_time_kernel too)
         const int zf = py_rules() ? 1 : 0;
         if (tl.n_slices == 0) return;
-        if (pr.has_priors) LAUNCH_GM(pr.by_lm.G, k_lin_lm, 1, nbL, stream, tl, ps, lmrec, gauge_l, ninv, (T)lambda, zf, lm_prior_args());
-        else LAUNCH_G(pr.by_lm.G, k_lin_lm, nbL, stream, tl, ps, lmrec, gauge_l, ninv, (T)lambda, zf);
+        pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(pr.has_priors, [&](auto pri) {
+            launch(k_lin_lm<T, g, pri>, nbL, tl, ps, lmrec, gauge_l, ninv, (T)lambda, zf, pri ? lm_prior_args() : no_priors());
+        }); });
     }
     void launch_lin_pose_only() {       // (tsgo_time_kernel too)
         const int zf = py_rules() ? 1 : 0;
-        if (pr.has_priors) {
-            if (oj()) LAUNCH_GML(pr.by_pose.G, k_lin_pose, 1, 1, nbP, stream, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf, odom_analytic_flag(), pose_prior_args());
-            else LAUNCH_GML(pr.by_pose.G, k_lin_pose, 0, 1, nbP, stream, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf, 0, pose_prior_args());
-            return;
-        }
-        if (oj()) LAUNCH_GM(pr.by_pose.G, k_lin_pose, 1, nbP, stream, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf, odom_analytic_flag());
-        else LAUNCH_G(pr.by_pose.G, k_lin_pose, nbP, stream, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf);
+        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) {
+            launch(k_lin_pose<T, g, general, pri>, nbP, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf,
+                   general ? odom_analytic_flag() : 0, pri ? pose_prior_args() : no_priors());
+        }); }); });
     }
     void launch_finalize() {
         hipLaunchKernelGGL((k_pose_finalize<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, part, ps, dp, minv, r, p, q, x, zc, gpart[0], st[0], (const T*)(amg_on ? omega_dev : one_dev), gscale_dev, amg_on && low_cycle ? zc32 : (float*)nullptr);
@@ -70,29 +76,38 @@
     // on every rank.  (r, z) partials are computed redundantly from replicated vectors and need no reduction.
     int launch_matvec(int slot, bool with_rz = false, bool low = false, const GateArgs<T>* gate = nullptr, bool post_smooth = false, bool as_residual = false) {
         const char* wh = low ? "in-cycle product" : (with_rz ? "PCG product" : "product");
-        const GateArgs<T> ga = gate ? *gate : GateArgs<T>{nullptr, nullptr, nullptr, 0, T(0), nullptr, 0};
-        if (low) {
-            PF(bytes_schur_lm(true) + (gate ? 2.0 * nbC * sizeof(T) : 0.0), gate ? "stopping rule + in-cycle product" : wh, "k_schur_lm<%s, %d, 0, 1>", tname(), pr.by_lm.G);
-            if (tl.n_slices > 0) LAUNCH_GML(pr.by_lm.G, k_schur_lm, 0, 1, nbL, stream, tl, zc, lmrec, (const T*)ninv, tvec, st[slot], T(0), dl, npart, (const float*)zc32, tvec32, ga);
-            PF(bytes_schur_pose(true) + (post_smooth ? pr.P * (6 + 3 + 3 + 3) * (double)sizeof(T) : 0.0), post_smooth ? "in-cycle product + post-smoothing L0" : wh, "k_schur_pose<%s, %d, 1, %d>", tname(), pr.by_pose.G, oj() ? 1 : 0);
-            const T* pm_ = post_smooth ? (const T*)minv : (const T*)nullptr;      // the level-0 post-smoothing in this pass's epilogue (k_schur_pose)
-            const T* pr_ = (post_smooth || as_residual) ? (const T*)r : (const T*)nullptr;      // ... or sbuf = r - S z (as_residual: the cycle's first product)
-            if (oj()) LAUNCH_GML(pr.by_pose.G, k_schur_pose, 1, 1, nbP, stream, tp, to, zc, tvec, dp, pr.pose_first, pr.pose_last, sbuf, sbuf + (size_t)pr.P * 3, st[slot],
-                                 (const T*)nullptr, rzpart, (const float*)zc32, (const float*)tvec32, pm_, pr_, (const T*)omega_dev, zc);
-            else LAUNCH_GML1(pr.by_pose.G, k_schur_pose, 1, nbP, stream, tp, to, zc, tvec, dp, pr.pose_first, pr.pose_last, sbuf, sbuf + (size_t)pr.P * 3, st[slot],
-                             (const T*)nullptr, rzpart, (const float*)zc32, (const float*)tvec32, pm_, pr_, (const T*)omega_dev, zc);
-        } else {
-            PF(bytes_schur_lm(false), wh, "k_schur_lm<%s, %d, 0, 0>", tname(), pr.by_lm.G);
-            if (tl.n_slices > 0) LAUNCH_GM(pr.by_lm.G, k_schur_lm, 0, nbL, stream, tl, zc, lmrec, (const T*)ninv, tvec, st[slot], T(0), dl, npart);
-            PF(bytes_schur_pose(false), wh, "k_schur_pose<%s, %d, 0, %d>", tname(), pr.by_pose.G, oj() ? 1 : 0);
-            if (oj()) LAUNCH_GML(pr.by_pose.G, k_schur_pose, 0, 1, nbP, stream, tp, to, zc, tvec, dp, pr.pose_first, pr.pose_last, sbuf, sbuf + (size_t)pr.P * 3, st[slot],
-                                 (const T*)(with_rz ? r : nullptr), rzpart);
-            else LAUNCH_G(pr.by_pose.G, k_schur_pose, nbP, stream, tp, to, zc, tvec, dp, pr.pose_first, pr.pose_last, sbuf, sbuf + (size_t)pr.P * 3, st[slot],
-                          (const T*)(with_rz ? r : nullptr), rzpart);
-        }
+        launch_schur_lm(slot, low, low ? gate : nullptr, wh);
+        launch_schur_pose(slot, low, (const T*)(!low && with_rz ? r : nullptr), rzpart, low && post_smooth, low && as_residual, wh);
         return allreduce(sbuf, (size_t)pr.P * 3 + nbP);
     }
+    // the two passes of a product (tsgo_time_kernel too).  The f32 operands, the gate and the epilogue go with LOW = 1 alone
+    void launch_schur_lm(int slot, bool low, const GateArgs<T>* gate, const char* wh) {
+        pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(low, [&](auto lo) {
+            PF(bytes_schur_lm(lo) + (gate ? 2.0 * nbC * sizeof(T) : 0.0), gate ? "stopping rule + in-cycle product" : wh, "k_schur_lm", tname(), g, 0, lo);
+            if (tl.n_slices > 0) launch(k_schur_lm<T, g, 0, lo>, nbL, tl, zc, lmrec, (const T*)ninv, tvec, st[slot], T(0), dl, npart,
+                                        lo ? (const float*)zc32 : nullptr, lo ? tvec32 : nullptr, lo && gate ? *gate : no_gate());
+        }); });
+    }
+    void launch_schur_pose(int slot, bool low, const T* rvec, T* rz_part, bool post_smooth, bool as_residual, const char* wh) {
+        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(low, [&](auto lo) { pick<0, 1>(oj(), [&](auto general) {
+            PF(bytes_schur_pose(lo) + (post_smooth ? pr.P * (6 + 3 + 3 + 3) * (double)sizeof(T) : 0.0), post_smooth ? "in-cycle product + post-smoothing L0" : wh, "k_schur_pose", tname(), g, lo, general);
+            const T* pm_ = post_smooth ? (const T*)minv : (const T*)nullptr;      // the level-0 post-smoothing in this pass's epilogue (k_schur_pose)
+            const T* pr_ = (post_smooth || as_residual) ? (const T*)r : (const T*)nullptr;      // ... or sbuf = r - S z (as_residual: the cycle's first product)
+            launch(k_schur_pose<T, g, lo, general>, nbP, tp, to, zc, tvec, dp, pr.pose_first, pr.pose_last, sbuf, sbuf + (size_t)pr.P * 3, st[slot], rvec, rz_part,
+                   lo ? (const float*)zc32 : nullptr, lo ? (const float*)tvec32 : nullptr, pm_, pr_, lo ? (const T*)omega_dev : nullptr, lo ? zc : nullptr);
+        }); }); });
+    }
     static int grid_for(int n, int per_thread_lanes = 1) { return std::max(1, (int)(((size_t)n * per_thread_lanes + kBlock - 1) / kBlock)); }
+
+    // One Galerkin product from its pair lists (TRANS 0: T = A P; 1: A_next = P^T T, upper blocks): a lane per output block, or 8 / 16 / 64 lanes
+    // sharing one where the average list is long
+    template <int TRANS> void launch_pair_gemm(double avg_pairs, int n_out, const int* ptr, const int* px, const int* py, const H* X, const H* Y, H* out, const int* upper) {
+        if (avg_pairs > kMediumPairList)
+            pick<8, 16, 64>(avg_pairs > kVeryLongPairList ? 64 : (avg_pairs > kLongPairList ? 16 : 8), [&](auto lpb) {
+                launch(k_pair_gemm_wave<T, TRANS, lpb>, grid_for(n_out, lpb), n_out, ptr, px, py, X, Y, out, upper);
+            });
+        else launch(k_pair_gemm<T, TRANS>, grid_for((n_out + kPairBlocksPerWave - 1) / kPairBlocksPerWave, 64), n_out, ptr, px, py, X, Y, out, upper);
+    }
 
     // numeric multigrid setup for the current linearisation (after lin + finalize)
     int launch_amg_setup() {
@@ -105,30 +120,23 @@
                            sc_optr, sc_os, tp, (const T*)to.dyn, to.slots, (const T*)lmrec, (const T*)ps, (const T*)part, L0.A, pr.rank == 0 ? 1 : 0,
                            to.idx, oj() ? 1 : 0, (const int*)(n_upper0 >= 0 ? upper0 : nullptr), (const int*)(n_upper0 >= 0 ? lower0 : nullptr), (T)hier_shift);
         if (int rc = allreduce_h(L0.A, (size_t)L0.nnzA * 9)) return rc;
-        if (explicit0) do { if (cy16) hipLaunchKernelGGL((k_to_planes<T, 1>), dim3(grid_for(L0.n, 8)), dim3(kBlock), 0, stream, L0.n, (const int*)L0.A_ptr, (const H*)L0.A, L0.Apm); else hipLaunchKernelGGL((k_to_planes<T, 0>), dim3(grid_for(L0.n, 8)), dim3(kBlock), 0, stream, L0.n, (const int*)L0.A_ptr, (const H*)L0.A, L0.Apm); } while (0);
+        if (explicit0) pick<0, 1>(cy16, [&](auto pk) { launch(k_to_planes<T, pk>, grid_for(L0.n, 8), L0.n, (const int*)L0.A_ptr, (const H*)L0.A, L0.Apm); });
         for (size_t l = 0; l < lv.size(); ++l) {
             DevLevel<T>& L = lv[l];
             H* Anext = l + 1 < lv.size() ? lv[l + 1].A : A_last;
             hipLaunchKernelGGL((k_block_inv<T>), dim3(grid_for(L.n)), dim3(kBlock), 0, stream, L.n, L.diag, (const H*)L.A, L.Dinv);
-            if (cy16) hipLaunchKernelGGL((k_prolongator<T, 1>), dim3(grid_for(L.nnzP)), dim3(kBlock), 0, stream, L.nnzP, L.P_row, L.p_self, L.ps_ptr, L.ps_x, L.ps_y,
-                               (const H*)L.A, (const H*)L.Dinv, (const T*)L.rel, (T)kProlongOmega, L.P, L.p_to_r, L.Rv, (const int*)L.P_ptr, (const int*)L.P_col, (const int*)L.R_ptr, L.Ppm, L.Rpm);
-            else hipLaunchKernelGGL((k_prolongator<T, 0>), dim3(grid_for(L.nnzP)), dim3(kBlock), 0, stream, L.nnzP, L.P_row, L.p_self, L.ps_ptr, L.ps_x, L.ps_y,
-                               (const H*)L.A, (const H*)L.Dinv, (const T*)L.rel, (T)kProlongOmega, L.P, L.p_to_r, L.Rv, (const int*)L.P_ptr, (const int*)L.P_col, (const int*)L.R_ptr, L.Ppm, L.Rpm);
-            if (L.pairs_T > kVeryLongPairList) hipLaunchKernelGGL((k_pair_gemm_wave<T, 0, 64>), dim3(grid_for(L.nnzT, 64)), dim3(kBlock), 0, stream, L.nnzT, L.ts_ptr, L.ts_x, L.ts_y, (const H*)L.A, (const H*)L.P, L.Tv, (const int*)nullptr);
-            else if (L.pairs_T > kLongPairList) hipLaunchKernelGGL((k_pair_gemm_wave<T, 0, 16>), dim3(grid_for(L.nnzT, 16)), dim3(kBlock), 0, stream, L.nnzT, L.ts_ptr, L.ts_x, L.ts_y, (const H*)L.A, (const H*)L.P, L.Tv, (const int*)nullptr);
-            else if (L.pairs_T > kMediumPairList) hipLaunchKernelGGL((k_pair_gemm_wave<T, 0, 8>), dim3(grid_for(L.nnzT, 8)), dim3(kBlock), 0, stream, L.nnzT, L.ts_ptr, L.ts_x, L.ts_y, (const H*)L.A, (const H*)L.P, L.Tv, (const int*)nullptr);
-            else hipLaunchKernelGGL((k_pair_gemm<T, 0>), dim3(grid_for((L.nnzT + kPairBlocksPerWave - 1) / kPairBlocksPerWave, 64)), dim3(kBlock), 0, stream, L.nnzT, L.ts_ptr, L.ts_x, L.ts_y, (const H*)L.A, (const H*)L.P, L.Tv, (const int*)nullptr);
-            if (L.pairs_A > kVeryLongPairList) hipLaunchKernelGGL((k_pair_gemm_wave<T, 1, 64>), dim3(grid_for(L.n_upper, 64)), dim3(kBlock), 0, stream, L.n_upper, L.as_ptr, L.as_x, L.as_y, (const H*)L.P, (const H*)L.Tv, Anext, (const int*)L.as_upper);
-            else if (L.pairs_A > kLongPairList) hipLaunchKernelGGL((k_pair_gemm_wave<T, 1, 16>), dim3(grid_for(L.n_upper, 16)), dim3(kBlock), 0, stream, L.n_upper, L.as_ptr, L.as_x, L.as_y, (const H*)L.P, (const H*)L.Tv, Anext, (const int*)L.as_upper);
-            else if (L.pairs_A > kMediumPairList) hipLaunchKernelGGL((k_pair_gemm_wave<T, 1, 8>), dim3(grid_for(L.n_upper, 8)), dim3(kBlock), 0, stream, L.n_upper, L.as_ptr, L.as_x, L.as_y, (const H*)L.P, (const H*)L.Tv, Anext, (const int*)L.as_upper);
-            else hipLaunchKernelGGL((k_pair_gemm<T, 1>), dim3(grid_for((L.n_upper + kPairBlocksPerWave - 1) / kPairBlocksPerWave, 64)), dim3(kBlock), 0, stream, L.n_upper, L.as_ptr, L.as_x, L.as_y, (const H*)L.P, (const H*)L.Tv, Anext, (const int*)L.as_upper);
+            pick<0, 1>(cy16, [&](auto pk) {
+                launch(k_prolongator<T, pk>, grid_for(L.nnzP), L.nnzP, L.P_row, L.p_self, L.ps_ptr, L.ps_x, L.ps_y, (const H*)L.A, (const H*)L.Dinv, (const T*)L.rel, (T)kProlongOmega, L.P,
+                       L.p_to_r, L.Rv, (const int*)L.P_ptr, (const int*)L.P_col, (const int*)L.R_ptr, L.Ppm, L.Rpm);
+            });
+            launch_pair_gemm<0>(L.pairs_T, L.nnzT, L.ts_ptr, L.ts_x, L.ts_y, (const H*)L.A, (const H*)L.P, L.Tv, (const int*)nullptr);
+            launch_pair_gemm<1>(L.pairs_A, L.n_upper, L.as_ptr, L.as_x, L.as_y, (const H*)L.P, (const H*)L.Tv, Anext, (const int*)L.as_upper);
             {   // the mirrored blocks of the next level's matrix and, in the same pass, its cycle-format copy (the last one, the dense level's, has none)
                 const bool packed_next = l + 1 < lv.size();
                 const int* rows_next = packed_next ? (const int*)lv[l + 1].A_row : (const int*)nullptr;
                 const int* ptr_next = packed_next ? (const int*)lv[l + 1].A_ptr : (const int*)nullptr;
                 uint32_t* pm_next = packed_next ? lv[l + 1].Apm : (uint32_t*)nullptr;
-                if (cy16) hipLaunchKernelGGL((k_mirror_pack<T, 1>), dim3(grid_for(L.nnzNext)), dim3(kBlock), 0, stream, L.nnzNext, (const int*)L.as_mirror, Anext, rows_next, ptr_next, pm_next);
-                else hipLaunchKernelGGL((k_mirror_pack<T, 0>), dim3(grid_for(L.nnzNext)), dim3(kBlock), 0, stream, L.nnzNext, (const int*)L.as_mirror, Anext, rows_next, ptr_next, pm_next);
+                pick<0, 1>(cy16, [&](auto pk) { launch(k_mirror_pack<T, pk>, grid_for(L.nnzNext), L.nnzNext, (const int*)L.as_mirror, Anext, rows_next, ptr_next, pm_next); });
             }
         }
         hipLaunchKernelGGL((k_dense_inverse<T>), dim3(1), dim3(kDenseThreads), 0, stream, nb_last, last_ptr, last_col, (const H*)A_last, inv_last);
@@ -155,40 +163,37 @@
         *xcd = (lpr_xcd && g >= kXcdMinBlocks) ? 1 : 0;
         return *xcd ? 8 * ((g + 7) / 8) : g;
     }
-#define LAUNCH_LPR_(LPR, INST, n_rows, ...)                                                                              \
-    do {                                                                                                                 \
-        int xcd_ = 0;                                                                                                    \
-        switch (LPR) {                                                                                                   \
-            case 4: { const int g_ = lpr_grid(n_rows, 4, &xcd_); hipLaunchKernelGGL((INST(4)), dim3(g_), dim3(kBlock), 0, stream, __VA_ARGS__, xcd_); } break;   \
-            case 8: { const int g_ = lpr_grid(n_rows, 8, &xcd_); hipLaunchKernelGGL((INST(8)), dim3(g_), dim3(kBlock), 0, stream, __VA_ARGS__, xcd_); } break;   \
-            case 16: { const int g_ = lpr_grid(n_rows, 16, &xcd_); hipLaunchKernelGGL((INST(16)), dim3(g_), dim3(kBlock), 0, stream, __VA_ARGS__, xcd_); } break; \
-            case 32: { const int g_ = lpr_grid(n_rows, 32, &xcd_); hipLaunchKernelGGL((INST(32)), dim3(g_), dim3(kBlock), 0, stream, __VA_ARGS__, xcd_); } break; \
-            default: { const int g_ = lpr_grid(n_rows, 64, &xcd_); hipLaunchKernelGGL((INST(64)), dim3(g_), dim3(kBlock), 0, stream, __VA_ARGS__, xcd_); } break; \
-        }                                                                                                                \
-    } while (0)
-    // a block-row sweep over the cycle-format copy of a level's matrix (MODE 0 residual, 1 smoothing sweep), f32 or packed half
-#define SWEEP_INST16(L_) k_bcsr_residual<T, L_, SWEEP_MODE, 1, 1, V>
-#define SWEEP_INST32(L_) k_bcsr_residual<T, L_, SWEEP_MODE, 1, 0, V>
-#define RESTRICT_INST16(L_) k_restrict<T, L_, SWEEP_MODE, 1, VI, VO>
-#define RESTRICT_INST32(L_) k_restrict<T, L_, SWEEP_MODE, 0, VI, VO>
-#define PROLONG_INST16(L_) k_prolong_add<T, L_, 1, VE, VZ>
-#define PROLONG_INST32(L_) k_prolong_add<T, L_, 0, VE, VZ>
-#define APPLY_INST16(L_) k_bcsr_apply<T, L_, 1>
-#define APPLY_INST32(L_) k_bcsr_apply<T, L_, 0>
-    template <int SWEEP_MODE, typename V> void launch_sweep(int lpr, DevLevel<T>& L, const V* rhs, const V* cur, V* out, const T* omega, const CgState<T>* s) {
-        if (cy16) LAUNCH_LPR_(lpr, SWEEP_INST16, L.n, L.n, L.A_ptr, L.A_col, (const void*)L.Apm, rhs, cur, (const H*)L.Dinv, out, omega, s);
-        else LAUNCH_LPR_(lpr, SWEEP_INST32, L.n, L.n, L.A_ptr, L.A_col, (const void*)L.Apm, rhs, cur, (const H*)L.Dinv, out, omega, s);
+    // A block-row kernel with `lpr` lanes per row over the cycle-format copies: f(LPR, PK, grid, xcd), PK = packed half (1) or f32 (0) blocks
+    template <typename F> void pick_block_row(int lpr, int n_rows, F&& f) {
+        pick<4, 8, 16, 32, 64>(lpr, [&](auto lanes) { pick<0, 1>(cy16, [&](auto pk) {
+            int xcd = 0;
+            const int grid = lpr_grid(n_rows, lanes, &xcd);
+            f(lanes, pk, grid, xcd);
+        }); });
     }
-    template <int SWEEP_MODE, typename VI, typename VO> void launch_restrict(int lpr, DevLevel<T>& L, const VI* va, const VI* vb, VO* rc, const H* dinv_next, VO* z_next, const T* omega, const CgState<T>* s) {
-        if (cy16) LAUNCH_LPR_(lpr, RESTRICT_INST16, L.n_agg, L.n_agg, L.R_ptr, L.R_col, (const uint32_t*)L.Rpm, va, vb, rc, dinv_next, z_next, omega, s);
-        else LAUNCH_LPR_(lpr, RESTRICT_INST32, L.n_agg, L.n_agg, L.R_ptr, L.R_col, (const uint32_t*)L.Rpm, va, vb, rc, dinv_next, z_next, omega, s);
+    // a block-row sweep over the cycle-format copy of a level's matrix (MODE 0 residual, 1 smoothing sweep); role: the profiler's label
+    template <int MODE, typename V> void launch_sweep(const char* role, size_t level, int lpr, const V* rhs, const V* cur, V* out, const T* omega, const CgState<T>* s) {
+        DevLevel<T>& L = lv[level];
+        pick_block_row(lpr, L.n, [&](auto lanes, auto pk, int grid, int xcd) {
+            PF(bytes_sweep(L), lvl(role, level).c_str(), "k_bcsr_residual", tname(), lanes, MODE, 1, pk, tname_of<V>());
+            launch(k_bcsr_residual<T, lanes, MODE, 1, pk, V>, grid, L.n, L.A_ptr, L.A_col, (const void*)L.Apm, rhs, cur, (const H*)L.Dinv, out, omega, s, xcd);
+        });
     }
-    template <typename VE, typename VZ> void launch_prolong(DevLevel<T>& L, const VE* e, VZ* z, int zs, const CgState<T>* s, size_t level) {
-        PF(bytes_transfer(L, 2, level == 0), lvl("prolong into", level).c_str(), "k_prolong_add<%s, %d, %d, %s, %s>", tname(), lanes_for((double)L.nnzP / std::max(1, L.n)), cy16 ? 1 : 0, vname(), level == 0 ? tname() : vname());
-        const int lpr = lanes_for((double)L.nnzP / std::max(1, L.n));
+    // restriction of level `level` (SUB 1: of va - vb, two fine vectors), with the first pre-sweep of the level below where dinv_next is given
+    template <int SUB, typename VI, typename VO> void launch_restrict(size_t level, int lpr, const VI* va, const VI* vb, VO* rc, const H* dinv_next, VO* z_next, const T* omega, const CgState<T>* s) {
+        DevLevel<T>& L = lv[level];
+        pick_block_row(lpr, L.n_agg, [&](auto lanes, auto pk, int grid, int xcd) {
+            PF(bytes_transfer(L, SUB ? 2 : 1, level == 0), lvl("restrict from", level).c_str(), "k_restrict", tname(), lanes, SUB, pk, tname_of<VI>(), tname_of<VO>());
+            launch(k_restrict<T, lanes, SUB, pk, VI, VO>, grid, L.n_agg, L.R_ptr, L.R_col, (const uint32_t*)L.Rpm, va, vb, rc, dinv_next, z_next, omega, s, xcd);
+        });
+    }
+    template <typename VE, typename VZ> void launch_prolong(size_t level, const VE* e, VZ* z, int zs, const CgState<T>* s) {
+        DevLevel<T>& L = lv[level];
         float* z32 = (level == 0 && low_cycle && !explicit0) ? zc32 : (float*)nullptr;      // level 0 prolongs into the pose records: keep their f32 copy current
-        if (cy16) LAUNCH_LPR_(lpr, PROLONG_INST16, L.n, L.n, L.P_ptr, L.P_col, (const uint32_t*)L.Ppm, e, z, zs, s, z32);
-        else LAUNCH_LPR_(lpr, PROLONG_INST32, L.n, L.n, L.P_ptr, L.P_col, (const uint32_t*)L.Ppm, e, z, zs, s, z32);
+        pick_block_row(lanes_for((double)L.nnzP / std::max(1, L.n)), L.n, [&](auto lanes, auto pk, int grid, int xcd) {
+            PF(bytes_transfer(L, 2, level == 0), lvl("prolong into", level).c_str(), "k_prolong_add", tname(), lanes, pk, tname_of<VE>(), tname_of<VZ>());
+            launch(k_prolong_add<T, lanes, pk, VE, VZ>, grid, L.n, L.P_ptr, L.P_col, (const uint32_t*)L.Ppm, e, z, zs, s, z32, xcd);
+        });
     }
 
     // Damping of the block-Jacobi smoother per level from a power iteration on D^-1 A (12 steps): the V-cycle
@@ -203,13 +208,9 @@
             hipLaunchKernelGGL((k_seed_vector<T>), dim3(grid_for(n3)), dim3(kBlock), 0, stream, n3, a);
             const int lprA = lanes_for((double)L.nnzA / std::max(1, L.n));
             for (int it = 0; it < kRhoSteps; ++it) {
-                switch (lprA) {     // the block-indexed matrix (PM = 0): level 0 has no cycle-format copy
-                    case 4: hipLaunchKernelGGL((k_bcsr_residual<T, 4, 2, 0>), dim3(grid_for(L.n, 4)), dim3(kBlock), 0, stream, L.n, L.A_ptr, L.A_col, (const void*)L.A, (const T*)a, (const T*)a, (const H*)L.Dinv, b, (const T*)omega_dev, (const CgState<T>*)st[0]); break;
-                    case 16: hipLaunchKernelGGL((k_bcsr_residual<T, 16, 2, 0>), dim3(grid_for(L.n, 16)), dim3(kBlock), 0, stream, L.n, L.A_ptr, L.A_col, (const void*)L.A, (const T*)a, (const T*)a, (const H*)L.Dinv, b, (const T*)omega_dev, (const CgState<T>*)st[0]); break;
-                    case 8: hipLaunchKernelGGL((k_bcsr_residual<T, 8, 2, 0>), dim3(grid_for(L.n, 8)), dim3(kBlock), 0, stream, L.n, L.A_ptr, L.A_col, (const void*)L.A, (const T*)a, (const T*)a, (const H*)L.Dinv, b, (const T*)omega_dev, (const CgState<T>*)st[0]); break;
-                    case 32: hipLaunchKernelGGL((k_bcsr_residual<T, 32, 2, 0>), dim3(grid_for(L.n, 32)), dim3(kBlock), 0, stream, L.n, L.A_ptr, L.A_col, (const void*)L.A, (const T*)a, (const T*)a, (const H*)L.Dinv, b, (const T*)omega_dev, (const CgState<T>*)st[0]); break;
-                    default: hipLaunchKernelGGL((k_bcsr_residual<T, 64, 2, 0>), dim3(grid_for(L.n, 64)), dim3(kBlock), 0, stream, L.n, L.A_ptr, L.A_col, (const void*)L.A, (const T*)a, (const T*)a, (const H*)L.Dinv, b, (const T*)omega_dev, (const CgState<T>*)st[0]); break;
-                }
+                pick<4, 8, 16, 32, 64>(lprA, [&](auto lanes) {     // the block-indexed matrix (PM = 0): level 0 has no cycle-format copy
+                    launch(k_bcsr_residual<T, lanes, 2, 0>, grid_for(L.n, lanes), L.n, L.A_ptr, L.A_col, (const void*)L.A, (const T*)a, (const T*)a, (const H*)L.Dinv, b, (const T*)omega_dev, (const CgState<T>*)st[0], 0);
+                });
                 std::swap(a, b);
             }
             // a = v_K, b = v_{K-1}
@@ -244,10 +245,10 @@
     int launch_cycle_product(int slot, const GateArgs<T>* gate = nullptr, bool post_smooth = false, bool as_residual = false) {
         if (!explicit0) return launch_matvec(slot, false, low_cycle, gate, post_smooth, as_residual);
         DevLevel<T>& L = lv[0];
-        PF(bytes_sweep(L), "in-cycle product (explicit)", "k_bcsr_apply<%s, %d, %d>", tname(), lanes_for_sweep((double)L.nnzA / std::max(1, L.n), L.n), cy16 ? 1 : 0);
-        const int lpr = lanes_for_sweep((double)L.nnzA / std::max(1, L.n), L.n);
-        if (cy16) LAUNCH_LPR_(lpr, APPLY_INST16, L.n, L.n, L.A_ptr, L.A_col, (const uint32_t*)L.Apm, (const T*)zc, kPoseRec, sbuf, (const CgState<T>*)st[slot]);
-        else LAUNCH_LPR_(lpr, APPLY_INST32, L.n, L.n, L.A_ptr, L.A_col, (const uint32_t*)L.Apm, (const T*)zc, kPoseRec, sbuf, (const CgState<T>*)st[slot]);
+        pick_block_row(lanes_for_sweep((double)L.nnzA / std::max(1, L.n), L.n), L.n, [&](auto lanes, auto pk, int grid, int xcd) {
+            PF(bytes_sweep(L), "in-cycle product (explicit)", "k_bcsr_apply", tname(), lanes, pk);
+            launch(k_bcsr_apply<T, lanes, pk>, grid, L.n, L.A_ptr, L.A_col, (const uint32_t*)L.Apm, (const T*)zc, kPoseRec, sbuf, (const CgState<T>*)st[slot], xcd);
+        });
         return 0;
     }
     // the cycle's vectors below level 0 are V (CV<T>; T under cyc64, testing builds only)
@@ -270,9 +271,8 @@
             DevLevel<T>& L = lv[0];
             const int lpr = lanes_for((double)L.nnzP / std::max(1, L.n_agg));
             const H* dnext = (bottom_dense && nl == 2) ? (const H*)nullptr : (nl > 1 ? (const H*)lv[1].Dinv : (const H*)nullptr);      // (nl == 3 with the factored level: lv[1] keeps its pre-sweep)
-            if (nl > 1) PF(bytes_transfer(L, res_fused ? 1 : 2, true), "restrict from L0", "k_restrict<%s, %d, %d, %d, %s, %s>", tname(), lpr, res_fused ? 0 : 1, cy16 ? 1 : 0, tname(), vname());
-            if (nl > 1 && res_fused) launch_restrict<0>(lpr, L, (const T*)sbuf, (const T*)sbuf, v(lv[1].r), dnext, v(lv[1].z), (const T*)(omega_dev + 1), s);
-            else if (nl > 1) launch_restrict<1>(lpr, L, (const T*)r, (const T*)sbuf, v(lv[1].r), dnext, v(lv[1].z), (const T*)(omega_dev + 1), s);
+            if (nl > 1 && res_fused) launch_restrict<0>(0, lpr, (const T*)sbuf, (const T*)sbuf, v(lv[1].r), dnext, v(lv[1].z), (const T*)(omega_dev + 1), s);
+            else if (nl > 1) launch_restrict<1>(0, lpr, (const T*)r, (const T*)sbuf, v(lv[1].r), dnext, v(lv[1].z), (const T*)(omega_dev + 1), s);
         }
         // coarse levels: V(nu,nu) with nu = coarse_sweeps block-Jacobi sweeps (the first pre-sweep comes fused
         // with the restriction above).  The current iterate alternates between L.z and L.z2; it ends in L.z2.
@@ -285,17 +285,14 @@
             const int lprA = lanes_for_sweep((double)L.nnzA / std::max(1, L.n), L.n);
             V* cur = v(L.z); V* oth = v(L.z2);
             for (int sw = 1; sw < nu; ++sw) {
-                PF(bytes_sweep(L), lvl("pre-sweep", l).c_str(), "k_bcsr_residual<%s, %d, 1, 1, %d, %s>", tname(), lprA, cy16 ? 1 : 0, vname());
-                launch_sweep<1>(lprA, L, cv(L.r), (const V*)cur, oth, (const T*)(omega_dev + l), s);
+                launch_sweep<1>("pre-sweep", l, lprA, cv(L.r), (const V*)cur, oth, (const T*)(omega_dev + l), s);
                 std::swap(cur, oth);
             }
-            PF(bytes_sweep(L), lvl("residual", l).c_str(), "k_bcsr_residual<%s, %d, 0, 1, %d, %s>", tname(), lprA, cy16 ? 1 : 0, vname());
-            launch_sweep<0>(lprA, L, cv(L.r), (const V*)cur, v(L.res), (const T*)(omega_dev + l), s);
+            launch_sweep<0>("residual", l, lprA, cv(L.r), (const V*)cur, v(L.res), (const T*)(omega_dev + l), s);
             if (l + 1 < nl) {
                 const int lpr = lanes_for((double)L.nnzP / std::max(1, L.n_agg));
                 const bool no_presmooth = dense_bottom && !dense_tail2 && l + 2 == nl;      // the dense bottom operator pre-smooths by itself (the factored level wants z1 = W r)
-                PF(bytes_transfer(L, 1), lvl("restrict from", l).c_str(), "k_restrict<%s, %d, 0, %d, %s, %s>", tname(), lpr, cy16 ? 1 : 0, vname(), vname());
-                launch_restrict<0>(lpr, L, cv(L.res), cv(L.res), v(lv[l + 1].r), no_presmooth ? (const H*)nullptr : (const H*)lv[l + 1].Dinv, v(lv[l + 1].z), (const T*)(omega_dev + l + 1), s);
+                launch_restrict<0>(l, lpr, cv(L.res), cv(L.res), v(lv[l + 1].r), no_presmooth ? (const H*)nullptr : (const H*)lv[l + 1].Dinv, v(lv[l + 1].z), (const T*)(omega_dev + l + 1), s);
             }
         }
         // iterate of level l after the down pass: L.z when nu is odd, L.z2 when even
@@ -304,34 +301,33 @@
         if (dense_tail2) {       // levels nl-2 and nl-1 at once: z2 = 2 z1 - W A z1 + G (E^T r), z1 = W r left by the restriction into nl-2
             DevLevel<T>& L = lv[nl - 2];
             const int n3 = L.n * 3, nd = lv[nl - 1].n * 3;
-            PF((double)n3 * nd * sizeof(float) + (double)(n3 + nd) * cv_bytes(), lvl("t = E^T r of", nl - 2).c_str(), "k_rowdot_wg<%s, %s>", tname(), vname());
+            PF((double)n3 * nd * sizeof(float) + (double)(n3 + nd) * cv_bytes(), lvl("t = E^T r of", nl - 2).c_str(), "k_rowdot_wg", tname(), tname_of<V>());
             hipLaunchKernelGGL((k_rowdot_wg<T, V>), dim3(nd), dim3(kBlock), 0, stream, nd, n3, (const float*)tail_Etf, cv(L.r), v(tail_t), s);
-            PF(bytes_sweep(L) + (double)n3 * nd * sizeof(float), lvl("cycles of", nl - 2).c_str(), "k_tail_up<%s, %d, %s>", tname(), cy16 ? 1 : 0, vname());
-            if (cy16) hipLaunchKernelGGL((k_tail_up<T, 1, V>), dim3(L.n), dim3(kBlock), 0, stream, L.n, (const int*)L.A_ptr, (const int*)L.A_col, (const uint32_t*)L.Apm, (const H*)L.Dinv, (const T*)(omega_dev + nl - 2), cv(L.z), nd, (const float*)tail_Gf, cv(tail_t), v(L.z2), s);
-            else hipLaunchKernelGGL((k_tail_up<T, 0, V>), dim3(L.n), dim3(kBlock), 0, stream, L.n, (const int*)L.A_ptr, (const int*)L.A_col, (const uint32_t*)L.Apm, (const H*)L.Dinv, (const T*)(omega_dev + nl - 2), cv(L.z), nd, (const float*)tail_Gf, cv(tail_t), v(L.z2), s);
+            pick<0, 1>(cy16, [&](auto pk) {
+                PF(bytes_sweep(L) + (double)n3 * nd * sizeof(float), lvl("cycles of", nl - 2).c_str(), "k_tail_up", tname(), pk, tname_of<V>());
+                launch(k_tail_up<T, pk, V>, L.n, L.n, (const int*)L.A_ptr, (const int*)L.A_col, (const uint32_t*)L.Apm, (const H*)L.Dinv, (const T*)(omega_dev + nl - 2), cv(L.z), nd, (const float*)tail_Gf, cv(tail_t), v(L.z2), s);
+            });
         } else if (dense_bottom) {      // z2 = B r: pre-sweep, coarse correction through the dense inverse and post-sweep of the last explicit level at once
             DevLevel<T>& L = lv[nl - 1];
             const int n3 = L.n * 3;
-            PF((double)n3 * n3 * sizeof(float) + 2.0 * n3 * cv_bytes(), lvl("whole cycle of", nl - 1).c_str(), "k_bottom_apply<%s, %s>", tname(), vname());
+            PF((double)n3 * n3 * sizeof(float) + 2.0 * n3 * cv_bytes(), lvl("whole cycle of", nl - 1).c_str(), "k_bottom_apply", tname(), tname_of<V>());
             hipLaunchKernelGGL((k_bottom_apply<T, V>), dim3(grid_for(n3, 64)), dim3(kBlock), 0, stream, n3, n3, (const float*)bot_Bf, cv(L.r), v(L.z2), s);
         } else if (nl > 1 && lv[nl - 1].n * 4 <= kDenseThreads) {   // bottom: restrict + dense inverse + prolong in one workgroup, on the last explicit level
             DevLevel<T>& L = lv[nl - 1];
-            PF(2.0 * L.nnzP * (9 * sizeof(H) + 4) + (double)nb_last * 3 * nb_last * 3 * sizeof(T) + L.n * 6.0 * cv_bytes(), lvl("restrict + dense solve + prolong", nl - 1).c_str(), "k_coarse_tail<%s, %s>", tname(), vname());
+            PF(2.0 * L.nnzP * (9 * sizeof(H) + 4) + (double)nb_last * 3 * nb_last * 3 * sizeof(T) + L.n * 6.0 * cv_bytes(), lvl("restrict + dense solve + prolong", nl - 1).c_str(), "k_coarse_tail", tname(), tname_of<V>());
             hipLaunchKernelGGL((k_coarse_tail<T, V>), dim3(1), dim3(kDenseThreads), 0, stream, L.n, L.n_agg, L.R_ptr, L.R_col, (const H*)L.Rv, L.P_ptr, L.P_col, (const H*)L.P,
                                cv(L.res), (const T*)inv_last, down_iter(L, nu_at(nl - 1)), s);
         } else if (nl > 1) {   // a last explicit level too long for the one-workgroup kernel (4 lanes per row): the same three steps as launches
             DevLevel<T>& L = lv[nl - 1];
-            PF(bytes_transfer(L, 1), lvl("restrict from", nl - 1).c_str(), "k_restrict<%s, 8, 0, %d, %s, %s>", tname(), cy16 ? 1 : 0, vname(), vname());
-            launch_restrict<0>(8, L, cv(L.res), cv(L.res), v(r_last), (const H*)nullptr, (V*)nullptr, (const T*)one_dev, s);
-            PF((double)nb_last * 3 * nb_last * 3 * sizeof(T), "dense solve", "k_dense_apply<%s, %s>", tname(), vname());
+            launch_restrict<0>(nl - 1, 8, cv(L.res), cv(L.res), v(r_last), (const H*)nullptr, (V*)nullptr, (const T*)one_dev, s);
+            PF((double)nb_last * 3 * nb_last * 3 * sizeof(T), "dense solve", "k_dense_apply", tname(), tname_of<V>());
             hipLaunchKernelGGL((k_dense_apply<T, V>), dim3(1), dim3(kBlock), 0, stream, nb_last * 3, (const T*)inv_last, cv(r_last), v(z_last), s);
-            launch_prolong(L, cv(z_last), down_iter(L, nu_at(nl - 1)), 3, s, nl - 1);
+            launch_prolong(nl - 1, cv(z_last), down_iter(L, nu_at(nl - 1)), 3, s);
         } else {        // only level 0 above the dense level: residual r - S z is restricted from (r, sbuf)
             DevLevel<T>& L = lv[0];
-            PF(bytes_transfer(L, res_fused ? 1 : 2, true), "restrict from L0", "k_restrict<%s, 8, %d, %d, %s, %s>", tname(), res_fused ? 0 : 1, cy16 ? 1 : 0, tname(), vname());
-            if (res_fused) launch_restrict<0>(8, L, (const T*)sbuf, (const T*)sbuf, v(r_last), (const H*)nullptr, (V*)nullptr, (const T*)one_dev, s);
-            else launch_restrict<1>(8, L, (const T*)r, (const T*)sbuf, v(r_last), (const H*)nullptr, (V*)nullptr, (const T*)one_dev, s);
-            PF((double)nb_last * 3 * nb_last * 3 * sizeof(T), "dense solve", "k_dense_apply<%s, %s>", tname(), vname());
+            if (res_fused) launch_restrict<0>(0, 8, (const T*)sbuf, (const T*)sbuf, v(r_last), (const H*)nullptr, (V*)nullptr, (const T*)one_dev, s);
+            else launch_restrict<1>(0, 8, (const T*)r, (const T*)sbuf, v(r_last), (const H*)nullptr, (V*)nullptr, (const T*)one_dev, s);
+            PF((double)nb_last * 3 * nb_last * 3 * sizeof(T), "dense solve", "k_dense_apply", tname(), tname_of<V>());
             hipLaunchKernelGGL((k_dense_apply<T, V>), dim3(1), dim3(kBlock), 0, stream, nb_last * 3, (const T*)inv_last, cv(r_last), v(z_last), s);
         }
         for (size_t l = nl - 1; l >= 1; --l) {
@@ -339,22 +335,21 @@
             if (l >= first_dense) continue;      // a dense level's result is in its z2 already
             const int nu = nu_at(l);
             V* cur = down_iter(L, nu); V* oth = down_other(L, nu);
-            if (l + 1 < nl) launch_prolong(L, cv(lv[l + 1].z2), cur, 3, s, l);
+            if (l + 1 < nl) launch_prolong(l, cv(lv[l + 1].z2), cur, 3, s);
             const int lprA = lanes_for_sweep((double)L.nnzA / std::max(1, L.n), L.n);
             for (int sw = 0; sw < nu; ++sw) {
-                PF(bytes_sweep(L), lvl("post-sweep", l).c_str(), "k_bcsr_residual<%s, %d, 1, 1, %d, %s>", tname(), lprA, cy16 ? 1 : 0, vname());
-                launch_sweep<1>(lprA, L, cv(L.r), (const V*)cur, oth, (const T*)(omega_dev + l), s);
+                launch_sweep<1>("post-sweep", l, lprA, cv(L.r), (const V*)cur, oth, (const T*)(omega_dev + l), s);
                 std::swap(cur, oth);
             }
             // nu post-sweeps after nu-1 pre-swaps: the result sits in L.z2 for every nu (odd+odd / even+even swaps)
         }
-        launch_prolong(lv[0], nl > 1 ? cv(lv[1].z2) : cv(z_last), zc, kPoseRec, s, 0);
+        launch_prolong(0, nl > 1 ? cv(lv[1].z2) : cv(z_last), zc, kPoseRec, s);
         // level-0 post-smoothing zc += omega Minv (r - S zc): in the epilogue of the product's pose pass where that pass reads f32 copies and its
         // result needs no all-reduce (one shard), else a launch of its own
         const bool fuse_post = fuse_post_smooth && !explicit0 && low_cycle && !collective();
         if (int rc = launch_cycle_product(slot, nullptr, fuse_post)) return rc;
         if (!fuse_post) {
-            PF(pr.P * (6 + 3 + 3 + 3 + 3) * (double)sizeof(T), "post-smoothing L0", "k_smooth0<%s, 1>", tname());
+            PF(pr.P * (6 + 3 + 3 + 3 + 3) * (double)sizeof(T), "post-smoothing L0", "k_smooth0", tname(), 1);
             hipLaunchKernelGGL((k_smooth0<T, 1>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, (const T*)minv, (const T*)r, (const T*)sbuf, zc, (const T*)omega_dev, s);
         }
         return 0;
@@ -363,11 +358,11 @@
         const T tol2 = (T)(cfg.pcg_rel_tol * cfg.pcg_rel_tol);
         const T* dots = sbuf + (size_t)pr.P * 3; const T* rzs = rzpart; int n_part = nbP;
         if (nbP > kFoldAbove) {       // a million poses: fold the partials once instead of in every workgroup of k_cg_step
-            PF(2.0 * nbP * sizeof(T), "partials of the two dot products folded", "k_fold_partials<%s>", tname());
+            PF(2.0 * nbP * sizeof(T), "partials of the two dot products folded", "k_fold_partials", tname());
             hipLaunchKernelGGL((k_fold_partials<T>), dim3(kFoldOut, 2), dim3(kBlock), 0, stream, nbP, dots, rzs, fold_part);
             dots = fold_part; rzs = fold_part + kFoldOut; n_part = kFoldOut;
         }
-        PF(pr.P * (3 + 3 + 6 + 4 * 3 * 2) * (double)sizeof(T), "vector step + pre-smoothing L0", "k_cg_step<%s>", tname());
+        PF(pr.P * (3 + 3 + 6 + 4 * 3 * 2) * (double)sizeof(T), "vector step + pre-smoothing L0", "k_cg_step", tname());
         hipLaunchKernelGGL((k_cg_step<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, (const T*)sbuf, dots, rzs, n_part,
                            (const CgState<T>*)st[slot], st[slot ^ 1], r, p, q, x, zc, (const T*)minv, (const T*)omega_dev, tol2, cfg.pcg_max_iters, (const T*)gscale_dev, kAmgStallIter, (T)kAmgStallRatio,
                            npart, low_cycle && !explicit0 ? zc32 : (float*)nullptr);
@@ -380,7 +375,7 @@
             const GateArgs<T> ga{st[slot], (const T*)npart, (const T*)gpart[0], nbC, (T)(cfg.pcg_rel_tol * cfg.pcg_rel_tol), seq > 0 ? h_flag : (int*)nullptr, seq};
             const bool fold = fold_gate && !explicit0 && low_cycle && tl.n_slices > 0;
             if (!fold) {
-                PF(2.0 * nbC * sizeof(T), "stopping rule", "k_iter_gate<%s>", tname());
+                PF(2.0 * nbC * sizeof(T), "stopping rule", "k_iter_gate", tname());
                 hipLaunchKernelGGL((k_iter_gate<T>), dim3(1), dim3(kBlock), 0, stream, ga.st, ga.rdr_part, ga.bpart, ga.n, ga.tol2, ga.host_flag, ga.seq);
             }
             if (int rc = launch_vcycle(slot, fold ? &ga : nullptr)) return rc;
@@ -397,7 +392,7 @@
     }
     void launch_cg_update(int slot) {
         const T tol2 = (T)(cfg.pcg_rel_tol * cfg.pcg_rel_tol);
-        PF(pr.P * (3 + 3 + 6 + 4 * 3 * 2) * (double)sizeof(T), "vector step", "k_cg_update<%s>", tname());
+        PF(pr.P * (3 + 3 + 6 + 4 * 3 * 2) * (double)sizeof(T), "vector step", "k_cg_update", tname());
         hipLaunchKernelGGL((k_cg_update<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, sbuf, sbuf + (size_t)pr.P * 3, nbP, gpart[slot], nbC,
                            gpart[slot ^ 1], st[slot], st[slot ^ 1], minv, r, p, q, x, zc, tol2, cfg.pcg_max_iters, (const T*)gscale_dev);
     }

@@ -32,26 +32,14 @@
     // ---- launches ----
     template <int NV> void mb_lm(const T* v, T* t, const int* stop) {
         if (tl.n_slices == 0) return;
-        switch (pr.by_lm.G) {
-            case 1: hipLaunchKernelGGL((k_mb_schur_lm<T, 1, NV>), dim3(nbL), dim3(kBlock), 0, stream, tl, v, (const T*)ps, (const T*)ninv, t, stop); break;
-            case 2: hipLaunchKernelGGL((k_mb_schur_lm<T, 2, NV>), dim3(nbL), dim3(kBlock), 0, stream, tl, v, (const T*)ps, (const T*)ninv, t, stop); break;
-            case 4: hipLaunchKernelGGL((k_mb_schur_lm<T, 4, NV>), dim3(nbL), dim3(kBlock), 0, stream, tl, v, (const T*)ps, (const T*)ninv, t, stop); break;
-            default: hipLaunchKernelGGL((k_mb_schur_lm<T, 8, NV>), dim3(nbL), dim3(kBlock), 0, stream, tl, v, (const T*)ps, (const T*)ninv, t, stop); break;
-        }
-    }
-    template <int NV, int MODE, int OJ> void mb_pose_oj(const T* v, const T* t, T* out, const T* rvec, T* dpart, const int* stop) {
-        switch (pr.by_pose.G) {
-            case 1: hipLaunchKernelGGL((k_mb_schur_pose<T, 1, OJ, NV, MODE>), dim3(nbP), dim3(kBlock), 0, stream, tp, to, v, t, (const T*)ps, (const T*)dp, out, rvec, dpart, stop); break;
-            case 2: hipLaunchKernelGGL((k_mb_schur_pose<T, 2, OJ, NV, MODE>), dim3(nbP), dim3(kBlock), 0, stream, tp, to, v, t, (const T*)ps, (const T*)dp, out, rvec, dpart, stop); break;
-            case 4: hipLaunchKernelGGL((k_mb_schur_pose<T, 4, OJ, NV, MODE>), dim3(nbP), dim3(kBlock), 0, stream, tp, to, v, t, (const T*)ps, (const T*)dp, out, rvec, dpart, stop); break;
-            default: hipLaunchKernelGGL((k_mb_schur_pose<T, 8, OJ, NV, MODE>), dim3(nbP), dim3(kBlock), 0, stream, tp, to, v, t, (const T*)ps, (const T*)dp, out, rvec, dpart, stop); break;
-        }
+        pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { launch(k_mb_schur_lm<T, g, NV>, nbL, tl, v, (const T*)ps, (const T*)ninv, t, stop); });
     }
     // S v (MODE 0: + partials of v^T S v; 2: without) or rvec - S v (MODE 1), all NV columns
     template <int NV, int MODE> void mb_product(MbBuf& B, const T* v, T* out, const T* rvec, const int* stop) {
         mb_lm<NV>(v, B.t, stop);
-        if (oj()) mb_pose_oj<NV, MODE, 1>(v, B.t, out, rvec, B.dpart, stop);
-        else mb_pose_oj<NV, MODE, 0>(v, B.t, out, rvec, B.dpart, stop);
+        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) {
+            launch(k_mb_schur_pose<T, g, general, NV, MODE>, nbP, tp, to, v, B.t, (const T*)ps, (const T*)dp, out, rvec, B.dpart, stop);
+        }); });
     }
     template <int NV, int MODE> void mb_bsr(int n, const int* ptr, const int* col, const H* M, const T* x, const T* b, const H* dinv, const T* omega, T* out, const int* stop) {
         hipLaunchKernelGGL((k_mb_bsr<T, NV, MODE>), dim3(grid_for(n * NV)), dim3(kBlock), 0, stream, n, ptr, col, M, x, b, dinv, omega, out, stop);
@@ -288,11 +276,7 @@
     // the whole call between the snapshot and the restore
     int mb_compute(const std::vector<MbQuery>& qs, double tol, double* cov, tsgo_marginal_stats& s) {
         if (int rc = mb_prepare()) return rc;
-        switch (marginal_width()) {
-            case 1: return mb_run<1>(qs, tol, cov, s);
-            case 16: return mb_run<16>(qs, tol, cov, s);
-            default: return mb_run<8>(qs, tol, cov, s);
-        }
+        return pick<1, 16, 8>(marginal_width(), [&](auto nv) { return mb_run<nv>(qs, tol, cov, s); });
     }
 
     // The shell both entry points share.  mb_queries: the handle's checks and the id -> (pose | landmark, index) map (`name` prefixes
@@ -435,11 +419,7 @@
         const int Di = (int)D;
         const int rc = mb_guarded([&]() -> int {
             if (int r = mb_prepare()) return r;
-            switch (marginal_width()) {
-                case 1: return mb_run_joint<1>(qs, Di, tol, cov, s);
-                case 16: return mb_run_joint<16>(qs, Di, tol, cov, s);
-                default: return mb_run_joint<8>(qs, Di, tol, cov, s);
-            }
+            return pick<1, 16, 8>(marginal_width(), [&](auto nv) { return mb_run_joint<nv>(qs, Di, tol, cov, s); });
         });
         if (rc) return rc;
         s.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();

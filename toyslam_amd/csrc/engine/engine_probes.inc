@@ -1,11 +1,12 @@
 // engine/engine_probes.inc — part of `template <typename T> struct Engine` (tsgo_hip.hip includes it INSIDE the class body):
 // timing probes behind tsgo_cycle_probe / tsgo_profile_iteration / tsgo_time_kernel.
-    void probe_sweep(int lprA, DevLevel<T>& L, const T* omega) {      // one smoothing sweep on the level's own vectors, in their type
+    void probe_sweep(int lprA, size_t level, const T* omega) {      // one smoothing sweep on the level's own vectors, in their type
         const CgState<T>* s0 = st[0];
+        DevLevel<T>& L = lv[level];
 #ifdef TSGO_TESTING
-        if (cyc64) { launch_sweep<1>(lprA, L, (const T*)L.r, (const T*)L.z, (T*)L.z2, omega, s0); return; }
+        if (cyc64) { launch_sweep<1>("", level, lprA, (const T*)L.r, (const T*)L.z, (T*)L.z2, omega, s0); return; }
 #endif
-        launch_sweep<1>(lprA, L, (const CV<T>*)L.r, (const CV<T>*)L.z, (CV<T>*)L.z2, omega, s0);
+        launch_sweep<1>("", level, lprA, (const CV<T>*)L.r, (const CV<T>*)L.z, (CV<T>*)L.z2, omega, s0);
     }
     int cycle_probe(int reps, tsgo_cycle_level* out, int cap) override {
         if (!have_graph_data) return set_error(-3, "tsgo_cycle_probe: no graph set");
@@ -21,7 +22,7 @@
                 const int m = pass == 0 ? 3 : reps;
                 HIP_OK(hipEventRecord(ev[0], stream));
                 for (int k = 0; k < m; ++k)
-                    probe_sweep(lprA, L, (const T*)(omega_dev + l));
+                    probe_sweep(lprA, l, (const T*)(omega_dev + l));
                 HIP_OK(hipEventRecord(ev[1], stream));
                 HIP_OK(hipEventSynchronize(ev[1]));
                 if (pass == 1) { float ms = 0; HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1])); out[n].us_per_sweep = 1e3 * ms / m; }
@@ -99,10 +100,8 @@
             HIP_OK(hipEventRecord(ev[0], stream));
             for (int k = 0; k < n; ++k) {
                 switch (which) {
-                    case 0: if (tl.n_slices > 0) LAUNCH_GM(pr.by_lm.G, k_schur_lm, 0, nbL, stream, tl, zc, lmrec, (const T*)ninv, tvec, st[0], T(0), dl, npart); break;
-                    case 1: if (oj()) LAUNCH_GML(pr.by_pose.G, k_schur_pose, 0, 1, nbP, stream, tp, to, zc, tvec, dp, pr.pose_first, pr.pose_last, sbuf, sbuf + (size_t)pr.P * 3, st[0], (const T*)nullptr, (T*)nullptr);
-                            else LAUNCH_G(pr.by_pose.G, k_schur_pose, nbP, stream, tp, to, zc, tvec, dp, pr.pose_first, pr.pose_last, sbuf, sbuf + (size_t)pr.P * 3, st[0], (const T*)nullptr, (T*)nullptr);
-                            break;
+                    case 0: launch_schur_lm(0, false, nullptr, ""); break;
+                    case 1: launch_schur_pose(0, false, (const T*)nullptr, (T*)nullptr, false, false, ""); break;
                     case 2: {   // state slot 1 is never written here, slot 0 stays "iters = 0, not done"
                         const T tol2 = (T)0;
                         hipLaunchKernelGGL((k_cg_update<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, sbuf, sbuf + (size_t)pr.P * 3, nbP, gpart[0], nbC,

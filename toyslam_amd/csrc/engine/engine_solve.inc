@@ -302,7 +302,9 @@
             hipLaunchKernelGGL((k_pack_x<T>), dim3(nbC), dim3(kBlock), 0, stream, P, x, zc, WarmTerms<T>{}, (int*)nullptr);
             have_prev = false; n_prev = 0; n_tested = 0;
         }
-        if (tl.n_slices > 0) LAUNCH_GM(pr.by_lm.G, k_schur_lm, 1, nbL, stream, tl, zc, lmrec, (const T*)ninv, tvec, st[0], step, dl, npart + nbC);
+        if (tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
+            launch(k_schur_lm<T, g, 1, 0>, nbL, tl, zc, lmrec, (const T*)ninv, tvec, st[0], step, dl, npart + nbC, (const float*)nullptr, (float*)nullptr, no_gate());
+        });
         hipLaunchKernelGGL((k_pose_update<T>), dim3(nbC), dim3(kBlock), 0, stream, P, x, ps, theta, step, npart);
         const int nl = tl.n_slices > 0 ? nbL : 0;
         HIP_OK(hipMemcpyAsync(h_scratch, npart, sizeof(T) * (size_t)(nbC + nl), hipMemcpyDeviceToHost, stream));

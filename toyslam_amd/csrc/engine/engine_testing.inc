@@ -43,13 +43,7 @@
         { std::vector<char> is_pose((size_t)pr.n_vertices, 0); for (int i = 0; i < P; ++i) is_pose[(size_t)pr.pose_vertex[i]] = 1;
           int k = 0; for (int v = 0; v < pr.n_vertices; ++v) if (is_pose[(size_t)v]) rank_of_vertex[(size_t)v] = k++; }
         for (int i = 0; i < P; ++i) of_graph[(size_t)i] = rank_of_vertex[(size_t)pr.pose_vertex[i]];
-        if (which == 3) {
-            switch (marginal_width()) {
-                case 1: return ta_batched<1>(of_graph, in, out, n_cols);
-                case 16: return ta_batched<16>(of_graph, in, out, n_cols);
-                default: return ta_batched<8>(of_graph, in, out, n_cols);
-            }
-        }
+        if (which == 3) return pick<1, 16, 8>(marginal_width(), [&](auto nv) { return ta_batched<nv>(of_graph, in, out, n_cols); });
         std::vector<T> hz((size_t)P * kPoseRec), h3((size_t)P * 3); std::vector<float> hz32((size_t)P * kPoseRec);
         { if (int rc = copy_sync(hz.data(), zc, hz.size() * sizeof(T), hipMemcpyDeviceToHost)) return rc; }
         { if (int rc = copy_sync(hz32.data(), zc32, hz32.size() * sizeof(float), hipMemcpyDeviceToHost)) return rc; }

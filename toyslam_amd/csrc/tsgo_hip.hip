@@ -23,14 +23,15 @@
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/tsgo.h"
@@ -64,44 +65,29 @@ using namespace tsgo;
             return set_error(-11, std::string(#expr) + ": " + ncclGetErrorString(e_));                 \
     } while (0)
 
-// launch a kernel template over the lanes-per-vertex parameter
-#define LAUNCH_G(G, KERNEL, grid, stream, ...)                                                         \
-    do {                                                                                               \
-        switch (G) {                                                                                   \
-            case 1: hipLaunchKernelGGL((KERNEL<T, 1>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            case 2: hipLaunchKernelGGL((KERNEL<T, 2>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            case 4: hipLaunchKernelGGL((KERNEL<T, 4>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL((KERNEL<T, 8>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-        }                                                                                              \
-    } while (0)
-#define LAUNCH_GM(G, KERNEL, MODE, grid, stream, ...)                                                  \
-    do {                                                                                               \
-        switch (G) {                                                                                   \
-            case 1: hipLaunchKernelGGL((KERNEL<T, 1, MODE>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            case 2: hipLaunchKernelGGL((KERNEL<T, 2, MODE>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            case 4: hipLaunchKernelGGL((KERNEL<T, 4, MODE>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL((KERNEL<T, 8, MODE>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-        }                                                                                              \
-    } while (0)
-
-#define LAUNCH_GML(G, KERNEL, MODE, LOW, grid, stream, ...)                                             \
-    do {                                                                                               \
-        switch (G) {                                                                                   \
-            case 1: hipLaunchKernelGGL((KERNEL<T, 1, MODE, LOW>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            case 2: hipLaunchKernelGGL((KERNEL<T, 2, MODE, LOW>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            case 4: hipLaunchKernelGGL((KERNEL<T, 4, MODE, LOW>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL((KERNEL<T, 8, MODE, LOW>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-        }                                                                                              \
-    } while (0)
-#define LAUNCH_GML1(G, KERNEL, LOW, grid, stream, ...)                                                 \
-    do {                                                                                               \
-        switch (G) {                                                                                   \
-            case 1: hipLaunchKernelGGL((KERNEL<T, 1, LOW>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            case 2: hipLaunchKernelGGL((KERNEL<T, 2, LOW>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            case 4: hipLaunchKernelGGL((KERNEL<T, 4, LOW>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL((KERNEL<T, 8, LOW>), dim3(grid), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-        }                                                                                              \
-    } while (0)
+// Run-time value -> template argument: f(std::integral_constant<int, Vk>{}) for the listed Vk that equals v, and for the LAST listed value
+// when none does (lanes per vertex outside {1, 2, 4} run the 8-lane kernels, lanes per row outside {4, 8, 16, 32} the 64-lane ones).  A flag
+// is pick<0, 1>.  Calls nest, one per template axis; the constant a call site receives feeds both its instantiation and its profiler name.
+template <int V0, int... Vs, typename F> inline decltype(auto) pick(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+    else {
+        if (v == V0) return f(std::integral_constant<int, V0>{});
+        return pick<Vs...>(v, std::forward<F>(f));
+    }
+}
+// A kernel symbol as rocprofv3 prints it, without the namespace: kernel_name("k_schur_lm", "double", 4, 0, 1) = "k_schur_lm<double, 4, 0, 1>".
+// Type arguments come as strings, integer arguments as integers or as the constants pick() hands out.
+inline void template_arg(std::string& s, const char* type) { s += type; }
+inline void template_arg(std::string& s, int value) { s += std::to_string(value); }
+template <typename... A> std::string kernel_name(const char* base, const A&... args) {
+    std::string s(base);
+    if constexpr (sizeof...(A) > 0) {
+        const char* sep = "<";
+        ((s += sep, template_arg(s, args), sep = ", "), ...);
+        s += ">";
+    }
+    return s;
+}
 
 }  // namespace
 
