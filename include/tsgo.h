@@ -90,7 +90,20 @@ typedef struct tsgo_config {
                                 short-step / getting-worse stops, b untouched at fixed vertices).  1: the loop of the reference's in-process
                                 Python optimizer, python/optimizer/graph_optimizer.py:20-92 — Levenberg-Marquardt-style damping H + lambda I
                                 (lambda from 1e-3, x1.1 when chi^2 rose, /1.1 otherwise, within [1e-6, 10]; the `lambdaVal` the C++
-                                declares and never uses, OptimizerCpu.h:70), step `lr`, b zeroed at fixed vertices, stop on ||lr dx|| < 1e-3 only. */
+                                declares and never uses, OptimizerCpu.h:70), step `lr`, b zeroed at fixed vertices, stop on ||lr dx|| < 1e-3 only.
+                                2: Levenberg-Marquardt with step acceptance (no reference counterpart; the loop g2o and Ceres run).  One TRIAL =
+                                linearise at x with H + lambda I (b zeroed at fixed vertices as under 1), solve (H + lambda I) d = b (PCG from
+                                zero: warm_start is ignored, a full step leaves no remainder), take the FULL step x + d tentatively, evaluate the
+                                robustified chi^2 there and decide by the gain ratio rho = (chi^2(x) - chi^2(x + d)) / pred, pred = b^T d +
+                                lambda d^T d (the drop of the quadratic model: grad(sum rho_huber) = -2 b exactly, d^T H d = b^T d - lambda d^T d).
+                                Accepted (rho > 0 and pred > 0): the step stays, lambda *= max(1/3, 1 - (2 rho - 1)^3), nu = 2.  Rejected: the
+                                estimates are restored bit for bit, lambda *= nu, nu *= 2, and the next trial linearises again at the restored
+                                point.  lambda starts at lm_lambda0 (nu at 2) on every tsgo_optimize and stays within [1e-9, 1e9].  Trials count
+                                against `iterations`; chi^2 never rises.  Stops: TSGO_STOP_CONVERGED after an accepted step with ||d|| < 1e-3 or
+                                chi^2(x) - chi^2(x + d) <= lm_chi2_rel_tol * chi^2(x); TSGO_STOP_DAMPING when a rejection would push lambda past
+                                1e9; TSGO_STOP_CAP; TSGO_STOP_SOLVER.  Meant to be run with odom_jacobian = 1: under the constant Jacobians the
+                                model is wrong and the loop rejects often (and says so in steps_rejected).  precision = 32 and world > 1 are
+                                refused by tsgo_create. */
     double lr;               /* rules = 1: the step scale `lr` of GraphOptimizer.optimize(iterations, lr) (slam_main.py passes 0.2); ignored by rules = 0 */
     int32_t odom_jacobian;   /* 0 (default): the reference's ODOM Jacobians, the constants A = -I, B = +I (remote/graph/edge/EdgeSe2.h:35-37;
                                 parity).  1: the analytic Jacobians of the same residual under the reference's vertex update (SURVEY 8f
@@ -115,9 +128,13 @@ typedef struct tsgo_config {
                                 returned (python/slam_main.py:215-238; the reference re-creates everything per message,
                                 remote/app/ConnectionHandler.h:18-21).  Same answer to pcg_rel_tol.  What graph_optimizer runs, per connection
                                 (tsgo_reset_history). */
+    double lm_lambda0;       /* rules = 2: the damping of the first trial of every tsgo_optimize call; default 1e-3 (where rules = 1 starts) */
+    double lm_chi2_rel_tol;  /* rules = 2: an accepted step that lowered chi^2 by no more than this fraction of it ends the run (converged);
+                                default 1e-6 */
 } tsgo_config;
 
-enum { TSGO_STOP_CAP = 0, TSGO_STOP_WORSE = 1, TSGO_STOP_PLATEAU = 2, TSGO_STOP_CONVERGED = 3, TSGO_STOP_SOLVER = 4 };
+enum { TSGO_STOP_CAP = 0, TSGO_STOP_WORSE = 1, TSGO_STOP_PLATEAU = 2, TSGO_STOP_CONVERGED = 3, TSGO_STOP_SOLVER = 4,
+       TSGO_STOP_DAMPING = 5 /* rules = 2: a rejected trial would have raised lambda past its upper bound */ };
 
 #define TSGO_MAX_TRACE 256
 typedef struct tsgo_stats {
@@ -143,6 +160,13 @@ typedef struct tsgo_stats {
                                             request (kept in place or carried over by vertex id), 2 when it did and the first solve dropped it
                                             (it did not fit the new estimates), 0 otherwise */
     int32_t graph_replay;                /* 1 when this run replayed captured hipGraphs of the PCG iteration (tsgo_config.use_graphs), 0: eager launches */
+    /* rules = 2 (all zero under rules 0 and 1).  Every trace of a rules = 2 run is PER TRIAL: chi2[it] is the chi^2 at the point trial `it`
+     * linearised (it repeats after a rejection), lambda_last the damping of the last trial, iterations_run the number of trials. */
+    int32_t steps_rejected;              /* trials whose step was rolled back */
+    double lm_lambda[TSGO_MAX_TRACE];    /* damping of each trial */
+    double lm_gain[TSGO_MAX_TRACE];      /* gain ratio rho of each trial (0 where pred = 0); accepted when > 0 with pred > 0 */
+    double lm_pred[TSGO_MAX_TRACE];      /* predicted decrease b^T d + lambda d^T d of each trial */
+    double lm_chi2_trial[TSGO_MAX_TRACE];/* robustified chi^2 at the trial point x + d: the chi2 of the next trial when the step was accepted */
 } tsgo_stats;
 
 /* Fills cfg with defaults. */
@@ -203,7 +227,8 @@ int tsgo_comm_time_allreduce(tsgo_optimizer* opt, int64_t n_elements, int32_t re
 /* Timing probe used by bench.py: average device time (hipEvent, microseconds) of `reps` back-to-back
  * launches of one kernel on the handle's stream, and the algorithmic bytes one launch moves.
  * which: 0 schur_lm, 1 schur_pose, 2 cg_update, 3 lin_lm, 4 lin_pose, 5 one whole PCG iteration
- * (preconditioner application included), 6 the multigrid numeric setup of one GN iteration. */
+ * (preconditioner application included), 6 the multigrid numeric setup of one GN iteration, 7 the chi^2-only evaluation pass of a
+ * rules = 2 trial (a handle created with rules = 2; to be compared with 3 + 4, the linearisation it stands in for). */
 int tsgo_time_kernel(tsgo_optimizer* opt, int32_t which, int32_t reps, double* us_per_launch, double* bytes_per_launch);
 
 /* Timing probe for the multigrid V-cycle's coarse levels (bench.py's per-kernel table): for every explicit level below

@@ -124,10 +124,21 @@ public:
         if (stats.stop_reason == TSGO_STOP_WORSE) std::cout << "Error is getting worse\n";
         if (stats.stop_reason == TSGO_STOP_PLATEAU) std::cout << "Plateau: NO MORE OPT\n";
         if (stats.stop_reason == TSGO_STOP_CONVERGED) std::cout << "CONVERGED\n";
+        if (stats.stop_reason == TSGO_STOP_DAMPING) std::cout << "Damping at its upper bound: no step lowers the error\n";      // rules = 2 only
         const int last = stats.iterations_run > 0 ? (stats.iterations_run < TSGO_MAX_TRACE ? stats.iterations_run : TSGO_MAX_TRACE) - 1 : 0;
         std::cout << "Summary() error = " << stats.chi2[last] << std::endl;
     }
     const tsgo_stats& Stats() const { return stats; }
+    // rules = 2 (Levenberg-Marquardt, tsgo_config.rules): what the last Optimize did trial by trial — Stats().lm_lambda / lm_gain / lm_pred /
+    // lm_chi2_trial, entries 0 .. Stats().trace_len - 1 — and how many of its steps were rolled back
+    int StepsRejected() const { return stats.steps_rejected; }
+    bool StepAccepted(int trial) const { return trial >= 0 && trial < stats.trace_len && stats.lm_gain[trial] > 0 && stats.lm_pred[trial] > 0; }
+    // A config for that loop: the defaults with rules = 2 and the analytic ODOM Jacobians it is meant to run with.
+    static tsgo_config LevenbergMarquardtConfig(double lambda0 = 1e-3, double chi2_rel_tol = 1e-6) {
+        tsgo_config c; tsgo_default_config(&c);
+        c.rules = 2; c.odom_jacobian = 1; c.lm_lambda0 = lambda0; c.lm_chi2_rel_tol = chi2_rel_tol;
+        return c;
+    }
 
     // Marginal covariances at the estimates of the last Optimize (tsgo_marginals): 9 doubles per id, row-major; a landmark's 2x2 block
     // in the leading 2x2.  Throws on an error (unknown id, no fixed vertex, no graph yet, precision 32).

@@ -336,6 +336,14 @@
         HIP_OK(hipHostMalloc((void**)&h_flag, 16 * sizeof(int), hipHostMallocCoherent));
         std::memset(h_flag, 0, 16 * sizeof(int));
         HIP_OK(hipHostMalloc((void**)&h_scratch, sizeof(T) * (size_t)(std::max(nbP, 2 * nbC) + nbL + 8)));
+        snap_ps = snap_theta = snap_lm = lm_red = nullptr;
+        if (lm_rules()) {
+            if (int rc = dalloc(&snap_ps, (size_t)P * 4)) return rc;
+            if (int rc = dalloc(&snap_theta, (size_t)P)) return rc;
+            if (int rc = dalloc(&snap_lm, (size_t)std::max(L, 1) * 2)) return rc;
+            if (int rc = dalloc(&lm_red, lm_red_size())) return rc;
+            HIP_OK(hipHostMalloc((void**)&h_lm, sizeof(T) * lm_red_size()));
+        }
         HIP_OK(hipStreamSynchronize(stream));
         lap("state + slot tables to the device");
         if (amg_on) { if (int rc = upload_amg()) return rc; }

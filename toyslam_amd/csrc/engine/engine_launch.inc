@@ -38,11 +38,12 @@
     // damping of the current linearisation (rules = 1, graph_optimizer.py:24-43; 0 under the cpu/eigen rules) and the step the update takes
     double lambda = 0;
     bool py_rules() const { return cfg.rules == 1; }
+    bool lm_rules() const { return cfg.rules == 2; }      // Levenberg-Marquardt with step acceptance (engine_solve.inc: lm_loop)
     // pose-pose slots in general form (tsgo_math.h: eight dynamic planes per slot): analytic ODOM Jacobians, or a graph that holds
     // virtual landmark measurements (edge type 2) — the kernels' OJ = 1 instantiations
     bool oj() const { return cfg.odom_jacobian == 1 || pr.has_vlm; }
     int odom_analytic_flag() const { return cfg.odom_jacobian == 1 ? 1 : 0; }
-    double step_scale() const { return py_rules() ? cfg.lr : kStepScale; }
+    double step_scale() const { return lm_rules() ? 1.0 : (py_rules() ? cfg.lr : kStepScale); }
     // a graph with priors (edge types 3, 4) takes the PRI = 1 instantiations; one without launches exactly what it did before priors existed
     PriorArgs<T> pose_prior_args() const { return PriorArgs<T>{pri_p_off, pri_p, pri_lchi, tl.n_slices > 0 ? nbL : 0}; }
     PriorArgs<T> lm_prior_args() const { return PriorArgs<T>{pri_l_off, pri_l, pri_lchi, 0}; }
@@ -53,19 +54,29 @@
         launch_lin_pose_only();
     }
     void launch_lin_lm() {              // (tsgo_time_kernel too)
-        const int zf = py_rules() ? 1 : 0;
+        const int zf = (py_rules() || lm_rules()) ? 1 : 0;
         if (tl.n_slices == 0) return;
         pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(pr.has_priors, [&](auto pri) {
             launch(k_lin_lm<T, g, pri>, nbL, tl, ps, lmrec, gauge_l, ninv, (T)lambda, zf, pri ? lm_prior_args() : no_priors());
         }); });
     }
     void launch_lin_pose_only() {       // (tsgo_time_kernel too)
-        const int zf = py_rules() ? 1 : 0;
+        const int zf = (py_rules() || lm_rules()) ? 1 : 0;
         pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) {
             launch(k_lin_pose<T, g, general, pri>, nbP, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf,
                    general ? odom_analytic_flag() : 0, pri ? pose_prior_args() : no_priors());
         }); }); });
     }
+    // rules = 2: robustified chi^2 at the current estimates, nbP partials into `out` (tsgo_lm_kernels.h; tsgo_time_kernel 7 too).  One launch,
+    // and one more in front of it on a graph with priors (the landmark priors' partials, which k_chi2<.., 1> folds as k_lin_pose<.., 1> does)
+    void launch_chi2(T* out) {
+        if (pr.has_priors && tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { launch(k_chi2_lm_prior<T, g>, nbL, tl, (const T*)lmrec, lm_prior_args()); });
+        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) {
+            launch(k_chi2<T, g, general, pri>, nbP, tp, to, (const T*)ps, (const T*)lmrec, out, pri ? pose_prior_args() : no_priors());
+        }); }); });
+    }
+    // (LM slot: index, zx zy w0 w1, 16 B of the landmark record; pose-pose slot: its index, and at the first endpoint nine planes + the neighbour's record)
+    double bytes_chi2() { const double v = sizeof(T); return (double)pr.n_lm_edges * (4 + 6 * v) + pr.P * 4.0 * v + od_slots_live() * (4 + 6.5 * v) + nbP * v; }
     void launch_finalize() {
         hipLaunchKernelGGL((k_pose_finalize<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, part, ps, dp, minv, r, p, q, x, zc, gpart[0], st[0], (const T*)(amg_on ? omega_dev : one_dev), gscale_dev, amg_on && low_cycle ? zc32 : (float*)nullptr);
     }
@@ -85,7 +96,7 @@
         pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(low, [&](auto lo) {
             PF(bytes_schur_lm(lo) + (gate ? 2.0 * nbC * sizeof(T) : 0.0), gate ? "stopping rule + in-cycle product" : wh, "k_schur_lm", tname(), g, 0, lo);
             if (tl.n_slices > 0) launch(k_schur_lm<T, g, 0, lo>, nbL, tl, zc, lmrec, (const T*)ninv, tvec, st[slot], T(0), dl, npart,
-                                        lo ? (const float*)zc32 : nullptr, lo ? tvec32 : nullptr, lo && gate ? *gate : no_gate());
+                                        lo ? (const float*)zc32 : nullptr, lo ? tvec32 : nullptr, lo && gate ? *gate : no_gate(), T(0), (T*)nullptr);
         }); });
     }
     void launch_schur_pose(int slot, bool low, const T* rvec, T* rz_part, bool post_smooth, bool as_residual, const char* wh) {

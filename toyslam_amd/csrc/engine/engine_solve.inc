@@ -303,7 +303,7 @@
             have_prev = false; n_prev = 0; n_tested = 0;
         }
         if (tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
-            launch(k_schur_lm<T, g, 1, 0>, nbL, tl, zc, lmrec, (const T*)ninv, tvec, st[0], step, dl, npart + nbC, (const float*)nullptr, (float*)nullptr, no_gate());
+            launch(k_schur_lm<T, g, 1, 0>, nbL, tl, zc, lmrec, (const T*)ninv, tvec, st[0], step, dl, npart + nbC, (const float*)nullptr, (float*)nullptr, no_gate(), T(0), (T*)nullptr);
         });
         hipLaunchKernelGGL((k_pose_update<T>), dim3(nbC), dim3(kBlock), 0, stream, P, x, ps, theta, step, npart);
         const int nl = tl.n_slices > 0 ? nbL : 0;
@@ -327,6 +327,82 @@
         HIP_OK(hipMemcpyAsync(&v, d, sizeof(T), hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));
         *nl2 = (double)v;
+        return 0;
+    }
+
+    // ---- rules = 2: Levenberg-Marquardt with step acceptance (include/tsgo.h: tsgo_config.rules; DESIGN.md section 12) ----
+    static constexpr double kLmLambdaMin = 1e-9, kLmLambdaMax = 1e9;
+    int lm_nl() const { return tl.n_slices > 0 ? nbL : 0; }
+    size_t lm_red_size() const { return (size_t)2 * (nbC + std::max(nbL, 1)) + nbP; }
+    // The tentative full step of a trial and everything the decision needs, in one chain of launches and ONE copy back: snapshot of the
+    // estimates, back-substitution + update with step 1 (the landmarks' predicted decrease in the same pass, k_schur_lm<.., 2>; the poses'
+    // in k_pose_update_lm), chi^2 at the trial point (k_chi2).  Nothing of the step enters the warm start's history: a full step leaves
+    // no remainder to start from, and a rejected one must leave nothing at all.
+    int do_lm_step(double lam, double* np2, double* nl2, double* pred, double* chi2_trial) {
+        const int P = pr.P, L = pr.L, nl = lm_nl();
+        T* norm_p = lm_red; T* norm_l = lm_red + nbC; T* pred_p = norm_l + nl; T* pred_l = pred_p + nbC; T* chi = pred_l + nl;
+        launch(k_lm_state<T, 0>, grid_for(std::max(P, L)), P, L, ps, theta, lmrec, snap_ps, snap_theta, snap_lm);
+        hipLaunchKernelGGL((k_pack_x<T>), dim3(nbC), dim3(kBlock), 0, stream, P, x, zc, WarmTerms<T>{}, (int*)nullptr);
+        have_prev = false; n_prev = 0; n_tested = 0;
+        if (nl > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
+            launch(k_schur_lm<T, g, 2, 0>, nbL, tl, zc, lmrec, (const T*)ninv, tvec, st[0], T(1), dl, norm_l, (const float*)nullptr, (float*)nullptr, no_gate(), (T)lam, pred_l);
+        });
+        launch(k_pose_update_lm<T>, nbC, P, (const T*)x, ps, theta, (const T*)part, (T)lam, norm_p, pred_p);
+        launch_chi2(chi);
+        const size_t n = (size_t)2 * (nbC + nl) + nbP;
+        HIP_OK(hipMemcpyAsync(h_lm, lm_red, sizeof(T) * n, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        auto sum = [&](size_t from, int count) { double v = 0; for (int k = 0; k < count; ++k) v += (double)h_lm[from + k]; return v; };
+        *np2 = sum(0, nbC); *nl2 = sum(nbC, nl);
+        *pred = sum((size_t)nbC + nl, nbC) + sum((size_t)2 * nbC + nl, nl);
+        *chi2_trial = sum((size_t)2 * (nbC + nl), nbP);
+        return 0;
+    }
+    int lm_restore() {
+        launch(k_lm_state<T, 1>, grid_for(std::max(pr.P, pr.L)), pr.P, pr.L, ps, theta, lmrec, snap_ps, snap_theta, snap_lm);
+        return 0;
+    }
+    // The loop.  One trial = linearise (H + lambda I, b zeroed at fixed vertices), solve, tentative full step, decide; a rejected trial is
+    // followed by a fresh linearisation at the restored point: lambda is baked into the landmark inverses and the pose diagonals.
+    int lm_loop(int iterations, tsgo_stats& s) {
+        double lam = std::min(std::max(cfg.lm_lambda0, kLmLambdaMin), kLmLambdaMax), nu = 2;
+        for (int it = 0; it < iterations; ++it) {
+            double err = 0; float ms = 0;
+            HIP_OK(hipEventRecord(ev[0], stream));
+            lambda = lam;
+            if (int rc = do_linearize(&err)) return rc;
+            HIP_OK(hipEventRecord(ev[1], stream));
+            const bool traced = it < TSGO_MAX_TRACE;
+            if (traced) { s.chi2[it] = err; s.lm_lambda[it] = lam; }
+            s.chi2_last = err; s.lambda_last = lam;
+            s.iterations_run = it + 1; s.trace_len = std::min(it + 1, TSGO_MAX_TRACE);
+            int cg = 0, fail = 0;
+            if (int rc = do_solve(&cg, &fail)) return rc;
+            HIP_OK(hipEventRecord(ev[2], stream));
+            if (traced) s.pcg_iters[it] = cg;
+            s.pcg_iters_total += cg;
+            if (fail != 0) { s.stop_reason = TSGO_STOP_SOLVER; break; }
+            double np2 = 0, nl2 = 0, pred = 0, trial = 0;
+            if (int rc = do_lm_step(lam, &np2, &nl2, &pred, &trial)) return rc;
+            HIP_OK(hipEventRecord(ev[3], stream));
+            HIP_OK(hipEventSynchronize(ev[3]));
+            HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1])); s.ms_linearize += ms;
+            HIP_OK(hipEventElapsedTime(&ms, ev[1], ev[2])); s.ms_solve += ms;
+            HIP_OK(hipEventElapsedTime(&ms, ev[2], ev[3])); s.ms_update += ms;
+            s.last_delta_norm = std::sqrt(np2 + nl2);
+            const double gain = pred != 0 ? (err - trial) / pred : 0.0;
+            if (traced) { s.lm_pred[it] = pred; s.lm_chi2_trial[it] = trial; s.lm_gain[it] = gain; }
+            if (gain > 0 && pred > 0) {      // (a NaN anywhere fails both tests: rejected)
+                const double t = 2 * gain - 1;
+                lam = std::min(std::max(lam * std::max(1.0 / 3.0, 1 - t * t * t), kLmLambdaMin), kLmLambdaMax); nu = 2;
+                if (s.last_delta_norm < kDeltaTol || err - trial <= cfg.lm_chi2_rel_tol * err) { s.stop_reason = TSGO_STOP_CONVERGED; break; }
+            } else {
+                if (int rc = lm_restore()) return rc;
+                ++s.steps_rejected;
+                if (lam * nu > kLmLambdaMax) { s.stop_reason = TSGO_STOP_DAMPING; break; }
+                lam *= nu; nu *= 2;
+            }
+        }
         return 0;
     }
 
@@ -359,7 +435,8 @@
         const double lam_max = 1e1, lam_min = 1e-6, lam_fac = 1.1;
         double lam = 1e-3;
         const double step = step_scale();
-        for (int it = 0; it < iterations; ++it) {
+        if (lm_rules()) { if (int rc = lm_loop(iterations, s)) return rc; }
+        for (int it = 0; it < (lm_rules() ? 0 : iterations); ++it) {      // rules 0 and 1
             double err = 0; float ms = 0;
             HIP_OK(hipEventRecord(ev[0], stream));
             if (py_rules()) {

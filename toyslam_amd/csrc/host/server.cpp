@@ -6,7 +6,8 @@
 //   goes to its connection's last handle when that is idle (it holds the connection's structure and solver history), else to the listed
 //   GPU with the fewest requests in flight.  One graph per GPU, no collective: how this server uses a node.
 //   RULES "python" or "python:LR": the loop of the reference's in-process Python optimizer instead (lambda * I damping, step LR,
-//   default 0.2 as slam_main.py passes); ODOM_JACOBIAN "analytic": the extension of tsgo_config.odom_jacobian.  Both default to
+//   default 0.2 as slam_main.py passes); "lm" or "lm:LAMBDA0": Levenberg-Marquardt with step acceptance (tsgo_config.rules = 2: full steps,
+//   a rejected step is rolled back, ITERATIONS counts trials; best with ODOM_JACOBIAN=analytic); ODOM_JACOBIAN "analytic": the extension of tsgo_config.odom_jacobian.  Both default to
 //   what the reference's C++ server does.  WARM_REQUESTS 1: tsgo_config.warm_requests (a connection's next request starts its PCG
 //   solves from the history of ITS OWN last one when it gets the same engine handle back; a handle that last served another
 //   connection forgets that history first, so no client's iteration counts or low-order bits depend on other clients' traffic;
@@ -311,6 +312,11 @@ int main(int argc, char* argv[]) {
             const size_t colon = rulesS.find(':');
             if (colon != std::string::npos) cfg.lr = std::stod(rulesS.substr(colon + 1));
             std::cout << "rules: python/optimizer/graph_optimizer.py (lambda * I, lr " << cfg.lr << ")\n";
+        } else if (rulesS.rfind("lm", 0) == 0) {
+            cfg.rules = 2;
+            const size_t colon = rulesS.find(':');
+            if (colon != std::string::npos) cfg.lm_lambda0 = std::stod(rulesS.substr(colon + 1));
+            std::cout << "rules: Levenberg-Marquardt with step acceptance (full steps, gain ratio, lambda from " << cfg.lm_lambda0 << ")\n";
         }
         if (odomS == "analytic") { cfg.odom_jacobian = 1; std::cout << "ODOM Jacobians: analytic (extension)\n"; }
         cfg.warm_requests = warm_requests ? 1 : 0;      // a connection's next request continues from the last one's solver history (tsgo.h)

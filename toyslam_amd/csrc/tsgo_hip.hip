@@ -45,6 +45,7 @@
 #include "host/problem.h"
 #include "tsgo_amg_kernels.h"
 #include "tsgo_kernels.h"
+#include "tsgo_lm_kernels.h"
 #include "tsgo_marginal_kernels.h"
 #include "tsgo_sym_kernels.h"
 
@@ -246,6 +247,9 @@ template <typename T> struct Engine : IEngine {
     CgState<T>* h_state = nullptr;     // pinned
     int* h_flag = nullptr;             // pinned, coherent: what the gate of the last launched iteration saw (k_iter_gate, do_solve_paced)
     T* h_scratch = nullptr;            // pinned, partial sums
+    // rules = 2 only (null otherwise): the estimates before a trial's step (k_lm_state), and the partials one trial brings back in one copy:
+    // lm_red = [ |d_p|^2 (nbC) | |d_l|^2 (nbL) | pred, poses (nbC) | pred, landmarks (nbL) | chi^2 at the trial point (nbP) ], h_lm its pinned twin
+    T *snap_ps = nullptr, *snap_theta = nullptr, *snap_lm = nullptr, *lm_red = nullptr, *h_lm = nullptr;
     int nbP = 0, nbL = 0, nbC = 0;
     bool fuse_post_smooth = true;      // the level-0 post-smoothing in the epilogue of the cycle's second product (research: TSGO_FUSE_POST=0 = k_smooth0)
     double hier_shift_cfg = 0;         // what a graph starts with (0; research: TSGO_HIER_SHIFT)
@@ -351,6 +355,7 @@ template <typename T> struct Engine : IEngine {
         if (h_state) { (void)hipHostFree(h_state); h_state = nullptr; }
         if (h_flag) { (void)hipHostFree(h_flag); h_flag = nullptr; }
         if (h_scratch) { (void)hipHostFree(h_scratch); h_scratch = nullptr; }
+        if (h_lm) { (void)hipHostFree(h_lm); h_lm = nullptr; }
         if (h_rho) { (void)hipHostFree(h_rho); h_rho = nullptr; }
         have_graph_data = false;
     }
@@ -445,6 +450,12 @@ int tsgo_create(const tsgo_config* cfg, tsgo_optimizer** out) {
     if (c.world < 1) c.world = 1;
     if (c.pcg_rel_tol <= 0) c.pcg_rel_tol = 1e-10;
     if (c.pcg_max_iters <= 0) c.pcg_max_iters = 20000;
+    if (c.rules == 2) {
+        if (c.precision != 64) return tsgo::set_error(-1, "tsgo_create: rules = 2 (Levenberg-Marquardt) needs precision = 64: the gain ratio near the optimum is below f32 resolution");
+        if (c.world > 1) return tsgo::set_error(-1, "tsgo_create: rules = 2 (Levenberg-Marquardt) does not support edge-sharded handles (world > 1)");
+        if (!(c.lm_lambda0 > 0)) c.lm_lambda0 = 1e-3;
+        if (!(c.lm_chi2_rel_tol >= 0)) c.lm_chi2_rel_tol = 1e-6;
+    }
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
         return tsgo::set_error(-10, "tsgo_create: no HIP device is visible; this library has no CPU fallback");

@@ -418,13 +418,16 @@ __global__ __launch_bounds__(kBlock) void k_pose_finalize(int P, const T* __rest
 // ------------------------------------------------------------------------------------------------
 // KA schur_lm: per landmark — t = Dl^-1 W^T v, v being the vector held in zc[.][0..2].
 //   MODE 0: write t.   MODE 1 (back-substitution): dl = u - t, landmark += step * dl, |dl|^2 partial.
+//   MODE 2 (the back-substitution of a rules = 2 trial): MODE 1, and the landmarks' share of the predicted decrease, g_l^T dl + lambda |dl|^2
+//   with g_l = D_l u recovered from the inverse block already in registers, one partial per workgroup into pred_part.
 // HOT KERNEL 1 of the PCG iteration.
 template <typename T, int G, int MODE, int LOW = 0>
 __global__ __launch_bounds__(kBlock) void k_schur_lm(Table<T> tb, const T* __restrict__ zc, T* __restrict__ lmrec,
                                                      const T* __restrict__ ninv, T* __restrict__ t, const CgState<T>* __restrict__ st,
                                                      T step, T* __restrict__ dl_out, T* __restrict__ norm_part,
                                                      const float* __restrict__ zc32 = nullptr, float* __restrict__ t32 = nullptr,
-                                                     const GateArgs<T> gate = GateArgs<T>{nullptr, nullptr, nullptr, 0, T(0), nullptr, 0}) {
+                                                     const GateArgs<T> gate = GateArgs<T>{nullptr, nullptr, nullptr, 0, T(0), nullptr, 0},
+                                                     T lambda = T(0), T* __restrict__ pred_part = nullptr) {
     __shared__ T red[kWavesPerBlock];
     // The iteration's stopping rule rides in workgroup 0 of its first product (gate.st set): one launch fewer per iteration.  The other
     // workgroups do not wait for the verdict: a solve that has just converged runs this one pass for nothing (its output is scratch) and
@@ -438,7 +441,7 @@ __global__ __launch_bounds__(kBlock) void k_schur_lm(Table<T> tb, const T* __res
     const int lane = threadIdx.x & 63;
     constexpr int VPS = 64 / G;
     const int l = slice * VPS + lane / G;
-    T nrm = 0;
+    T nrm = 0, prd = 0;
     if (live) {
         T acc0 = 0, acc1 = 0;
         const size_t S = tb.slots;
@@ -498,17 +501,28 @@ __global__ __launch_bounds__(kBlock) void k_schur_lm(Table<T> tb, const T* __res
                 else { t[(size_t)l * 2] = t0; t[(size_t)l * 2 + 1] = t1; }
             }
             else {
-                const T d0 = lr[5] - t0, d1 = lr[6] - t1;
+                const T u0 = lr[5], u1 = lr[6];
+                const T d0 = u0 - t0, d1 = u1 - t1;
                 dl_out[(size_t)l * 2] = d0; dl_out[(size_t)l * 2 + 1] = d1;
                 lr[0] += step * d0; lr[1] += step * d1;
                 nrm = d0 * d0 + d1 * d1;
+                if (MODE == 2) {
+                    T dxx, dxy, dyy;
+                    inv_sym2<T>(ixx, ixy, iyy, dxx, dxy, dyy);      // D_l (damping and gauge inside); a landmark without edges has 0 and d = 0
+                    const T g0 = dxx * u0 + dxy * u1, g1 = dxy * u0 + dyy * u1;
+                    prd = g0 * d0 + g1 * d1 + lambda * nrm;
+                }
             }
         }
     }
     else if (done) return;
-    if (MODE == 1) {
+    if (MODE != 0) {
         const T total = block_sum<T>(nrm, red);
         if (threadIdx.x == 0) norm_part[blockIdx.x] = total;
+    }
+    if (MODE == 2) {
+        const T total = block_sum<T>(prd, red);
+        if (threadIdx.x == 0) pred_part[blockIdx.x] = total;
     }
 }
 

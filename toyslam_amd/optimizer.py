@@ -11,13 +11,14 @@ import numpy as np
 from . import _lib
 from .graph import GraphArrays
 
-STOP = {0: "cap", 1: "worse", 2: "plateau", 3: "converged", 4: "solver_failed"}
+STOP = {0: "cap", 1: "worse", 2: "plateau", 3: "converged", 4: "solver_failed", 5: "damping"}
 
 
 class HipOptimizer:
     def __init__(self, device=0, precision=64, pcg_rel_tol=1e-10, pcg_max_iters=20000, lanes_per_pose=0,
                  lanes_per_lm=0, use_graphs="auto", rank=0, world=1, preconditioner="amg", xcd_map=None, warm_start=None,
-                 reuse_structure=None, rules="cpp", lr=0.2, odom_jacobian="constant", cycle_level0="implicit", cycle_storage=16, warm_requests=False, testing=False):
+                 reuse_structure=None, rules="cpp", lr=0.2, odom_jacobian="constant", cycle_level0="implicit", cycle_storage=16, warm_requests=False, lm_lambda0=None, lm_chi2_rel_tol=None,
+                 testing=False):
         # testing=True: libtsgo_hip_testing.so (the same sources with -DTSGO_TESTING: hooks, research variables, in-process group)
         # (TSGO_PY_TESTING_LIB=1: research scripts under tools/research and tests/research that set hook / research variables pick the
         # testing library without being edited; it selects which LIBRARY this Python wrapper loads, the product library reads nothing)
@@ -35,7 +36,12 @@ class HipOptimizer:
             cfg.warm_start = int(warm_start)
         if reuse_structure is not None:
             cfg.reuse_structure = int(reuse_structure)
-        cfg.rules, cfg.lr = {"cpp": 0, "python": 1}[rules], float(lr)
+        cfg.rules, cfg.lr = {"cpp": 0, "python": 1, "lm": 2}[rules], float(lr)
+        # rules="lm": Levenberg-Marquardt with step acceptance (tsgo_config.rules = 2); meant for odom_jacobian="analytic"
+        if lm_lambda0 is not None:
+            cfg.lm_lambda0 = float(lm_lambda0)
+        if lm_chi2_rel_tol is not None:
+            cfg.lm_chi2_rel_tol = float(lm_chi2_rel_tol)
         cfg.odom_jacobian = {"constant": 0, "analytic": 1}[odom_jacobian]
         cfg.cycle_level0 = {"implicit": 0, "explicit": 1}[cycle_level0]
         cfg.cycle_storage = {16: 16, 32: 32}[cycle_storage]
@@ -88,7 +94,10 @@ class HipOptimizer:
                     cg_iters=np.array(st.pcg_iters[:n]), delta_norm=st.last_delta_norm, ms_total=st.ms_total,
                     ms_linearize=st.ms_linearize, ms_solve=st.ms_solve, ms_update=st.ms_update, ms_setup=st.ms_setup, structure_reused=bool(st.structure_reused), lambda_last=st.lambda_last,
                     n_pose=st.n_pose, n_lm=st.n_lm, n_odom_edges=st.n_odom_edges, n_lm_edges=st.n_lm_edges,
-                    cg_total=st.pcg_iters_total, fallbacks=st.pcg_fallbacks, cycle_storage_now=st.cycle_storage_now, history_carried=st.history_carried, graph_replay=bool(st.graph_replay))
+                    cg_total=st.pcg_iters_total, fallbacks=st.pcg_fallbacks, cycle_storage_now=st.cycle_storage_now, history_carried=st.history_carried, graph_replay=bool(st.graph_replay),
+                    # rules="lm": per-trial traces (zeros under the other rules); trial k was accepted when lm_gain[k] > 0 and lm_pred[k] > 0
+                    rejected=st.steps_rejected, lm_lambda=np.array(st.lm_lambda[:n]), lm_gain=np.array(st.lm_gain[:n]), lm_pred=np.array(st.lm_pred[:n]),
+                    lm_chi2_trial=np.array(st.lm_chi2_trial[:n]))
 
     def vertices(self):
         out = np.zeros((self.n_vertices, 3)) if self._v_in is None else np.ascontiguousarray(self._v_in.copy())
@@ -218,7 +227,9 @@ class GraphOptimizer:
         """rules="cpp" (default): the C++ server's loop, whose step is fixed at 0.2 (remote/optimizer/OptimizerCpu.h:164).
         rules="python": the reference's own GraphOptimizer.optimize(iterations, lr) — damping lambda*I, any lr."""
         kw = dict(self.kw)
-        if kw.get("rules", "cpp") == "cpp":
+        if kw.get("rules", "cpp") == "lm":
+            pass                                           # full steps: lr has no meaning
+        elif kw.get("rules", "cpp") == "cpp":
             if lr != 0.2:
                 raise ValueError("the remote optimizer's step is fixed at 0.2 (remote/optimizer/OptimizerCpu.h:164); pass rules=\"python\" for GraphOptimizer.optimize(iterations, lr)")
         else:
