@@ -223,10 +223,8 @@ struct Twin {
             if (pr.has_priors)      // landmark priors (type 4, as k_lin_lm<.., 1>): D_l += Omega_w, g_l -= Omega_w (l - m)
                 for (uint32_t k = pr.prior_l_off[l]; k < pr.prior_l_off[l + 1]; ++k) {
                     const double* q = &pri_l[(size_t)k * tsgo::PRI_LM_REC];
-                    const double e0 = lx - q[tsgo::PRL_MX], e1 = ly - q[tsgo::PRL_MY];
-                    double rho, hw; tsgo::huber<double>(q[tsgo::PRL_W0] * e0 * e0 + q[tsgo::PRL_W1] * e1 * e1, rho, hw);
-                    const double a0 = hw * q[tsgo::PRL_W0], a1 = hw * q[tsgo::PRL_W1];
-                    dxx += a0; dyy += a1; g0 -= a0 * e0; g1 -= a1 * e1; chi_pr += rho;
+                    const auto o = tsgo::lm_prior_linearize<double>(q[tsgo::PRL_MX], q[tsgo::PRL_MY], q[tsgo::PRL_W0], q[tsgo::PRL_W1], lx, ly);
+                    dxx += o.a0; dyy += o.a1; g0 -= o.a0 * o.e0; g1 -= o.a1 * o.e1; chi_pr += o.rho;
                 }
             if (zero_fixed && pr.gauge_l[l] > 0) { g0 = 0; g1 = 0; }
             double ixx, ixy, iyy; tsgo::inv_sym2(dxx, dxy, dyy, ixx, ixy, iyy);
@@ -321,14 +319,12 @@ struct Twin {
             if (pr.has_priors)      // pose priors (type 3, as pose_prior_fold): e_t = R_m^T (t - t_m), e_th = wrap(th - m_th), J = blockdiag(R_m^T, 1)
                 for (uint32_t k = pr.prior_p_off[i]; k < pr.prior_p_off[i + 1]; ++k) {
                     const double* q = &pri_p[(size_t)k * tsgo::PRI_POSE_REC];
-                    const double cm = q[tsgo::PRI_C], sm = q[tsgo::PRI_S], dx = x0 - q[tsgo::PRI_MX], dy = y0 - q[tsgo::PRI_MY];
-                    const double e0 = cm * dx + sm * dy, e1 = cm * dy - sm * dx, et = std::atan2(sn * cm - c * sm, c * cm + sn * sm);
-                    double rho, hw; tsgo::huber<double>(q[tsgo::PRI_W0] * e0 * e0 + q[tsgo::PRI_W1] * e1 * e1 + q[tsgo::PRI_W2] * et * et, rho, hw);
-                    const double a0 = hw * q[tsgo::PRI_W0], a1 = hw * q[tsgo::PRI_W1], a2 = hw * q[tsgo::PRI_W2];
-                    o18[0] += a0 * cm * cm + a1 * sm * sm; o18[1] += (a0 - a1) * cm * sm; o18[3] += a0 * sm * sm + a1 * cm * cm; o18[5] += a2;
-                    const double f0 = a0 * e0, f1 = a1 * e1;
-                    o18[6] -= cm * f0 - sm * f1; o18[7] -= sm * f0 + cm * f1; o18[8] -= a2 * et;
-                    chi += rho;
+                    const double cm = q[tsgo::PRI_C], sm = q[tsgo::PRI_S];
+                    const auto o = tsgo::pose_prior_linearize<double>(q[tsgo::PRI_MX], q[tsgo::PRI_MY], cm, sm, q[tsgo::PRI_W0], q[tsgo::PRI_W1], q[tsgo::PRI_W2], x0, y0, c, sn);
+                    o18[0] += o.a0 * cm * cm + o.a1 * sm * sm; o18[1] += (o.a0 - o.a1) * cm * sm; o18[3] += o.a0 * sm * sm + o.a1 * cm * cm; o18[5] += o.a2;
+                    const double f0 = o.a0 * o.e0, f1 = o.a1 * o.e1;
+                    o18[6] -= cm * f0 - sm * f1; o18[7] -= sm * f0 + cm * f1; o18[8] -= o.a2 * o.et;
+                    chi += o.rho;
                 }
             if (zero_fixed && pr.gauge_p[i] > 0) { o18[6] = 0; o18[7] = 0; o18[8] = 0; }
         }

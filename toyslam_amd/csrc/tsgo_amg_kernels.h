@@ -114,15 +114,13 @@ __global__ __launch_bounds__(kBlock) void k_schur_blocks(int nnz, const int* __r
         return;
     }
     const T ci = ps[(size_t)i * 4 + 2], si = ps[(size_t)i * 4 + 3], ck = ps[(size_t)k * 4 + 2], sk = ps[(size_t)k * 4 + 3];
-    const size_t S = tb.slots;
     T acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int q = sptr[b]; q < sptr[b + 1]; ++q) {
         const size_t e1 = slot_i[q], e2 = slot_k[q];
         const uint32_t l = tb.idx[e1];
-        const auto ai = ld2<T>(tb.dyn + 2 * e1), pi = ld2<T>(tb.dyn + 2 * (S + e1));
-        const auto ak = ld2<T>(tb.dyn + 2 * e2), pk = ld2<T>(tb.dyn + 2 * (S + e2));
-        const T a0i = ai.x, a1i = ai.y, vi0 = pi.y, vi1 = -pi.x;
-        const T a0k = ak.x, a1k = ak.y, vk0 = pk.y, vk1 = -pk.x;
+        const LmSlot<T> di = lm_slot<T>(tb, e1), dk = lm_slot<T>(tb, e2);
+        const T a0i = di.a0, a1i = di.a1, vi0 = di.ppy, vi1 = -di.ppx;
+        const T a0k = dk.a0, a1k = dk.a1, vk0 = dk.ppy, vk1 = -dk.ppx;
         const T* lr = lmrec + (size_t)l * kLmRec;
         const T nxx = lr[2], nxy = lr[3], nyy = lr[4];
         const T m00 = nxx * ck + nxy * sk, m01 = nxy * ck - nxx * sk, m10 = nxy * ck + nyy * sk, m11 = nyy * ck - nxy * sk;
@@ -140,10 +138,8 @@ __global__ __launch_bounds__(kBlock) void k_schur_blocks(int nnz, const int* __r
     for (int q = optr[b]; q < optr[b + 1]; ++q) {
         const size_t e = oslot[q];
         if (odom_analytic) {      // general pose-pose slots (tsgo_math.h): the slot's own row block [[-K, c], [r^T, -kappa]]
-            T h[PP_PLANES];
-#pragma unroll
-            for (int m = 0; m < PP_PLANES; ++m) h[m] = od_dyn[(size_t)m * od_slots + e];
-            d[0] -= h[PP_K00]; d[1] -= h[PP_K01]; d[3] -= h[PP_K01]; d[4] -= h[PP_K11]; d[2] += h[PP_C0]; d[5] += h[PP_C1]; d[6] += h[PP_R0]; d[7] += h[PP_R1]; d[8] -= h[PP_KAPPA];
+            const PairSlot<T> h = pair_slot<T>(od_dyn, od_slots, e);
+            d[0] -= h.v[PP_K00]; d[1] -= h.v[PP_K01]; d[3] -= h.v[PP_K01]; d[4] -= h.v[PP_K11]; d[2] += h.v[PP_C0]; d[5] += h.v[PP_C1]; d[6] += h.v[PP_R0]; d[7] += h.v[PP_R1]; d[8] -= h.v[PP_KAPPA];
         } else { d[0] -= od_dyn[e]; d[4] -= od_dyn[od_slots + e]; d[8] -= od_dyn[2 * od_slots + e]; }
     }
 #pragma unroll

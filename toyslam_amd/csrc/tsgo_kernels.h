@@ -74,6 +74,64 @@ template <typename T> struct Table {       // one SELL table on the device
 // depends on the placement guess, never correctness.
 __device__ __forceinline__ int xcd_block() { return (int)((blockIdx.x % 8u) * (gridDim.x / 8u) + blockIdx.x / 8u); }
 
+// ---- accessors of the table kernels: values in, values out -------------------------------------------------------------------------
+// Where a thread stands: its slice (through the XCD map when the table asks for it), its lane, the vertex its group of G lanes works on,
+// whether the slice exists, and whether the lane is the group's head (the one that writes the vertex's result and folds its priors).
+struct Walk { int slice, lane, vertex, live, head; };
+template <int G, typename T> __device__ __forceinline__ Walk walk_of(const Table<T>& tb) {
+    Walk w;
+    w.slice = (tb.xcd ? xcd_block() : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+    w.live = w.slice < tb.n_slices;
+    w.lane = threadIdx.x & 63;
+    w.vertex = w.slice * (64 / G) + w.lane / G;
+    w.head = (w.lane % G) == 0;
+    return w;
+}
+
+// LM slot k: what was measured (static planes), what the linearisation left (dyn, or dyn32 under LOW), and the store of both copies.
+template <typename T> struct LmMeas { T zx, zy, w0, w1; };
+template <typename T> __device__ __forceinline__ LmMeas<T> lm_meas(const Table<T>& tb, size_t k) {
+    const auto zz = ld2<T>(tb.st + 2 * k), ww = ld2<T>(tb.st + 2 * (tb.slots + k));
+    return {zz.x, zz.y, ww.x, ww.y};
+}
+template <typename T> struct LmSlot { T a0, a1, ppx, ppy; };
+template <typename T, int LOW = 0> __device__ __forceinline__ LmSlot<T> lm_slot(const Table<T>& tb, size_t k) {
+    if (LOW) { const float4 f = tb.dyn32[k]; return {f.x, f.y, f.z, f.w}; }
+    const auto aa = ld2<T>(tb.dyn + 2 * k), pp = ld2<T>(tb.dyn + 2 * (tb.slots + k));
+    return {aa.x, aa.y, pp.x, pp.y};
+}
+template <typename T> __device__ __forceinline__ void lm_slot_store(const Table<T>& tb, size_t k, const LmLin<T>& o) {
+    st2<T>(tb.dyn + 2 * k, o.a0, o.a1); st2<T>(tb.dyn + 2 * (tb.slots + k), o.ppx, o.ppy);
+    tb.dyn32[k] = make_float4((float)o.a0, (float)o.a1, (float)o.ppx, (float)o.ppy);
+}
+
+// Pose-pose slot k: the nine static planes (mi, w; a virtual landmark slot keeps its two points and two weights there) and the
+// PP_PLANES dynamic planes of the general form (tsgo_math.h).
+template <typename T> struct OdomMeas { T mi[6], w[3]; };
+template <typename T> __device__ __forceinline__ OdomMeas<T> odom_meas(const Table<T>& od, size_t k) {
+    OdomMeas<T> o;
+#pragma unroll
+    for (int m = 0; m < 6; ++m) o.mi[m] = od.st[(size_t)m * od.slots + k];
+#pragma unroll
+    for (int m = 0; m < 3; ++m) o.w[m] = od.st[(size_t)(6 + m) * od.slots + k];
+    return o;
+}
+template <typename T> __device__ __forceinline__ PairSlot<T> pair_slot(const T* dyn, size_t S, size_t k) {
+    PairSlot<T> h;
+#pragma unroll
+    for (int m = 0; m < PP_PLANES; ++m) h.v[m] = dyn[(size_t)m * S + k];
+    return h;
+}
+
+// Pose record i of zc (or of its f32 copy zc32 under LOW: 32 B instead of 64 gathered through L2): the vector and the pose's cos / sin.
+template <typename T> struct PoseVec { T v0, v1, v2, c, s; };
+template <typename T, int LOW> __device__ __forceinline__ PoseVec<T> pose_vec(const T* zc, const float* zc32, size_t i) {
+    if (LOW) { const float* zr = zc32 + i * kPoseRec; const float4 q = *reinterpret_cast<const float4*>(zr); return {q.x, q.y, q.z, q.w, zr[4]}; }
+    const T* zr = zc + i * kPoseRec;
+    const auto z01 = ld2<T>(zr), z23 = ld2<T>(zr + 2);
+    return {z01.x, z01.y, z23.x, z23.y, zr[4]};
+}
+
 template <typename T, int G> __device__ __forceinline__ T group_sum(T v) {
 #pragma unroll
     for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m);
@@ -136,17 +194,12 @@ template <typename T> struct PriorArgs { const uint32_t* off; const T* rec; T* l
 // H_pp += [[R_m diag(a0, a1) R_m^T, 0], [0, a2]] (h00 h01 h11 h22), b_p -= J^T diag(a) e (b0 b1 b2); returns rho.
 template <typename T> __device__ __forceinline__ T pose_prior_fold(const T* q, T x, T y, T c, T s, T& h00, T& h01, T& h11, T& h22, T& b0, T& b1, T& b2) {
     const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C), w01 = ld2<T>(q + PRI_W0);
-    const T w2 = q[PRI_W2];
-    const T cm = cs.x, sm = cs.y, dx = x - m01.x, dy = y - m01.y;
-    const T e0 = cm * dx + sm * dy, e1 = cm * dy - sm * dx;
-    const T et = atan2(s * cm - c * sm, c * cm + s * sm);
-    T rho, hw;
-    huber<T>(w01.x * e0 * e0 + w01.y * e1 * e1 + w2 * et * et, rho, hw);
-    const T a0 = hw * w01.x, a1 = hw * w01.y, a2 = hw * w2;
-    h00 += a0 * cm * cm + a1 * sm * sm; h01 += (a0 - a1) * cm * sm; h11 += a0 * sm * sm + a1 * cm * cm; h22 += a2;
-    const T f0 = a0 * e0, f1 = a1 * e1;
-    b0 -= cm * f0 - sm * f1; b1 -= sm * f0 + cm * f1; b2 -= a2 * et;
-    return rho;
+    const T cm = cs.x, sm = cs.y;
+    const PosePriorLin<T> o = pose_prior_linearize<T>(m01.x, m01.y, cm, sm, w01.x, w01.y, q[PRI_W2], x, y, c, s);
+    h00 += o.a0 * cm * cm + o.a1 * sm * sm; h01 += (o.a0 - o.a1) * cm * sm; h11 += o.a0 * sm * sm + o.a1 * cm * cm; h22 += o.a2;
+    const T f0 = o.a0 * o.e0, f1 = o.a1 * o.e1;
+    b0 -= cm * f0 - sm * f1; b1 -= sm * f0 + cm * f1; b2 -= o.a2 * o.et;
+    return o.rho;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -159,49 +212,40 @@ template <typename T, int G, int PRI = 0>
 __global__ __launch_bounds__(kBlock) void k_lin_lm(Table<T> tb, const T* __restrict__ ps, T* __restrict__ lmrec,
                                                    const T* __restrict__ gauge_l, T* __restrict__ ninv, T lambda, int zero_fixed,
                                                    const PriorArgs<T> pa = PriorArgs<T>{nullptr, nullptr, nullptr, 0}) {
-    const int slice = (tb.xcd ? xcd_block() : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
-    const bool live = slice < tb.n_slices;
+    const Walk wk = walk_of<G>(tb);
+    const int slice = wk.slice, lane = wk.lane, l = wk.vertex, live = wk.live;
     if (!PRI && !live) return;
-    const int lane = threadIdx.x & 63;
-    constexpr int VPS = 64 / G;
-    const int l = slice * VPS + lane / G;
     const bool valid = l < tb.n_vertices;      // (false on every lane of a wave past the last slice)
     const int lc = valid ? l : tb.n_vertices - 1;
     const T lx = lmrec[(size_t)lc * kLmRec], ly = lmrec[(size_t)lc * kLmRec + 1];
     T dxx = 0, dxy = 0, dyy = 0, g0 = 0, g1 = 0;
     T chi = 0;
-    const size_t S = tb.slots;
     const uint32_t r0 = live ? tb.row_off[slice] : 0u, r1 = live ? tb.row_off[slice + 1] : 0u;
     for (uint32_t row = r0; row < r1; ++row) {
         const size_t k = (size_t)row * 64 + lane;
         const uint32_t i = tb.idx[k];
-        const auto zz = ld2<T>(tb.st + 2 * k), ww = ld2<T>(tb.st + 2 * (S + k));
-        const T zx = zz.x, zy = zz.y, w0 = ww.x, w1 = ww.y;
+        const LmMeas<T> z = lm_meas<T>(tb, k);
         const T* q = ps + (size_t)i * 4;
         const auto q01 = ld2<T>(q), q23 = ld2<T>(q + 2);
         const T x = q01.x, y = q01.y, c = q23.x, s = q23.y;
-        const LmLin<T> o = lm_linearize<T>(x, y, c, s, lx, ly, zx, zy, w0, w1);
-        st2<T>(tb.dyn + 2 * k, o.a0, o.a1); st2<T>(tb.dyn + 2 * (S + k), o.ppx, o.ppy);
-        tb.dyn32[k] = make_float4((float)o.a0, (float)o.a1, (float)o.ppx, (float)o.ppy);
+        const LmLin<T> o = lm_linearize<T>(x, y, c, s, lx, ly, z.zx, z.zy, z.w0, z.w1);
+        lm_slot_store<T>(tb, k, o);
         dxx += o.a0 * c * c + o.a1 * s * s; dxy += (o.a0 - o.a1) * c * s; dyy += o.a0 * s * s + o.a1 * c * c;
         const T f0 = o.a0 * o.e0, f1 = o.a1 * o.e1;
         g0 -= c * f0 - s * f1; g1 -= s * f0 + c * f1;
     }
     dxx = group_sum<T, G>(dxx); dxy = group_sum<T, G>(dxy); dyy = group_sum<T, G>(dyy);
     g0 = group_sum<T, G>(g0); g1 = group_sum<T, G>(g1);
-    if (valid && (lane % G) == 0) {
+    if (valid && wk.head) {
         // lambda: the LM-style damping of the reference's Python optimizer (H + lambda I, graph_optimizer.py:42), 0 under the
         // cpu/eigen rules; zero_fixed: that optimizer also zeroes b at fixed vertices (:150), OptimizerCpu.h does not
         if constexpr (PRI != 0) {
             for (uint32_t k = pa.off[l]; k < pa.off[l + 1]; ++k) {
                 const T* q = pa.rec + (size_t)k * PRI_LM_REC;
                 const auto m = ld2<T>(q + PRL_MX), w = ld2<T>(q + PRL_W0);
-                const T e0 = lx - m.x, e1 = ly - m.y;
-                T rho, hw;
-                huber<T>(w.x * e0 * e0 + w.y * e1 * e1, rho, hw);
-                const T a0 = hw * w.x, a1 = hw * w.y;
-                dxx += a0; dyy += a1; g0 -= a0 * e0; g1 -= a1 * e1;
-                chi += rho;
+                const LmPriorLin<T> o = lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly);
+                dxx += o.a0; dyy += o.a1; g0 -= o.a0 * o.e0; g1 -= o.a1 * o.e1;
+                chi += o.rho;
             }
         }
         const T ga = gauge_l[l];
@@ -237,12 +281,9 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, c
                                                      T* __restrict__ chi_part, T lambda, int zero_fixed, int odom_analytic = 0,
                                                      const PriorArgs<T> pa = PriorArgs<T>{nullptr, nullptr, nullptr, 0}) {
     __shared__ T red[kWavesPerBlock];
-    const int slice = (tb.xcd ? xcd_block() : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
-    const bool live = slice < tb.n_slices;
-    const int lane = threadIdx.x & 63;
-    constexpr int VPS = 64 / G;
-    const int i = slice * VPS + lane / G;
-    const bool valid = live && i < tb.n_vertices;
+    const Walk wk = walk_of<G>(tb);
+    const int slice = wk.slice, lane = wk.lane, i = wk.vertex;
+    const bool live = wk.live, valid = live && i < tb.n_vertices;
     T chi = 0;
     if (live) {
         const int ic = valid ? i : tb.n_vertices - 1;
@@ -250,19 +291,16 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, c
         T sA0 = 0, sA1 = 0, sAv0 = 0, sAv1 = 0, sVV = 0, ge0 = 0, ge1 = 0, get = 0;
         T K00 = 0, K01 = 0, K11 = 0, Kv0 = 0, Kv1 = 0, vKv = 0, wu0 = 0, wu1 = 0, wut = 0;
         {
-            const size_t S = tb.slots;
             const uint32_t r0 = tb.row_off[slice], r1 = tb.row_off[slice + 1];
             for (uint32_t row = r0; row < r1; ++row) {
                 const size_t k = (size_t)row * 64 + lane;
                 const uint32_t l = tb.idx[k];
-                const auto zz = ld2<T>(tb.st + 2 * k), ww = ld2<T>(tb.st + 2 * (S + k));
-                const T zx = zz.x, zy = zz.y, w0 = ww.x, w1 = ww.y;
+                const LmMeas<T> z = lm_meas<T>(tb, k);
                 const T* lr = lmrec + (size_t)l * kLmRec;
                 const auto l01 = ld2<T>(lr), l23 = ld2<T>(lr + 2), l45 = ld2<T>(lr + 4);
                 const T lx = l01.x, ly = l01.y, nxx = l23.x, nxy = l23.y, nyy = l45.x, ux = l45.y, uy = lr[6];
-                const LmLin<T> o = lm_linearize<T>(x0, y0, c, s, lx, ly, zx, zy, w0, w1);
-                st2<T>(tb.dyn + 2 * k, o.a0, o.a1); st2<T>(tb.dyn + 2 * (S + k), o.ppx, o.ppy);
-                tb.dyn32[k] = make_float4((float)o.a0, (float)o.a1, (float)o.ppx, (float)o.ppy);
+                const LmLin<T> o = lm_linearize<T>(x0, y0, c, s, lx, ly, z.zx, z.zy, z.w0, z.w1);
+                lm_slot_store<T>(tb, k, o);
                 chi += o.rho;
                 const T v0 = o.ppy, v1 = -o.ppx;
                 sA0 += o.a0; sA1 += o.a1; sAv0 += o.a0 * v0; sAv1 += o.a1 * v1; sVV += o.a0 * v0 * v0 + o.a1 * v1 * v1;
@@ -289,15 +327,11 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, c
                 const uint32_t raw = od.idx[k];
                 const bool second = (raw & kDirMask) != 0;
                 const uint32_t j = raw & kPoseIdxMask;
-                T mi[6], w[3];
-#pragma unroll
-                for (int m = 0; m < 6; ++m) mi[m] = od.st[(size_t)m * S + k];
-#pragma unroll
-                for (int m = 0; m < 3; ++m) w[m] = od.st[(size_t)(6 + m) * S + k];
+                const OdomMeas<T> z = odom_meas<T>(od, k);
                 const T* oq = ps + (size_t)j * 4;
                 const T xj = oq[0], yj = oq[1], cj = oq[2], sj = oq[3];
                 if (OJ && (raw & kVlmMask)) {      // virtual landmark measurement: mi = (pox, poy, pnx, pny, ., .), w = (w0, w1, .)
-                    const VlmLin<T> v = vlm_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, mi[0], mi[1], mi[2], mi[3], w[0], w[1]);
+                    const VlmLin<T> v = vlm_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1]);
                     T h[PP_PLANES];
                     vlm_slot<T>(v, h);
 #pragma unroll
@@ -307,10 +341,10 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, c
                     if (!second) chi += v.rho;
                     continue;
                 }
-                const OdomLin<T> o = second ? odom_linearize<T>(xj, yj, cj, sj, x0, y0, c, s, mi, w)
-                                            : odom_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, mi, w);
+                const OdomLin<T> o = second ? odom_linearize<T>(xj, yj, cj, sj, x0, y0, c, s, z.mi, z.w)
+                                            : odom_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi, z.w);
                 if (OJ && odom_analytic) {
-                    const OdomBlocks<T> ob = second ? odom_blocks<T>(o, xj, yj, cj, sj, x0, y0, c, s, mi) : odom_blocks<T>(o, x0, y0, c, s, xj, yj, cj, sj, mi);
+                    const OdomBlocks<T> ob = second ? odom_blocks<T>(o, xj, yj, cj, sj, x0, y0, c, s, z.mi) : odom_blocks<T>(o, x0, y0, c, s, xj, yj, cj, sj, z.mi);
                     // H_12 = [[-K, 0], [g^T, -w]] at the first endpoint, its transpose at the second
                     od.dyn[(size_t)PP_K00 * S + k] = ob.k00; od.dyn[(size_t)PP_K01 * S + k] = ob.k01; od.dyn[(size_t)PP_K11 * S + k] = ob.k11;
                     od.dyn[(size_t)PP_C0 * S + k] = second ? ob.g0 : T(0); od.dyn[(size_t)PP_C1 * S + k] = second ? ob.g1 : T(0);
@@ -339,7 +373,7 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, c
         GS(od0); GS(od1); GS(od2); GS(og0); GS(og1); GS(og2);
         if (OJ) { GS(od01); GS(od02); GS(od12); }
 #undef GS
-        if (valid && (lane % G) == 0) {
+        if (valid && wk.head) {
             // gauge and damping enter once: through the shard that owns the pose
             const bool own = i >= pose_first && i < pose_last;
             const T ga = own ? gauge_p[i] + lambda : T(0);
@@ -436,15 +470,11 @@ __global__ __launch_bounds__(kBlock) void k_schur_lm(Table<T> tb, const T* __res
     // the flag of a finished solve is requested here and tested after the loads that depend on the arguments alone (row bounds,
     // the vertex's inverse block) are on their way: tested first, it adds a scalar round trip in front of the first vector load
     const int done = MODE == 0 ? st->done : 0;
-    const int slice = (tb.xcd ? xcd_block() : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
-    const bool live = slice < tb.n_slices;
-    const int lane = threadIdx.x & 63;
-    constexpr int VPS = 64 / G;
-    const int l = slice * VPS + lane / G;
+    const Walk wk = walk_of<G>(tb);
+    const int slice = wk.slice, lane = wk.lane, l = wk.vertex;
     T nrm = 0, prd = 0;
-    if (live) {
+    if (wk.live) {
         T acc0 = 0, acc1 = 0;
-        const size_t S = tb.slots;
         const uint32_t r0 = tb.row_off[slice], r1 = tb.row_off[slice + 1];
         // the inverse block this vertex needs at the very end is requested first: its latency hides behind the rows
         const int lq = (l < tb.n_vertices) ? l : tb.n_vertices - 1;
@@ -457,42 +487,29 @@ __global__ __launch_bounds__(kBlock) void k_schur_lm(Table<T> tb, const T* __res
         // parallelism is what buys time.  Rows past the end are clamped (in bounds) and masked out of the sums.
         constexpr int UB = (G >= 4) ? 2 : 4;
         for (uint32_t base = r0; base < r1; base += UB) {
-            uint32_t i[UB]; T a0[UB], a1[UB], ppx[UB], ppy[UB];
+            uint32_t i[UB]; LmSlot<T> d[UB];
 #pragma unroll
             for (int u = 0; u < UB; ++u) {
                 const uint32_t row = min(base + u, r1 - 1);
                 const size_t k = (size_t)row * 64 + lane;
                 i[u] = tb.idx[k];
-                if (LOW) { const float4 f = tb.dyn32[k]; a0[u] = f.x; a1[u] = f.y; ppx[u] = f.z; ppy[u] = f.w; }
-                else {
-                    const auto aa = ld2<T>(tb.dyn + 2 * k), pp = ld2<T>(tb.dyn + 2 * (S + k));
-                    a0[u] = aa.x; a1[u] = aa.y; ppx[u] = pp.x; ppy[u] = pp.y;
-                }
+                d[u] = lm_slot<T, LOW>(tb, k);
             }
-            T v0[UB], v1[UB], v2[UB], c[UB], s[UB];
+            PoseVec<T> z[UB];
 #pragma unroll
-            for (int u = 0; u < UB; ++u) {
-                if (LOW) {      // the f32 copy of the pose records (32 B each): half the bytes gathered through L2
-                    const float* zr = zc32 + (size_t)i[u] * kPoseRec;
-                    const float4 q = *reinterpret_cast<const float4*>(zr);
-                    v0[u] = q.x; v1[u] = q.y; v2[u] = q.z; c[u] = q.w; s[u] = zr[4];
-                } else {
-                    const T* zr = zc + (size_t)i[u] * kPoseRec;
-                    const auto z01 = ld2<T>(zr), z23 = ld2<T>(zr + 2);
-                    v0[u] = z01.x; v1[u] = z01.y; v2[u] = z23.x; c[u] = z23.y; s[u] = zr[4];
-                }
-            }
+            for (int u = 0; u < UB; ++u) z[u] = pose_vec<T, LOW>(zc, zc32, i[u]);
 #pragma unroll
             for (int u = 0; u < UB; ++u) {
                 if (base + u < r1) {
-                    const T vt0 = c[u] * v0[u] + s[u] * v1[u], vt1 = c[u] * v1[u] - s[u] * v0[u];
-                    const T m0 = a0[u] * (ppy[u] * v2[u] - vt0), m1 = a1[u] * (-vt1 - ppx[u] * v2[u]);
-                    acc0 += c[u] * m0 - s[u] * m1; acc1 += s[u] * m0 + c[u] * m1;
+                    const T c = z[u].c, s = z[u].s;
+                    const T vt0 = c * z[u].v0 + s * z[u].v1, vt1 = c * z[u].v1 - s * z[u].v0;
+                    const T m0 = d[u].a0 * (d[u].ppy * z[u].v2 - vt0), m1 = d[u].a1 * (-vt1 - d[u].ppx * z[u].v2);
+                    acc0 += c * m0 - s * m1; acc1 += s * m0 + c * m1;
                 }
             }
         }
         acc0 = group_sum<T, G>(acc0); acc1 = group_sum<T, G>(acc1);
-        if (l < tb.n_vertices && (lane % G) == 0) {
+        if (l < tb.n_vertices && wk.head) {
             T* lr = lmrec + (size_t)l * kLmRec;
             const T ixx = n01.x, ixy = n01.y, iyy = n2;
             const T t0 = ixx * acc0 + ixy * acc1, t1 = ixy * acc0 + iyy * acc1;
@@ -544,24 +561,20 @@ __global__ __launch_bounds__(kBlock) void k_schur_pose(Table<T> tb, Table<T> od,
     // its operands from the f32 copies (zc32), so writing the f64 records it does not read is no race; the f32 copies are rewritten by
     // k_cg_step before anything reads them again.
     const int done = st->done;      // requested now, tested after the first argument-only loads are in flight (see k_schur_lm)
-    const int slice = (tb.xcd ? xcd_block() : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
-    const bool live = slice < tb.n_slices;
-    const int lane = threadIdx.x & 63;
-    constexpr int VPS = 64 / G;
-    const int i = slice * VPS + lane / G;
+    const Walk wk = walk_of<G>(tb);
+    const int slice = wk.slice, lane = wk.lane, i = wk.vertex, live = wk.live;
     T dot = 0, rz = 0;
     if (!live && done) return;      // workgroup-uniform: done is, and the other waves of the group leave below
     if (live) {
         const bool valid = i < tb.n_vertices;
         const int ic = valid ? i : tb.n_vertices - 1;
-        T v0, v1, v2, c, s;
-        if (LOW) { const float* zr = zc32 + (size_t)ic * kPoseRec; v0 = zr[0]; v1 = zr[1]; v2 = zr[2]; c = zr[3]; s = zr[4]; }
-        else { const T* zr = zc + (size_t)ic * kPoseRec; v0 = zr[0]; v1 = zr[1]; v2 = zr[2]; c = zr[3]; s = zr[4]; }
+        const PoseVec<T> zi = pose_vec<T, LOW>(zc, zc32, ic);
+        T v0 = zi.v0, v1 = zi.v1, v2 = zi.v2, c = zi.c, s = zi.s;
         const uint32_t lm_r0 = tb.row_off[slice], lm_r1 = tb.row_off[slice + 1];
         issue_before_exit(v0);
         if (done) return;
         // the pose's own diagonal block and residual entry are used at the very end: asked for first
-        const bool head = valid && (lane % G) == 0;
+        const bool head = valid && wk.head;
         const bool own = head && i >= pose_first && i < pose_last;
         T dpi[6] = {0, 0, 0, 0, 0, 0}, rv0 = 0, rv1 = 0, rv2 = 0;
         if (own) {
@@ -581,23 +594,17 @@ __global__ __launch_bounds__(kBlock) void k_schur_pose(Table<T> tb, Table<T> od,
         }
         T acc0 = 0, acc1 = 0, acc2 = 0;
         {
-            const size_t S = tb.slots;
             const uint32_t r0 = lm_r0, r1 = lm_r1;
 #pragma unroll 2
             for (uint32_t row = r0; row < r1; ++row) {
                 const size_t k = (size_t)row * 64 + lane;
                 const uint32_t l = tb.idx[k];
-                T a0, a1, ppx, ppy;
-                if (LOW) { const float4 f = tb.dyn32[k]; a0 = f.x; a1 = f.y; ppx = f.z; ppy = f.w; }
-                else {
-                    const auto aa = ld2<T>(tb.dyn + 2 * k), pp = ld2<T>(tb.dyn + 2 * (S + k));
-                    a0 = aa.x; a1 = aa.y; ppx = pp.x; ppy = pp.y;
-                }
+                const LmSlot<T> d = lm_slot<T, LOW>(tb, k);
                 T tx, ty;
                 if (LOW) { const float2 txy = *reinterpret_cast<const float2*>(t32 + (size_t)l * 2); tx = txy.x; ty = txy.y; }
                 else { const auto txy = ld2<T>(t + (size_t)l * 2); tx = txy.x; ty = txy.y; }
-                const T t0 = a0 * (c * tx + s * ty), t1 = a1 * (c * ty - s * tx);
-                acc0 += t0; acc1 += t1; acc2 += t0 * ppy - t1 * ppx;
+                const T t0 = d.a0 * (c * tx + s * ty), t1 = d.a1 * (c * ty - s * tx);
+                acc0 += t0; acc1 += t1; acc2 += t0 * d.ppy - t1 * d.ppx;
             }
         }
         T o0 = 0, o1 = 0, o2 = 0;
@@ -612,10 +619,8 @@ __global__ __launch_bounds__(kBlock) void k_schur_pose(Table<T> tb, Table<T> od,
                 if (LOW) { const float* q = zc32 + (size_t)j * kPoseRec; zj[0] = q[0]; zj[1] = q[1]; zj[2] = q[2]; }
                 else { const T* q = zc + (size_t)j * kPoseRec; zj[0] = q[0]; zj[1] = q[1]; zj[2] = q[2]; }
                 if (OJ) {           // the slot's own row block H_pn = [[-K, c], [r^T, -kappa]] (tsgo_math.h), whatever edge it came from
-                    T h[PP_PLANES];
-#pragma unroll
-                    for (int m = 0; m < PP_PLANES; ++m) h[m] = od.dyn[(size_t)m * S + k];
-                    pair_apply<T>(h, zj[0], zj[1], zj[2], o0, o1, o2);
+                    const PairSlot<T> h = pair_slot<T>(od.dyn, S, k);
+                    pair_apply<T>(h.v, zj[0], zj[1], zj[2], o0, o1, o2);
                 } else { o0 -= od.dyn[k] * zj[0]; o1 -= od.dyn[S + k] * zj[1]; o2 -= od.dyn[2 * S + k] * zj[2]; }
             }
         }

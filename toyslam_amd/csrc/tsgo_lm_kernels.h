@@ -9,97 +9,70 @@
 
 namespace tsgo {
 
-// rho of one pose prior: the residual and Huber of pose_prior_fold (tsgo_kernels.h), nothing else of it.
-template <typename T> __device__ __forceinline__ T pose_prior_rho(const T* q, T x, T y, T c, T s) {
-    const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C), w01 = ld2<T>(q + PRI_W0);
-    const T w2 = q[PRI_W2];
-    const T cm = cs.x, sm = cs.y, dx = x - m01.x, dy = y - m01.y;
-    const T e0 = cm * dx + sm * dy, e1 = cm * dy - sm * dx;
-    const T et = atan2(s * cm - c * sm, c * cm + s * sm);
-    T rho, hw;
-    huber<T>(w01.x * e0 * e0 + w01.y * e1 * e1 + w2 * et * et, rho, hw);
-    return rho;
-}
-
 // chi^2 of the landmark priors (edge type 4), one partial per workgroup into pa.lm_chi: the landmark -> lane -> workgroup map and the order
 // of the sums are k_lin_lm<.., 1>'s, so that k_chi2 below folds the same partials the linearisation would.  Graphs with priors only.
 template <typename T, int G>
 __global__ __launch_bounds__(kBlock) void k_chi2_lm_prior(Table<T> tb, const T* __restrict__ lmrec, const PriorArgs<T> pa) {
     __shared__ T red[kWavesPerBlock];
-    const int slice = (tb.xcd ? xcd_block() : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    constexpr int VPS = 64 / G;
-    const int l = slice * VPS + lane / G;
+    const Walk wk = walk_of<G>(tb);
+    const int l = wk.vertex;
     T chi = 0;
-    if (slice < tb.n_slices && l < tb.n_vertices && (lane % G) == 0) {
+    if (wk.live && l < tb.n_vertices && wk.head) {
         const T lx = lmrec[(size_t)l * kLmRec], ly = lmrec[(size_t)l * kLmRec + 1];
         for (uint32_t k = pa.off[l]; k < pa.off[l + 1]; ++k) {
             const T* q = pa.rec + (size_t)k * PRI_LM_REC;
             const auto m = ld2<T>(q + PRL_MX), w = ld2<T>(q + PRL_W0);
-            const T e0 = lx - m.x, e1 = ly - m.y;
-            T rho, hw;
-            huber<T>(w.x * e0 * e0 + w.y * e1 * e1, rho, hw);
-            chi += rho;
+            chi += lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly).rho;
         }
     }
     const T total = block_sum<T>(chi, red);
     if (threadIdx.x == 0) pa.lm_chi[blockIdx.x] = total;
 }
 
-// Robustified chi^2 at the current estimates: the walk of k_lin_pose over the pose-major LM table and the pose-pose table with the same
-// per-edge functions (lm_linearize, odom_linearize, vlm_linearize, huber), the same lane and row order and the same folding of the priors,
-// so that the chi^2 of an accepted trial point IS the chi^2 the next linearisation reports — but it reads estimates, measurements and
-// weights only (16 B of a landmark record instead of 56), forms no Jacobian product and writes one number per workgroup.
-// Every edge once: pose-pose slots are listed at both endpoints and counted at the first.  OJ = 1: the table may hold virtual landmark
-// slots (kVlmMask); the ODOM residual does not depend on which Jacobians the linearisation uses.
+// Robustified chi^2 at the current estimates, without a linearisation: estimates, measurements and weights are read (16 B of a landmark
+// record instead of 56), no Jacobian product is formed and one number per workgroup is written.  The chi^2 of an accepted trial point has
+// to BE the chi^2 the next linearisation (k_lin_lm, k_lin_pose) reports.  By construction: the walk position (walk_of), the slot loads
+// (lm_meas, odom_meas) and the per-edge arithmetic (lm_linearize, odom_linearize, vlm_linearize, pose_prior_linearize,
+// lm_prior_linearize) are the ones k_lin_pose calls.  Still a convention kept by hand in both kernels: rows in table order, a pose-pose
+// slot (listed at both endpoints) counted at the edge's first, a vertex's priors folded by its head lane after its rows, the landmark
+// priors' partials added by workgroup 0.  OJ = 1: virtual landmark slots (kVlmMask); the ODOM residual is the same under either Jacobians.
 template <typename T, int G, int OJ = 0, int PRI = 0>
 __global__ __launch_bounds__(kBlock) void k_chi2(Table<T> tb, Table<T> od, const T* __restrict__ ps, const T* __restrict__ lmrec,
                                                  T* __restrict__ chi_part, const PriorArgs<T> pa) {
     __shared__ T red[kWavesPerBlock];
-    const int slice = (tb.xcd ? xcd_block() : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
-    const bool live = slice < tb.n_slices;
-    const int lane = threadIdx.x & 63;
-    constexpr int VPS = 64 / G;
-    const int i = slice * VPS + lane / G;
-    const bool valid = live && i < tb.n_vertices;
+    const Walk wk = walk_of<G>(tb);
+    const int slice = wk.slice, lane = wk.lane, i = wk.vertex;
+    const bool valid = wk.live && i < tb.n_vertices;
     T chi = 0;
-    if (live) {
+    if (wk.live) {
         const int ic = valid ? i : tb.n_vertices - 1;
         const auto q01 = ld2<T>(ps + (size_t)ic * 4), q23 = ld2<T>(ps + (size_t)ic * 4 + 2);
         const T x0 = q01.x, y0 = q01.y, c = q23.x, s = q23.y;
-        {
-            const size_t S = tb.slots;
-            const uint32_t r0 = tb.row_off[slice], r1 = tb.row_off[slice + 1];
 #pragma unroll 2
-            for (uint32_t row = r0; row < r1; ++row) {
-                const size_t k = (size_t)row * 64 + lane;
-                const uint32_t l = tb.idx[k];
-                const auto zz = ld2<T>(tb.st + 2 * k), ww = ld2<T>(tb.st + 2 * (S + k));
-                const auto l01 = ld2<T>(lmrec + (size_t)l * kLmRec);
-                chi += lm_linearize<T>(x0, y0, c, s, l01.x, l01.y, zz.x, zz.y, ww.x, ww.y).rho;
-            }
+        for (uint32_t row = tb.row_off[slice], r1 = tb.row_off[slice + 1]; row < r1; ++row) {
+            const size_t k = (size_t)row * 64 + lane;
+            const uint32_t l = tb.idx[k];
+            const LmMeas<T> z = lm_meas<T>(tb, k);
+            const auto l01 = ld2<T>(lmrec + (size_t)l * kLmRec);
+            chi += lm_linearize<T>(x0, y0, c, s, l01.x, l01.y, z.zx, z.zy, z.w0, z.w1).rho;
         }
-        {
-            const size_t S = od.slots;
-            const uint32_t r0 = od.row_off[slice], r1 = od.row_off[slice + 1];
-            for (uint32_t row = r0; row < r1; ++row) {
-                const size_t k = (size_t)row * 64 + lane;
-                const uint32_t raw = od.idx[k];
-                if (raw & kDirMask) continue;      // the edge's second endpoint: counted at the first
-                const uint32_t j = raw & kPoseIdxMask;
-                T mi[6], w[3];
-#pragma unroll
-                for (int m = 0; m < 6; ++m) mi[m] = od.st[(size_t)m * S + k];
-#pragma unroll
-                for (int m = 0; m < 3; ++m) w[m] = od.st[(size_t)(6 + m) * S + k];
-                const auto j01 = ld2<T>(ps + (size_t)j * 4), j23 = ld2<T>(ps + (size_t)j * 4 + 2);
-                if (OJ && (raw & kVlmMask)) chi += vlm_linearize<T>(x0, y0, c, s, j01.x, j01.y, j23.x, j23.y, mi[0], mi[1], mi[2], mi[3], w[0], w[1]).rho;
-                else chi += odom_linearize<T>(x0, y0, c, s, j01.x, j01.y, j23.x, j23.y, mi, w).rho;      // a padding slot has w = 0: rho = 0
-            }
+        for (uint32_t row = od.row_off[slice], r1 = od.row_off[slice + 1]; row < r1; ++row) {
+            const size_t k = (size_t)row * 64 + lane;
+            const uint32_t raw = od.idx[k];
+            if (raw & kDirMask) continue;      // the edge's second endpoint: counted at the first
+            const uint32_t j = raw & kPoseIdxMask;
+            const OdomMeas<T> z = odom_meas<T>(od, k);
+            const auto j01 = ld2<T>(ps + (size_t)j * 4), j23 = ld2<T>(ps + (size_t)j * 4 + 2);
+            if (OJ && (raw & kVlmMask)) chi += vlm_linearize<T>(x0, y0, c, s, j01.x, j01.y, j23.x, j23.y, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1]).rho;
+            else chi += odom_linearize<T>(x0, y0, c, s, j01.x, j01.y, j23.x, j23.y, z.mi, z.w).rho;      // a padding slot has w = 0: rho = 0
         }
         if constexpr (PRI != 0) {
-            if (valid && (lane % G) == 0)
-                for (uint32_t k = pa.off[i]; k < pa.off[i + 1]; ++k) chi += pose_prior_rho<T>(pa.rec + (size_t)k * PRI_POSE_REC, x0, y0, c, s);
+            if (valid && wk.head)
+                for (uint32_t k = pa.off[i]; k < pa.off[i + 1]; ++k) {
+                    const T* q = pa.rec + (size_t)k * PRI_POSE_REC;
+                    const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C), w01 = ld2<T>(q + PRI_W0);
+                    chi += pose_prior_linearize<T>(m01.x, m01.y, cs.x, cs.y, w01.x, w01.y, q[PRI_W2], x0, y0, c, s).rho;
+                }
         }
     }
     if constexpr (PRI != 0) {

@@ -49,30 +49,28 @@ template <typename T, int G, int NV>
 __global__ __launch_bounds__(kBlock) void k_mb_schur_lm(Table<T> tb, const T* __restrict__ v, const T* __restrict__ ps, const T* __restrict__ ninv,
                                                         T* __restrict__ t, const int* __restrict__ stop) {
     if (*stop) return;
-    const int slice = (tb.xcd ? xcd_block() : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
-    if (slice >= tb.n_slices) return;
-    const int lane = threadIdx.x & 63;
-    const int l = slice * (64 / G) + lane / G;
-    const size_t S = tb.slots;
+    const Walk wk = walk_of<G>(tb);
+    if (!wk.live) return;
+    const int slice = wk.slice, lane = wk.lane, l = wk.vertex;
     T acc[NV][2];
 #pragma unroll
     for (int c = 0; c < NV; ++c) { acc[c][0] = 0; acc[c][1] = 0; }
     for (uint32_t row = tb.row_off[slice]; row < tb.row_off[slice + 1]; ++row) {
         const size_t k = (size_t)row * 64 + lane;
         const uint32_t i = tb.idx[k];
-        const auto aa = ld2<T>(tb.dyn + 2 * k), pp = ld2<T>(tb.dyn + 2 * (S + k));
+        const LmSlot<T> d = lm_slot<T>(tb, k);
         const auto cs = ld2<T>(ps + (size_t)i * 4 + 2);
         const T* vi = v + (size_t)i * NV * 3;
 #pragma unroll
         for (int c = 0; c < NV; ++c) {
             T o0, o1;
-            wt_apply<T>(aa.x, aa.y, pp.x, pp.y, cs.x, cs.y, vi[3 * c], vi[3 * c + 1], vi[3 * c + 2], o0, o1);
+            wt_apply<T>(d.a0, d.a1, d.ppx, d.ppy, cs.x, cs.y, vi[3 * c], vi[3 * c + 1], vi[3 * c + 2], o0, o1);
             acc[c][0] += o0; acc[c][1] += o1;
         }
     }
 #pragma unroll
     for (int c = 0; c < NV; ++c) { acc[c][0] = group_sum<T, G>(acc[c][0]); acc[c][1] = group_sum<T, G>(acc[c][1]); }
-    if (l < tb.n_vertices && (lane % G) == 0) {
+    if (l < tb.n_vertices && wk.head) {
         const T ixx = ninv[(size_t)l * kNinvRec], ixy = ninv[(size_t)l * kNinvRec + 1], iyy = ninv[(size_t)l * kNinvRec + 2];
         T* tl = t + (size_t)l * NV * 2;
 #pragma unroll
@@ -89,33 +87,30 @@ __global__ __launch_bounds__(kBlock) void k_mb_schur_pose(Table<T> tb, Table<T> 
                                                           const T* __restrict__ rvec, T* __restrict__ dot_part, const int* __restrict__ stop) {
     __shared__ T red[kWavesPerBlock * NV];
     if (*stop) return;      // workgroup-uniform
-    const int slice = (tb.xcd ? xcd_block() : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
-    const bool live = slice < tb.n_slices;
-    const int lane = threadIdx.x & 63;
-    const int i = slice * (64 / G) + lane / G;
+    const Walk wk = walk_of<G>(tb);
+    const int slice = wk.slice, lane = wk.lane, i = wk.vertex;
     T o[NV][3];
 #pragma unroll
     for (int c = 0; c < NV; ++c) { o[c][0] = 0; o[c][1] = 0; o[c][2] = 0; }
     T dot[NV];
 #pragma unroll
     for (int c = 0; c < NV; ++c) dot[c] = 0;
-    if (live) {
+    if (wk.live) {
         const bool valid = i < tb.n_vertices;
         const int ic = valid ? i : tb.n_vertices - 1;
         const auto cs = ld2<T>(ps + (size_t)ic * 4 + 2);
         const T c0 = cs.x, s0 = cs.y;
         {
-            const size_t S = tb.slots;
             for (uint32_t row = tb.row_off[slice]; row < tb.row_off[slice + 1]; ++row) {
                 const size_t k = (size_t)row * 64 + lane;
                 const uint32_t l = tb.idx[k];
-                const auto aa = ld2<T>(tb.dyn + 2 * k), pp = ld2<T>(tb.dyn + 2 * (S + k));
+                const LmSlot<T> d = lm_slot<T>(tb, k);
                 const T* tl = t + (size_t)l * NV * 2;
 #pragma unroll
                 for (int c = 0; c < NV; ++c) {
                     const T tx = tl[2 * c], ty = tl[2 * c + 1];
-                    const T t0 = aa.x * (c0 * tx + s0 * ty), t1 = aa.y * (c0 * ty - s0 * tx);
-                    o[c][0] += c0 * t0 - s0 * t1; o[c][1] += s0 * t0 + c0 * t1; o[c][2] -= t0 * pp.y - t1 * pp.x;
+                    const T t0 = d.a0 * (c0 * tx + s0 * ty), t1 = d.a1 * (c0 * ty - s0 * tx);
+                    o[c][0] += c0 * t0 - s0 * t1; o[c][1] += s0 * t0 + c0 * t1; o[c][2] -= t0 * d.ppy - t1 * d.ppx;
                 }
             }
         }
@@ -126,11 +121,9 @@ __global__ __launch_bounds__(kBlock) void k_mb_schur_pose(Table<T> tb, Table<T> 
                 const uint32_t j = od.idx[k] & kPoseIdxMask;
                 const T* vj = v + (size_t)j * NV * 3;
                 if (OJ) {
-                    T h[PP_PLANES];
+                    const PairSlot<T> h = pair_slot<T>(od.dyn, S, k);
 #pragma unroll
-                    for (int m = 0; m < PP_PLANES; ++m) h[m] = od.dyn[(size_t)m * S + k];
-#pragma unroll
-                    for (int c = 0; c < NV; ++c) pair_apply<T>(h, vj[3 * c], vj[3 * c + 1], vj[3 * c + 2], o[c][0], o[c][1], o[c][2]);
+                    for (int c = 0; c < NV; ++c) pair_apply<T>(h.v, vj[3 * c], vj[3 * c + 1], vj[3 * c + 2], o[c][0], o[c][1], o[c][2]);
                 } else {
                     const T h0 = od.dyn[k], h1 = od.dyn[S + k], h2 = od.dyn[2 * S + k];
 #pragma unroll
@@ -140,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void k_mb_schur_pose(Table<T> tb, Table<T> 
         }
 #pragma unroll
         for (int c = 0; c < NV; ++c) { o[c][0] = group_sum<T, G>(o[c][0]); o[c][1] = group_sum<T, G>(o[c][1]); o[c][2] = group_sum<T, G>(o[c][2]); }
-        if (valid && (lane % G) == 0) {
+        if (valid && wk.head) {
             T d[6];
 #pragma unroll
             for (int m = 0; m < 6; ++m) d[m] = dp[(size_t)i * 6 + m];
@@ -375,15 +368,14 @@ struct MbColumn { int kind, idx, comp, pad; };      // kind 0 pose, 1 landmark, 
 // give Y = 0.
 template <typename T>
 __device__ __forceinline__ void lm_y_block(const Table<T>& tb, const T* __restrict__ ps, size_t k, const T* dinv3, uint32_t& pose, T y[3][2]) {
-    const size_t S = tb.slots;
     pose = tb.idx[k];
-    const auto aa = ld2<T>(tb.dyn + 2 * k), pp = ld2<T>(tb.dyn + 2 * (S + k));
+    const LmSlot<T> d = lm_slot<T>(tb, k);
     const auto cs = ld2<T>(ps + (size_t)pose * 4 + 2);
     const T ixx = dinv3[0], ixy = dinv3[1], iyy = dinv3[2];
 #pragma unroll
     for (int kk = 0; kk < 3; ++kk) {       // column kk of W_il^T (2 x 3) = W_il^T e_kk; Y_il row kk = (Dl^-1 W_il^T e_kk)^T
         T m0, m1;
-        wt_apply<T>(aa.x, aa.y, pp.x, pp.y, cs.x, cs.y, T(kk == 0), T(kk == 1), T(kk == 2), m0, m1);
+        wt_apply<T>(d.a0, d.a1, d.ppx, d.ppy, cs.x, cs.y, T(kk == 0), T(kk == 1), T(kk == 2), m0, m1);
         y[kk][0] = ixx * m0 + ixy * m1; y[kk][1] = ixy * m0 + iyy * m1;
     }
 }

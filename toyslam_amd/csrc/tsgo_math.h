@@ -1,5 +1,5 @@
 // tsgo_math.h — per-edge arithmetic of the Gauss-Newton hot path, shared by the HIP kernels
-// (tsgo_kernels.hip) and by host code.  Everything is expressed in the POSE FRAME of the edge's
+// (tsgo_kernels.h and the headers beside it, compiled through tsgo_hip.hip) and by host code (the f64 twin, oracle/oracle_sparse.cpp).  Everything is expressed in the POSE FRAME of the edge's
 // first vertex, which is what lets one LM edge be stored as four numbers (a0, a1, ppx, ppy).
 //
 // Reference behaviour restated here (paths relative to the ToySlam tree):
@@ -7,6 +7,8 @@
 //             with v = (ppy, -ppx), (ppx, ppy) = R^T (l - t)   (A(0,2) = ppy, A(1,2) = -ppx, :58,:61)
 //   ODOM edge remote/graph/edge/EdgeSe2.h:23-38          e = (D02, D12, atan2(D10, D00)),
 //             D = meas^-1 (T1^-1 T2),  A = -I, B = +I (constant, :35-37)
+//   priors    edge types 3 and 4 (include/tsgo.h), an extension: a unary Gaussian on one pose, e = (R_m^T (t - t_m), wrap(th - th_m)),
+//             or on one landmark, e = l - m; diagonal information, Huber as for every other edge (pose_prior_linearize, lm_prior_linearize)
 //   Huber     remote/optimizer/OptimizerCpu.h:36-46      on chi^2, delta = 1.5
 //   blocks    remote/optimizer/OptimizerCpu.h:88-119     Omega_w = w_huber * Omega (diagonal on the wire,
 //             remote/serialization/DeserializeGraph.h:123-147)
@@ -102,6 +104,32 @@ TSGO_HD OdomLin<T> odom_linearize(T x1, T y1, T c1, T s1, T x2, T y2, T c2, T s2
     T hw;
     huber(chi2, o.rho, hw);
     o.a[0] = hw * w[0]; o.a[1] = hw * w[1]; o.a[2] = hw * w[2];
+    return o;
+}
+
+// Unary priors (edge types 3 and 4): measured pose (mx, my, cm = cos, sm = sin) or point (mx, my), diagonal information w.  e = residual
+// (a pose's translation part in the MEASURED pose's frame, J = blockdiag(R_m^T, 1); a landmark's in the world frame), a = Huber weight * w.
+template <typename T> struct PosePriorLin { T e0, e1, et, a0, a1, a2, rho; };
+template <typename T>
+TSGO_HD PosePriorLin<T> pose_prior_linearize(T mx, T my, T cm, T sm, T w0, T w1, T w2, T x, T y, T c, T s) {
+    PosePriorLin<T> o;
+    const T dx = x - mx, dy = y - my;
+    o.e0 = cm * dx + sm * dy; o.e1 = cm * dy - sm * dx;
+    o.et = atan2(s * cm - c * sm, c * cm + s * sm);
+    T hw;
+    huber<T>(w0 * o.e0 * o.e0 + w1 * o.e1 * o.e1 + w2 * o.et * o.et, o.rho, hw);
+    o.a0 = hw * w0; o.a1 = hw * w1; o.a2 = hw * w2;
+    return o;
+}
+
+template <typename T> struct LmPriorLin { T e0, e1, a0, a1, rho; };
+template <typename T>
+TSGO_HD LmPriorLin<T> lm_prior_linearize(T mx, T my, T w0, T w1, T lx, T ly) {
+    LmPriorLin<T> o;
+    o.e0 = lx - mx; o.e1 = ly - my;
+    T hw;
+    huber<T>(w0 * o.e0 * o.e0 + w1 * o.e1 * o.e1, o.rho, hw);
+    o.a0 = hw * w0; o.a1 = hw * w1;
     return o;
 }
 
