@@ -35,7 +35,7 @@ extern "C" {
  *            sit on one vertex (summed in input order), also on a fixed one.  Pose prior on an Se2 vertex: e_t = R_m^T (t - t_m),
  *            e_th = atan2(sin(th - m_th), cos(th - m_th)) (the ODOM residual of an edge whose first pose is held at the origin),
  *            J = blockdiag(R_m^T, 1): H_pp += [[R_m diag(a0, a1) R_m^T, 0], [0, a2]], b_p -= J^T Omega_w e.  Landmark prior on a Point2
- *            vertex: e = l - m, J = I: D_l += Omega_w, b_l -= Omega_w e.  Omega_w = Huber weight (delta 1.5) * diag(w), chi^2 += rho as
+ *            vertex: e = l - m, J = I: D_l += Omega_w, b_l -= Omega_w e.  Omega_w = the class's robust weight (default Huber, 1.5) * diag(w), chi^2 += rho as
  *            for every edge; independent of odom_jacobian; damped and (at a fixed vertex) zeroed with the rest under rules = 1
  *   e_meas : 9 doubles per edge: ODOM = the 3x3 measurement row-major (EdgeSe2.h); LM = (range,
  *            bearing, 0...) (EdgeSe2Point2d.h:34-35); virtual landmark = (range1, bearing1, range2, bearing2, 0...): the point
@@ -95,7 +95,8 @@ typedef struct tsgo_config {
                                 linearise at x with H + lambda I (b zeroed at fixed vertices as under 1), solve (H + lambda I) d = b (PCG from
                                 zero: warm_start is ignored, a full step leaves no remainder), take the FULL step x + d tentatively, evaluate the
                                 robustified chi^2 there and decide by the gain ratio rho = (chi^2(x) - chi^2(x + d)) / pred, pred = b^T d +
-                                lambda d^T d (the drop of the quadratic model: grad(sum rho_huber) = -2 b exactly, d^T H d = b^T d - lambda d^T d).
+                                lambda d^T d (the drop of the quadratic model: grad(sum rho) = -2 b exactly for every robust kernel of tsgo_set_robust, whose weight is
+                                w = rho'; d^T H d = b^T d - lambda d^T d).
                                 Accepted (rho > 0 and pred > 0): the step stays, lambda *= max(1/3, 1 - (2 rho - 1)^3), nu = 2.  Rejected: the
                                 estimates are restored bit for bit, lambda *= nu, nu *= 2, and the next trial linearises again at the restored
                                 point.  lambda starts at lm_lambda0 (nu at 2) on every tsgo_optimize and stays within [1e-9, 1e9].  Trials count
@@ -191,6 +192,31 @@ int tsgo_set_graph(tsgo_optimizer* opt, const tsgo_graph* g);
  * reference creates a fresh optimizer per message, remote/app/ConnectionHandler.h:18-21: nothing of one client ever reaches another). */
 void tsgo_reset_history(tsgo_optimizer* opt);
 
+/* Robust kernels per edge class (no reference counterpart: the reference robustifies every edge by Huber with delta = 1.5,
+ * remote/optimizer/OptimizerCpu.h:36-46,92, which is the default here).  All are functions of s = e^T Omega e, the unrobustified chi^2 of
+ * the edge: rho(s) goes into chi^2, w = rho'(s) scales Omega.
+ *   NONE            rho = s                                            w = 1
+ *   HUBER(d)        rho = s if s <= d^2, else 2 d sqrt(s) - d^2         w = 1 if s <= d^2, else d / sqrt(s)
+ *   CAUCHY(d)       rho = d^2 ln(1 + s / d^2)                          w = 1 / (1 + s / d^2)
+ *   GEMAN_MCCLURE   rho = d^2 s / (d^2 + s)                            w = (d^2 / (d^2 + s))^2
+ * tsgo_set_robust may be called any time after tsgo_create, before or after tsgo_set_graph, and takes effect at the next linearisation
+ * (tsgo_linearize, tsgo_solve_step, tsgo_optimize under every `rules`, tsgo_marginals, tsgo_joint_marginals).  The setting belongs to the
+ * handle: it survives tsgo_set_graph, whether the structure is rebuilt or reused, so it can be changed between two tsgo_optimize calls on
+ * one structure (wide, then narrow) without a rebuild.  A call that changes anything makes the next linearisation rebuild the multigrid
+ * hierarchy; the warm start's history stays (same answer to pcg_rel_tol).  precision 64 and 32.  A handle whose setting equals the default
+ * runs the same device code, bit for bit, as one that was never given a setting.  Errors (< 0, text in tsgo_last_error): a NULL argument,
+ * an unknown kernel id, a delta that is not finite or outside [1e-6, 1e6] on a class whose kernel uses one, a non-default setting on an
+ * edge-sharded handle (world > 1). */
+enum { TSGO_ROBUST_NONE = 0, TSGO_ROBUST_HUBER = 1, TSGO_ROBUST_CAUCHY = 2, TSGO_ROBUST_GEMAN_MCCLURE = 3 };
+typedef struct tsgo_robust {
+    int32_t kernel[5];   /* indexed by tsgo_graph.e_type: 0 ODOM, 1 LM, 2 virtual landmark, 3 pose prior, 4 landmark prior */
+    int32_t reserved;    /* 0 */
+    double  delta[5];    /* width; ignored by NONE */
+} tsgo_robust;
+void tsgo_default_robust(tsgo_robust* r);                        /* host-only too: HUBER, 1.5 everywhere */
+int tsgo_set_robust(tsgo_optimizer* opt, const tsgo_robust* r);
+int tsgo_get_robust(tsgo_optimizer* opt, tsgo_robust* out);
+
 /* Replaces IOptimizer<T>::Optimize(IGraph*) (remote/optimizer/IOptimizer.h:21; loop semantics of
  * OptimizerCpu.h:25-183) including ISolver<T>::Solve (remote/solver/ISolver.h:10).  The graph held by
  * the handle is updated in place. */
@@ -259,7 +285,7 @@ typedef struct tsgo_prof_entry {
 int tsgo_profile_iteration(tsgo_optimizer* opt, int32_t reps, tsgo_prof_entry* out, int32_t cap);
 
 /* Marginal covariances: the diagonal blocks of H^-1, H = the Gauss-Newton matrix of ONE linearisation at the handle's current
- * estimates (Huber weights, the gauge term once per occurrence in the fixed list, tsgo_config.odom_jacobian, virtual landmark edges;
+ * estimates (each class's robust weights, default Huber 1.5 (tsgo_set_robust); the gauge term once per occurrence in the fixed list, tsgo_config.odom_jacobian, virtual landmark edges;
  * NOT the rules = 1 damping).  Per queried vertex id, in query order, 9 doubles of cov_out: the 3x3 block of a pose, row-major, or the
  * 2x2 block of a landmark in the leading 2x2 (the other five entries 0); each block is symmetrised, (S + S^T) / 2.  A pose's block is
  * (S^-1)_ii of the reduced pose system S = Hpp - W D^-1 W^T, a landmark's D_l^-1 + Y_l^T S^-1 Y_l with Y_l = W_{:,l} D_l^-1: 3 k + 2 m

@@ -140,6 +140,23 @@ public:
         return c;
     }
 
+    // Robust kernel of one edge class (tsgo_set_robust): kernel = TSGO_ROBUST_*, delta its width (ignored by TSGO_ROBUST_NONE); the other
+    // classes keep what the handle has.  Takes effect at the next Optimize.  Throws on an error (unknown kernel, delta out of range).
+    void SetRobust(EdgeType edge_class, int kernel, double delta = 1.5) {
+        tsgo_robust r;
+        if (tsgo_get_robust(handle, &r)) throw std::runtime_error(tsgo_last_error());
+        r.kernel[(uint32_t)edge_class] = kernel; r.delta[(uint32_t)edge_class] = delta;
+        SetRobust(r);
+    }
+    void SetRobust(const tsgo_robust& setting) {
+        if (tsgo_set_robust(handle, &setting)) throw std::runtime_error(tsgo_last_error());
+    }
+    tsgo_robust Robust() const {
+        tsgo_robust r;
+        if (tsgo_get_robust(handle, &r)) throw std::runtime_error(tsgo_last_error());
+        return r;
+    }
+
     // Marginal covariances at the estimates of the last Optimize (tsgo_marginals): 9 doubles per id, row-major; a landmark's 2x2 block
     // in the leading 2x2.  Throws on an error (unknown id, no fixed vertex, no graph yet, precision 32).
     std::vector<double> Marginals(const std::vector<uint32_t>& ids) {

@@ -33,6 +33,14 @@ class tsgo_marginal_stats(C.Structure):
                 ("ms_total", C.c_double), ("ms_solve", C.c_double)]
 
 
+class tsgo_robust(C.Structure):
+    _fields_ = [("kernel", C.c_int32 * 5), ("reserved", C.c_int32), ("delta", C.c_double * 5)]
+
+
+ROBUST_KERNELS = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}      # TSGO_ROBUST_*
+ROBUST_CLASSES = ("odom", "lm", "virtual", "pose_prior", "lm_prior")            # = tsgo_graph.e_type 0 .. 4
+
+
 class tsgo_cycle_level(C.Structure):
     _fields_ = [("rows", C.c_int64), ("blocks", C.c_int64), ("sweeps_per_cycle", C.c_int32), ("lanes_per_row", C.c_int32),
                 ("us_per_sweep", C.c_double), ("bytes_per_sweep", C.c_double)]
@@ -61,18 +69,19 @@ class tsgo_amg_info(C.Structure):
                 ("agg_min", C.c_int32 * 8), ("agg_max", C.c_int32 * 8), ("checksum", C.c_uint64)]
 
 
-HOST_SYMBOLS = ["tsgo_default_config", "tsgo_last_error", "tsgo_wire_decode", "tsgo_wire_new", "tsgo_wire_decode_into", "tsgo_wire_view", "tsgo_wire_free",
+HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_last_error", "tsgo_wire_decode", "tsgo_wire_new", "tsgo_wire_decode_into", "tsgo_wire_view", "tsgo_wire_free",
                 "tsgo_wire_encode_response", "tsgo_wire_encode_request", "tsgo_synth_create", "tsgo_synth_view",
                 "tsgo_synth_truth", "tsgo_synth_free", "tsgo_layout_probe", "tsgo_amg_probe", "tsgo_amg_probe_shard"]
 DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_graph", "tsgo_reset_history", "tsgo_optimize", "tsgo_get_vertices",
                   "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
-                  "tsgo_marginals", "tsgo_joint_marginals"]
+                  "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
 
 def _declare_host(L):
     vp, u8p = C.c_void_p, C.POINTER(C.c_uint8)
     L.tsgo_default_config.argtypes = [C.POINTER(tsgo_config)]; L.tsgo_default_config.restype = None
+    L.tsgo_default_robust.argtypes = [C.POINTER(tsgo_robust)]; L.tsgo_default_robust.restype = None
     L.tsgo_last_error.restype = C.c_char_p
     L.tsgo_wire_decode.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp)]
     L.tsgo_wire_new.argtypes = []; L.tsgo_wire_new.restype = vp
@@ -112,6 +121,8 @@ def _declare_device(L):
     L.tsgo_profile_iteration.argtypes = [vp, C.c_int32, C.POINTER(tsgo_prof_entry), C.c_int32]
     L.tsgo_marginals.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.POINTER(tsgo_marginal_stats)]
     L.tsgo_joint_marginals.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.c_int64, C.POINTER(C.c_int32), C.POINTER(tsgo_marginal_stats)]
+    L.tsgo_set_robust.argtypes = [vp, C.POINTER(tsgo_robust)]
+    L.tsgo_get_robust.argtypes = [vp, C.POINTER(tsgo_robust)]
 
 
 def _declare_testing(L):

@@ -49,6 +49,30 @@
     PriorArgs<T> lm_prior_args() const { return PriorArgs<T>{pri_l_off, pri_l, pri_lchi, 0}; }
     static PriorArgs<T> no_priors() { return PriorArgs<T>{nullptr, nullptr, nullptr, 0}; }
     static GateArgs<T> no_gate() { return GateArgs<T>{nullptr, nullptr, nullptr, 0, T(0), nullptr, 0}; }
+    // Robust kernels per edge class (tsgo_set_robust): a property of the HANDLE (it survives tsgo_set_graph), read by every launch that
+    // robustifies.  A setting equal to the default takes the RK = 0 instantiations — the compile-time Huber, exactly what was launched
+    // before the setting existed; anything else the RK = 1 ones, which read kind and width from the by-value argument below.
+    tsgo_robust robust = default_robust();
+    static tsgo_robust default_robust() { tsgo_robust r; tsgo_default_robust(&r); return r; }
+    static bool same_robust(const tsgo_robust& a, const tsgo_robust& b) {
+        for (int k = 0; k < kEdgeClasses; ++k)
+            if (a.kernel[k] != b.kernel[k] || (a.kernel[k] != TSGO_ROBUST_NONE && a.delta[k] != b.delta[k])) return false;      // NONE ignores its width
+        return true;
+    }
+    int rk() const { return same_robust(robust, default_robust()) ? 0 : 1; }
+    RobustArgs<T> robust_args() const {
+        RobustArgs<T> a{};
+        for (int k = 0; k < kEdgeClasses; ++k) { a.kind[k] = robust.kernel[k]; a.delta[k] = (T)robust.delta[k]; }
+        return a;
+    }
+    int set_robust(const tsgo_robust& r) override {
+        if (!same_robust(r, default_robust()) && cfg.world > 1)
+            return set_error(-1, "tsgo_set_robust: a non-default robust kernel is not supported on an edge-sharded handle (world > 1)");
+        if (!same_robust(r, robust)) hier_age = -1;      // the weights may move wholesale: the next linearisation builds a fresh hierarchy
+        robust = r; robust.reserved = 0;
+        return 0;
+    }
+    void get_robust(tsgo_robust* out) const override { *out = robust; }
     void launch_lin() {
         launch_lin_lm();
         launch_lin_pose_only();
@@ -56,24 +80,26 @@
     void launch_lin_lm() {              // (tsgo_time_kernel too)
         const int zf = (py_rules() || lm_rules()) ? 1 : 0;
         if (tl.n_slices == 0) return;
-        pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(pr.has_priors, [&](auto pri) {
-            launch(k_lin_lm<T, g, pri>, nbL, tl, ps, lmrec, gauge_l, ninv, (T)lambda, zf, pri ? lm_prior_args() : no_priors());
-        }); });
+        pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick<0, 1>(rk(), [&](auto rk) {
+            launch(k_lin_lm<T, g, pri, rk>, nbL, tl, ps, lmrec, gauge_l, ninv, (T)lambda, zf, pri ? lm_prior_args() : no_priors(), robust_args());
+        }); }); });
     }
     void launch_lin_pose_only() {       // (tsgo_time_kernel too)
         const int zf = (py_rules() || lm_rules()) ? 1 : 0;
-        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) {
-            launch(k_lin_pose<T, g, general, pri>, nbP, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf,
-                   general ? odom_analytic_flag() : 0, pri ? pose_prior_args() : no_priors());
-        }); }); });
+        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick<0, 1>(rk(), [&](auto rk) {
+            launch(k_lin_pose<T, g, general, pri, rk>, nbP, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf,
+                   general ? odom_analytic_flag() : 0, pri ? pose_prior_args() : no_priors(), robust_args());
+        }); }); }); });
     }
     // rules = 2: robustified chi^2 at the current estimates, nbP partials into `out` (tsgo_lm_kernels.h; tsgo_time_kernel 7 too).  One launch,
     // and one more in front of it on a graph with priors (the landmark priors' partials, which k_chi2<.., 1> folds as k_lin_pose<.., 1> does)
     void launch_chi2(T* out) {
-        if (pr.has_priors && tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { launch(k_chi2_lm_prior<T, g>, nbL, tl, (const T*)lmrec, lm_prior_args()); });
-        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) {
-            launch(k_chi2<T, g, general, pri>, nbP, tp, to, (const T*)ps, (const T*)lmrec, out, pri ? pose_prior_args() : no_priors());
-        }); }); });
+        if (pr.has_priors && tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(rk(), [&](auto rk) {
+            launch(k_chi2_lm_prior<T, g, rk>, nbL, tl, (const T*)lmrec, lm_prior_args(), robust_args());
+        }); });
+        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick<0, 1>(rk(), [&](auto rk) {
+            launch(k_chi2<T, g, general, pri, rk>, nbP, tp, to, (const T*)ps, (const T*)lmrec, out, pri ? pose_prior_args() : no_priors(), robust_args());
+        }); }); }); });
     }
     // (LM slot: index, zx zy w0 w1, 16 B of the landmark record; pose-pose slot: its index, and at the first endpoint nine planes + the neighbour's record)
     double bytes_chi2() { const double v = sizeof(T); return (double)pr.n_lm_edges * (4 + 6 * v) + pr.P * 4.0 * v + od_slots_live() * (4 + 6.5 * v) + nbP * v; }

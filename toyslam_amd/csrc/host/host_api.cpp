@@ -14,6 +14,12 @@ extern "C" void tsgo_default_config(tsgo_config* c) {
     c->lm_lambda0 = 1e-3; c->lm_chi2_rel_tol = 1e-6;
 }
 
+extern "C" void tsgo_default_robust(tsgo_robust* r) {
+    if (!r) return;
+    for (int k = 0; k < 5; ++k) { r->kernel[k] = TSGO_ROBUST_HUBER; r->delta[k] = 1.5; }
+    r->reserved = 0;
+}
+
 extern "C" int tsgo_layout_probe(const tsgo_graph* g, int32_t rank, int32_t world, int32_t lanes_per_pose,
                                  int32_t lanes_per_lm, tsgo_layout_info* out) {
     if (!g || !out) return tsgo::set_error(-1, "tsgo_layout_probe: null argument");

@@ -142,6 +142,8 @@ struct IEngine {
     virtual int comm_selftest(int* ranks_out) = 0;
     virtual int comm_time_allreduce(int64_t n, int reps, double* us) = 0;
     virtual void reset_history() = 0;
+    virtual int set_robust(const tsgo_robust& r) = 0;
+    virtual void get_robust(tsgo_robust* out) const = 0;
     virtual int marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, tsgo_marginal_stats* st) = 0;
     virtual int joint_marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, int64_t cov_cap, int* dim_out, tsgo_marginal_stats* st) = 0;
 #ifdef TSGO_TESTING
@@ -539,6 +541,22 @@ int tsgo_joint_marginals(tsgo_optimizer* o, const uint32_t* ids, int32_t n_ids, 
 }
 void tsgo_reset_history(tsgo_optimizer* o) {
     if (o && o->eng) o->eng->reset_history();
+}
+int tsgo_set_robust(tsgo_optimizer* o, const tsgo_robust* r) {
+    if (!o || !r) return tsgo::set_error(-1, "tsgo_set_robust: null argument");
+    static const char* const cls[kEdgeClasses] = {"ODOM", "LM", "virtual landmark", "pose prior", "landmark prior"};
+    for (int k = 0; k < kEdgeClasses; ++k) {
+        if (r->kernel[k] < 0 || r->kernel[k] >= kRobustKinds)
+            return tsgo::set_error(-1, std::string("tsgo_set_robust: unknown robust kernel ") + std::to_string(r->kernel[k]) + " for class " + cls[k]);
+        if (r->kernel[k] != TSGO_ROBUST_NONE && !(std::isfinite(r->delta[k]) && r->delta[k] >= 1e-6 && r->delta[k] <= 1e6))
+            return tsgo::set_error(-1, std::string("tsgo_set_robust: delta of class ") + cls[k] + " must be finite and within [1e-6, 1e6]");
+    }
+    return o->eng->set_robust(*r);
+}
+int tsgo_get_robust(tsgo_optimizer* o, tsgo_robust* out) {
+    if (!o || !out) return tsgo::set_error(-1, "tsgo_get_robust: null argument");
+    o->eng->get_robust(out);
+    return 0;
 }
 int tsgo_comm_selftest(tsgo_optimizer* o, int32_t* ranks_out) {
     if (!o) return tsgo::set_error(-1, "tsgo_comm_selftest: null argument");

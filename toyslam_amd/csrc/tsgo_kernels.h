@@ -190,12 +190,23 @@ template <typename T> __device__ __forceinline__ void iter_gate_body(const GateA
 // partials of the landmark priors (k_lin_lm<.., 1>), which workgroup 0 of k_lin_pose<.., .., 1> adds to its own partial in a fixed order.
 template <typename T> struct PriorArgs { const uint32_t* off; const T* rec; T* lm_chi; int n_lm_chi; };
 
-// Pose prior (type 3): e_t = R_m^T (t - t_m), e_th = wrap(th - m_th); J = blockdiag(R_m^T, 1).  With a = Huber weight * (w0, w1, w2):
-// H_pp += [[R_m diag(a0, a1) R_m^T, 0], [0, a2]] (h00 h01 h11 h22), b_p -= J^T diag(a) e (b0 b1 b2); returns rho.
-template <typename T> __device__ __forceinline__ T pose_prior_fold(const T* q, T x, T y, T c, T s, T& h00, T& h01, T& h11, T& h22, T& b0, T& b1, T& b2) {
+// Robust kernels per edge class (tsgo_set_robust; tsgo_math.h: robust_eval), the compile-time axis RK of the kernels that robustify:
+// RK = 0 is the compile-time Huber (delta 1.5) — what a handle with the default setting launches, the same instructions as before the
+// setting existed; RK = 1 reads kind and width of the class whose table is being walked from this by-value kernel argument (kernarg
+// memory, scalar loads).  The class is known where the edge function is called (the LM rows, ODOM against virtual landmark by kVlmMask,
+// the prior records) and the kind is the same for every lane: the selection in robust_eval is a scalar branch.
+template <typename T> struct RobustArgs { int kind[kEdgeClasses]; int pad; T delta[kEdgeClasses]; };
+template <int RK, typename T> __device__ __forceinline__ auto robust_class(const RobustArgs<T>& ra, int cls) {
+    if constexpr (RK == 0) return HuberDefault{};
+    else return Robust<T>{ra.kind[cls], ra.delta[cls]};
+}
+
+// Pose prior (type 3): e_t = R_m^T (t - t_m), e_th = wrap(th - m_th); J = blockdiag(R_m^T, 1).  With a = robust weight * (w0, w1, w2):
+// H_pp += [[R_m diag(a0, a1) R_m^T, 0], [0, a2]] (h00 h01 h11 h22), b_p -= J^T diag(a) e (b0 b1 b2); returns rho.  rk: the class's robust kernel.
+template <typename T, typename K> __device__ __forceinline__ T pose_prior_fold(const T* q, T x, T y, T c, T s, T& h00, T& h01, T& h11, T& h22, T& b0, T& b1, T& b2, const K& rk) {
     const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C), w01 = ld2<T>(q + PRI_W0);
     const T cm = cs.x, sm = cs.y;
-    const PosePriorLin<T> o = pose_prior_linearize<T>(m01.x, m01.y, cm, sm, w01.x, w01.y, q[PRI_W2], x, y, c, s);
+    const PosePriorLin<T> o = pose_prior_linearize<T>(m01.x, m01.y, cm, sm, w01.x, w01.y, q[PRI_W2], x, y, c, s, rk);
     h00 += o.a0 * cm * cm + o.a1 * sm * sm; h01 += (o.a0 - o.a1) * cm * sm; h11 += o.a0 * sm * sm + o.a1 * cm * cm; h22 += o.a2;
     const T f0 = o.a0 * o.e0, f1 = o.a1 * o.e1;
     b0 -= cm * f0 - sm * f1; b1 -= sm * f0 + cm * f1; b2 -= o.a2 * o.et;
@@ -208,13 +219,16 @@ template <typename T> __device__ __forceinline__ T pose_prior_fold(const T* q, T
 //   writes: slot planes a0 a1 ppx ppy (lm-major copy), lmrec[l][2..6] = Dl^-1, u
 // PRI = 1: the landmark priors (type 4: D_l += Omega_w, b_l -= Omega_w (l - m)) before the inverse, and one chi^2 partial of them per
 // workgroup into pa.lm_chi (every wave reaches the workgroup sum: none leaves early)
-template <typename T, int G, int PRI = 0>
+// RK = 1: the robust kernels of classes LM and landmark prior from ra (RobustArgs above)
+template <typename T, int G, int PRI = 0, int RK = 0>
 __global__ __launch_bounds__(kBlock) void k_lin_lm(Table<T> tb, const T* __restrict__ ps, T* __restrict__ lmrec,
                                                    const T* __restrict__ gauge_l, T* __restrict__ ninv, T lambda, int zero_fixed,
-                                                   const PriorArgs<T> pa = PriorArgs<T>{nullptr, nullptr, nullptr, 0}) {
+                                                   const PriorArgs<T> pa = PriorArgs<T>{nullptr, nullptr, nullptr, 0},
+                                                   const RobustArgs<T> ra = RobustArgs<T>{}) {
     const Walk wk = walk_of<G>(tb);
     const int slice = wk.slice, lane = wk.lane, l = wk.vertex, live = wk.live;
     if (!PRI && !live) return;
+    const auto rk_lm = robust_class<RK>(ra, kClassLm);
     const bool valid = l < tb.n_vertices;      // (false on every lane of a wave past the last slice)
     const int lc = valid ? l : tb.n_vertices - 1;
     const T lx = lmrec[(size_t)lc * kLmRec], ly = lmrec[(size_t)lc * kLmRec + 1];
@@ -228,7 +242,7 @@ __global__ __launch_bounds__(kBlock) void k_lin_lm(Table<T> tb, const T* __restr
         const T* q = ps + (size_t)i * 4;
         const auto q01 = ld2<T>(q), q23 = ld2<T>(q + 2);
         const T x = q01.x, y = q01.y, c = q23.x, s = q23.y;
-        const LmLin<T> o = lm_linearize<T>(x, y, c, s, lx, ly, z.zx, z.zy, z.w0, z.w1);
+        const LmLin<T> o = lm_linearize<T>(x, y, c, s, lx, ly, z.zx, z.zy, z.w0, z.w1, rk_lm);
         lm_slot_store<T>(tb, k, o);
         dxx += o.a0 * c * c + o.a1 * s * s; dxy += (o.a0 - o.a1) * c * s; dyy += o.a0 * s * s + o.a1 * c * c;
         const T f0 = o.a0 * o.e0, f1 = o.a1 * o.e1;
@@ -243,7 +257,7 @@ __global__ __launch_bounds__(kBlock) void k_lin_lm(Table<T> tb, const T* __restr
             for (uint32_t k = pa.off[l]; k < pa.off[l + 1]; ++k) {
                 const T* q = pa.rec + (size_t)k * PRI_LM_REC;
                 const auto m = ld2<T>(q + PRL_MX), w = ld2<T>(q + PRL_W0);
-                const LmPriorLin<T> o = lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly);
+                const LmPriorLin<T> o = lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly, robust_class<RK>(ra, kClassLmPrior));
                 dxx += o.a0; dyy += o.a1; g0 -= o.a0 * o.e0; g1 -= o.a1 * o.e1;
                 chi += o.rho;
             }
@@ -274,16 +288,19 @@ __global__ __launch_bounds__(kBlock) void k_lin_lm(Table<T> tb, const T* __restr
 // ODOM edges under the reference's constant Jacobians are written in that form too when the graph holds the other kind.
 // PRI = 1: the pose priors (type 3, pose_prior_fold) of the pose in the epilogue, before a fixed pose's gradient is zeroed, and the landmark
 // priors' chi^2 partials (pa.lm_chi, left by k_lin_lm<.., 1>) in workgroup 0's partial.  The host lists only the priors of owned poses.
-template <typename T, int G, int OJ = 0, int PRI = 0>
+// RK = 1: the robust kernels of classes LM, ODOM, virtual landmark and pose prior from ra (RobustArgs above)
+template <typename T, int G, int OJ = 0, int PRI = 0, int RK = 0>
 __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, const T* __restrict__ ps,
                                                      const T* __restrict__ lmrec, const T* __restrict__ gauge_p,
                                                      int pose_first, int pose_last, T* __restrict__ part,
                                                      T* __restrict__ chi_part, T lambda, int zero_fixed, int odom_analytic = 0,
-                                                     const PriorArgs<T> pa = PriorArgs<T>{nullptr, nullptr, nullptr, 0}) {
+                                                     const PriorArgs<T> pa = PriorArgs<T>{nullptr, nullptr, nullptr, 0},
+                                                     const RobustArgs<T> ra = RobustArgs<T>{}) {
     __shared__ T red[kWavesPerBlock];
     const Walk wk = walk_of<G>(tb);
     const int slice = wk.slice, lane = wk.lane, i = wk.vertex;
     const bool live = wk.live, valid = live && i < tb.n_vertices;
+    const auto rk_lm = robust_class<RK>(ra, kClassLm), rk_odom = robust_class<RK>(ra, kClassOdom);
     T chi = 0;
     if (live) {
         const int ic = valid ? i : tb.n_vertices - 1;
@@ -299,7 +316,7 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, c
                 const T* lr = lmrec + (size_t)l * kLmRec;
                 const auto l01 = ld2<T>(lr), l23 = ld2<T>(lr + 2), l45 = ld2<T>(lr + 4);
                 const T lx = l01.x, ly = l01.y, nxx = l23.x, nxy = l23.y, nyy = l45.x, ux = l45.y, uy = lr[6];
-                const LmLin<T> o = lm_linearize<T>(x0, y0, c, s, lx, ly, z.zx, z.zy, z.w0, z.w1);
+                const LmLin<T> o = lm_linearize<T>(x0, y0, c, s, lx, ly, z.zx, z.zy, z.w0, z.w1, rk_lm);
                 lm_slot_store<T>(tb, k, o);
                 chi += o.rho;
                 const T v0 = o.ppy, v1 = -o.ppx;
@@ -331,7 +348,7 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, c
                 const T* oq = ps + (size_t)j * 4;
                 const T xj = oq[0], yj = oq[1], cj = oq[2], sj = oq[3];
                 if (OJ && (raw & kVlmMask)) {      // virtual landmark measurement: mi = (pox, poy, pnx, pny, ., .), w = (w0, w1, .)
-                    const VlmLin<T> v = vlm_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1]);
+                    const VlmLin<T> v = vlm_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1], robust_class<RK>(ra, kClassVlm));
                     T h[PP_PLANES];
                     vlm_slot<T>(v, h);
 #pragma unroll
@@ -341,8 +358,8 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, c
                     if (!second) chi += v.rho;
                     continue;
                 }
-                const OdomLin<T> o = second ? odom_linearize<T>(xj, yj, cj, sj, x0, y0, c, s, z.mi, z.w)
-                                            : odom_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi, z.w);
+                const OdomLin<T> o = second ? odom_linearize<T>(xj, yj, cj, sj, x0, y0, c, s, z.mi, z.w, rk_odom)
+                                            : odom_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi, z.w, rk_odom);
                 if (OJ && odom_analytic) {
                     const OdomBlocks<T> ob = second ? odom_blocks<T>(o, xj, yj, cj, sj, x0, y0, c, s, z.mi) : odom_blocks<T>(o, x0, y0, c, s, xj, yj, cj, sj, z.mi);
                     // H_12 = [[-K, 0], [g^T, -w]] at the first endpoint, its transpose at the second
@@ -385,7 +402,7 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, c
             if constexpr (PRI != 0) {
                 T h00 = 0, h01 = 0, h11 = 0, h22 = 0, b0 = 0, b1 = 0, b2 = 0;
                 for (uint32_t k = pa.off[i]; k < pa.off[i + 1]; ++k)
-                    chi += pose_prior_fold<T>(pa.rec + (size_t)k * PRI_POSE_REC, x0, y0, c, s, h00, h01, h11, h22, b0, b1, b2);
+                    chi += pose_prior_fold<T>(pa.rec + (size_t)k * PRI_POSE_REC, x0, y0, c, s, h00, h01, h11, h22, b0, b1, b2, robust_class<RK>(ra, kClassPosePrior));
                 o[0] += h00; o[1] += h01; o[3] += h11; o[5] += h22; o[6] += b0; o[7] += b1; o[8] += b2;
             }
             if (fixed_here) { o[6] = 0; o[7] = 0; o[8] = 0; }

@@ -8,8 +8,9 @@
 //   ODOM edge remote/graph/edge/EdgeSe2.h:23-38          e = (D02, D12, atan2(D10, D00)),
 //             D = meas^-1 (T1^-1 T2),  A = -I, B = +I (constant, :35-37)
 //   priors    edge types 3 and 4 (include/tsgo.h), an extension: a unary Gaussian on one pose, e = (R_m^T (t - t_m), wrap(th - th_m)),
-//             or on one landmark, e = l - m; diagonal information, Huber as for every other edge (pose_prior_linearize, lm_prior_linearize)
-//   Huber     remote/optimizer/OptimizerCpu.h:36-46      on chi^2, delta = 1.5
+//             or on one landmark, e = l - m; diagonal information, robustified as every other edge (pose_prior_linearize, lm_prior_linearize)
+//   Huber     remote/optimizer/OptimizerCpu.h:36-46      on chi^2, delta = 1.5 — the default; an extension lets a handle choose the robust
+//             kernel and its width per edge class (tsgo_set_robust, include/tsgo.h; robust_eval below)
 //   blocks    remote/optimizer/OptimizerCpu.h:88-119     Omega_w = w_huber * Omega (diagonal on the wire,
 //             remote/serialization/DeserializeGraph.h:123-147)
 #pragma once
@@ -36,12 +37,42 @@ template <typename T> TSGO_HD void huber(T chi2, T& rho, T& w) {
     else { const T sq = sqrt(chi2); rho = T(2) * sq * d - d2; w = d / sq; }
 }
 
+// Selectable robust kernels (tsgo_set_robust, include/tsgo.h: TSGO_ROBUST_*), all functions of s = e^T Omega e: rho(s) goes into chi^2,
+// w = rho'(s) scales Omega.  rho(0) = 0 and w(0) = 1 for every kernel: a padding slot (zero weights, s = 0) keeps contributing exactly 0.
+//   NONE            rho = s                          w = 1
+//   HUBER(d)        s | 2 d sqrt(s) - d^2            1 | d / sqrt(s)          (s <= d^2 | beyond; the arithmetic of huber() above, bit for bit)
+//   CAUCHY(d)       d^2 ln(1 + s / d^2)              1 / (1 + s / d^2)
+//   GEMAN_MCCLURE   d^2 s / (d^2 + s)                (d^2 / (d^2 + s))^2
+enum { kRobustNone = 0, kRobustHuber = 1, kRobustCauchy = 2, kRobustGemanMcClure = 3, kRobustKinds = 4 };
+enum { kClassOdom = 0, kClassLm = 1, kClassVlm = 2, kClassPosePrior = 3, kClassLmPrior = 4, kEdgeClasses = 5 };      // = tsgo_graph.e_type
+
+template <typename T> TSGO_HD void robust_eval(int kind, T delta, T s, T& rho, T& w) {
+    const T d2 = delta * delta;
+    switch (kind) {
+        case kRobustHuber:
+            if (s <= d2) { rho = s; w = T(1); }
+            else { const T sq = sqrt(s); rho = T(2) * sq * delta - d2; w = delta / sq; }
+            break;
+        case kRobustCauchy: { const T q = s / d2, lg = log1p(q); rho = d2 * lg; w = T(1) / (T(1) + q); break; }
+        case kRobustGemanMcClure: { const T t = d2 / (d2 + s); rho = t * s; w = t * t; break; }
+        default: rho = s; w = T(1); break;
+    }
+}
+
+// How an edge function robustifies its chi^2: HuberDefault = the compile-time Huber above (what every existing signature below means, and
+// what the device kernels' RK = 0 instantiations pass), Robust<T> = a kind and a width read at run time (RK = 1: the class's entry of the
+// handle's setting).  One body per edge function serves both, so the residual arithmetic exists once.
+struct HuberDefault {};
+template <typename T> struct Robust { int kind; T delta; };
+template <typename T> TSGO_HD void robustify(HuberDefault, T s, T& rho, T& w) { huber(s, rho, w); }
+template <typename T> TSGO_HD void robustify(const Robust<T>& k, T s, T& rho, T& w) { robust_eval<T>(k.kind, k.delta, s, rho, w); }
+
 // One LM edge seen from pose (x, y, c = cos th, s = sin th) and landmark (lx, ly); z = (r cos phi,
 // r sin phi) is precomputed on the host.  Outputs the four numbers every later pass needs.
 template <typename T> struct LmLin { T a0, a1, ppx, ppy, e0, e1, rho; };
 
-template <typename T>
-TSGO_HD LmLin<T> lm_linearize(T x, T y, T c, T s, T lx, T ly, T zx, T zy, T w0, T w1) {
+template <typename T, typename K>
+TSGO_HD LmLin<T> lm_linearize(T x, T y, T c, T s, T lx, T ly, T zx, T zy, T w0, T w1, const K& rk) {
     LmLin<T> o;
     const T dx = lx - x, dy = ly - y;
     o.ppx = c * dx + s * dy;
@@ -50,10 +81,14 @@ TSGO_HD LmLin<T> lm_linearize(T x, T y, T c, T s, T lx, T ly, T zx, T zy, T w0, 
     o.e1 = o.ppy - zy;
     const T chi2 = w0 * o.e0 * o.e0 + w1 * o.e1 * o.e1;
     T hw;
-    huber(chi2, o.rho, hw);
+    robustify(rk, chi2, o.rho, hw);
     o.a0 = hw * w0;
     o.a1 = hw * w1;
     return o;
+}
+template <typename T>
+TSGO_HD LmLin<T> lm_linearize(T x, T y, T c, T s, T lx, T ly, T zx, T zy, T w0, T w1) {
+    return lm_linearize<T>(x, y, c, s, lx, ly, zx, zy, w0, w1, HuberDefault{});
 }
 
 // ODOM edge: pose1 (x1,y1,c1,s1) -> pose2; mi = top two rows of meas^-1 (row-major 2x3).
@@ -91,8 +126,8 @@ TSGO_HD OdomBlocks<T> odom_blocks(const OdomLin<T>& o, T x1, T y1, T c1, T s1, T
     return b;
 }
 
-template <typename T>
-TSGO_HD OdomLin<T> odom_linearize(T x1, T y1, T c1, T s1, T x2, T y2, T c2, T s2, const T* mi, const T* w) {
+template <typename T, typename K>
+TSGO_HD OdomLin<T> odom_linearize(T x1, T y1, T c1, T s1, T x2, T y2, T c2, T s2, const T* mi, const T* w, const K& rk) {
     OdomLin<T> o;
     const T dx = x2 - x1, dy = y2 - y1;
     const T px = c1 * dx + s1 * dy, py = c1 * dy - s1 * dx;       // R1^T (t2 - t1)
@@ -102,35 +137,47 @@ TSGO_HD OdomLin<T> odom_linearize(T x1, T y1, T c1, T s1, T x2, T y2, T c2, T s2
     o.e[2] = atan2(mi[3] * cc + mi[4] * ss, mi[0] * cc + mi[1] * ss);
     const T chi2 = w[0] * o.e[0] * o.e[0] + w[1] * o.e[1] * o.e[1] + w[2] * o.e[2] * o.e[2];
     T hw;
-    huber(chi2, o.rho, hw);
+    robustify(rk, chi2, o.rho, hw);
     o.a[0] = hw * w[0]; o.a[1] = hw * w[1]; o.a[2] = hw * w[2];
     return o;
 }
+template <typename T>
+TSGO_HD OdomLin<T> odom_linearize(T x1, T y1, T c1, T s1, T x2, T y2, T c2, T s2, const T* mi, const T* w) {
+    return odom_linearize<T>(x1, y1, c1, s1, x2, y2, c2, s2, mi, w, HuberDefault{});
+}
 
 // Unary priors (edge types 3 and 4): measured pose (mx, my, cm = cos, sm = sin) or point (mx, my), diagonal information w.  e = residual
-// (a pose's translation part in the MEASURED pose's frame, J = blockdiag(R_m^T, 1); a landmark's in the world frame), a = Huber weight * w.
+// (a pose's translation part in the MEASURED pose's frame, J = blockdiag(R_m^T, 1); a landmark's in the world frame), a = robust weight * w.
 template <typename T> struct PosePriorLin { T e0, e1, et, a0, a1, a2, rho; };
-template <typename T>
-TSGO_HD PosePriorLin<T> pose_prior_linearize(T mx, T my, T cm, T sm, T w0, T w1, T w2, T x, T y, T c, T s) {
+template <typename T, typename K>
+TSGO_HD PosePriorLin<T> pose_prior_linearize(T mx, T my, T cm, T sm, T w0, T w1, T w2, T x, T y, T c, T s, const K& rk) {
     PosePriorLin<T> o;
     const T dx = x - mx, dy = y - my;
     o.e0 = cm * dx + sm * dy; o.e1 = cm * dy - sm * dx;
     o.et = atan2(s * cm - c * sm, c * cm + s * sm);
     T hw;
-    huber<T>(w0 * o.e0 * o.e0 + w1 * o.e1 * o.e1 + w2 * o.et * o.et, o.rho, hw);
+    robustify<T>(rk, w0 * o.e0 * o.e0 + w1 * o.e1 * o.e1 + w2 * o.et * o.et, o.rho, hw);
     o.a0 = hw * w0; o.a1 = hw * w1; o.a2 = hw * w2;
     return o;
 }
+template <typename T>
+TSGO_HD PosePriorLin<T> pose_prior_linearize(T mx, T my, T cm, T sm, T w0, T w1, T w2, T x, T y, T c, T s) {
+    return pose_prior_linearize<T>(mx, my, cm, sm, w0, w1, w2, x, y, c, s, HuberDefault{});
+}
 
 template <typename T> struct LmPriorLin { T e0, e1, a0, a1, rho; };
-template <typename T>
-TSGO_HD LmPriorLin<T> lm_prior_linearize(T mx, T my, T w0, T w1, T lx, T ly) {
+template <typename T, typename K>
+TSGO_HD LmPriorLin<T> lm_prior_linearize(T mx, T my, T w0, T w1, T lx, T ly, const K& rk) {
     LmPriorLin<T> o;
     o.e0 = lx - mx; o.e1 = ly - my;
     T hw;
-    huber<T>(w0 * o.e0 * o.e0 + w1 * o.e1 * o.e1, o.rho, hw);
+    robustify<T>(rk, w0 * o.e0 * o.e0 + w1 * o.e1 * o.e1, o.rho, hw);
     o.a0 = hw * w0; o.a1 = hw * w1;
     return o;
+}
+template <typename T>
+TSGO_HD LmPriorLin<T> lm_prior_linearize(T mx, T my, T w0, T w1, T lx, T ly) {
+    return lm_prior_linearize<T>(mx, my, w0, w1, lx, ly, HuberDefault{});
 }
 
 // ---- pose-pose slots in general form -------------------------------------------------------------------------------------------
@@ -158,10 +205,10 @@ template <typename T> TSGO_HD void pair_apply(const T* h, T z0, T z1, T zt, T& o
 // pose (x, y, c, s; local point (pox, poy)) with the neighbour (xn, yn, cn, sn; (pnx, pny)):
 //   d = own world point - neighbour's world point  (= e at the first endpoint, -e at the second),  u = dR_own/dth p_own,  v = dR_n/dth p_n
 //   J_own^T Omega (signed residual) = [I | u]^T Omega d,   H_pp += [I | u]^T Omega [I | u],   H_pn = -[I | u]^T Omega [I | v]
-// with Omega = Huber weight * diag(w0, w1) — no direction bit needed beyond counting chi^2 once.
+// with Omega = robust weight * diag(w0, w1) — no direction bit needed beyond counting chi^2 once.
 template <typename T> struct VlmLin { T om0, om1, u0, u1, v0, v1, d0, d1, rho; };
-template <typename T>
-TSGO_HD VlmLin<T> vlm_linearize(T x, T y, T c, T s, T xn, T yn, T cn, T sn, T pox, T poy, T pnx, T pny, T w0, T w1) {
+template <typename T, typename K>
+TSGO_HD VlmLin<T> vlm_linearize(T x, T y, T c, T s, T xn, T yn, T cn, T sn, T pox, T poy, T pnx, T pny, T w0, T w1, const K& rk) {
     VlmLin<T> o;
     o.d0 = (x + c * pox - s * poy) - (xn + cn * pnx - sn * pny);
     o.d1 = (y + s * pox + c * poy) - (yn + sn * pnx + cn * pny);
@@ -169,9 +216,13 @@ TSGO_HD VlmLin<T> vlm_linearize(T x, T y, T c, T s, T xn, T yn, T cn, T sn, T po
     o.v0 = -sn * pnx - cn * pny; o.v1 = cn * pnx - sn * pny;
     const T chi2 = w0 * o.d0 * o.d0 + w1 * o.d1 * o.d1;
     T hw;
-    huber(chi2, o.rho, hw);
+    robustify(rk, chi2, o.rho, hw);
     o.om0 = hw * w0; o.om1 = hw * w1;
     return o;
+}
+template <typename T>
+TSGO_HD VlmLin<T> vlm_linearize(T x, T y, T c, T s, T xn, T yn, T cn, T sn, T pox, T poy, T pnx, T pny, T w0, T w1) {
+    return vlm_linearize<T>(x, y, c, s, xn, yn, cn, sn, pox, poy, pnx, pny, w0, w1, HuberDefault{});
 }
 template <typename T> TSGO_HD void vlm_slot(const VlmLin<T>& o, T* h) {
     h[PP_K00] = o.om0; h[PP_K01] = T(0); h[PP_K11] = o.om1;

@@ -86,6 +86,30 @@ class HipOptimizer:
         """warm_requests: the next set_graph starts the solver from nothing (a pooled handle changing hands)."""
         self.lib.tsgo_reset_history(self.h)
 
+    def set_robust(self, odom=None, lm=None, virtual=None, pose_prior=None, lm_prior=None, all=None):
+        """Robust kernel per edge class (tsgo_set_robust): each value "none" or (name, delta), name one of "huber", "cauchy",
+        "geman_mcclure"; `all` sets every class, a class argument overrides it, a class left out keeps what the handle has.  Takes effect
+        at the next linearisation and survives set_graph."""
+        r = _lib.tsgo_robust()
+        _lib.check(self.lib, self.lib.tsgo_get_robust(self.h, C.byref(r)), "tsgo_get_robust")
+        for k, v in enumerate((odom, lm, virtual, pose_prior, lm_prior)):
+            v = all if v is None else v
+            if v is None:
+                continue
+            name, delta = (v, r.delta[k]) if isinstance(v, str) else v
+            if name not in _lib.ROBUST_KERNELS or (isinstance(v, str) and name != "none"):
+                raise ValueError('a robust kernel is "none" or (name, delta) with name in %s' % sorted(_lib.ROBUST_KERNELS))
+            r.kernel[k], r.delta[k] = _lib.ROBUST_KERNELS[name], float(delta)
+        _lib.check(self.lib, self.lib.tsgo_set_robust(self.h, C.byref(r)), "tsgo_set_robust")
+
+    @property
+    def robust(self):
+        """The handle's setting read back (tsgo_get_robust): {class: "none" or (name, delta)}."""
+        r = _lib.tsgo_robust()
+        _lib.check(self.lib, self.lib.tsgo_get_robust(self.h, C.byref(r)), "tsgo_get_robust")
+        names = {v: k for k, v in _lib.ROBUST_KERNELS.items()}
+        return {c: "none" if r.kernel[k] == 0 else (names[r.kernel[k]], r.delta[k]) for k, c in enumerate(_lib.ROBUST_CLASSES)}
+
     def optimize(self, iterations):
         st = _lib.tsgo_stats()
         _lib.check(self.lib, self.lib.tsgo_optimize(self.h, iterations, C.byref(st)), "tsgo_optimize")
