@@ -254,7 +254,8 @@ int tsgo_comm_time_allreduce(tsgo_optimizer* opt, int64_t n_elements, int32_t re
  * launches of one kernel on the handle's stream, and the algorithmic bytes one launch moves.
  * which: 0 schur_lm, 1 schur_pose, 2 cg_update, 3 lin_lm, 4 lin_pose, 5 one whole PCG iteration
  * (preconditioner application included), 6 the multigrid numeric setup of one GN iteration, 7 the chi^2-only evaluation pass of a
- * rules = 2 trial (a handle created with rules = 2; to be compared with 3 + 4, the linearisation it stands in for). */
+ * rules = 2 trial (a handle created with rules = 2; to be compared with 3 + 4, the linearisation it stands in for), 8 the summary-only pass
+ * of tsgo_edge_report on the handle's graph (to be compared with 7, which reads the same tables). */
 int tsgo_time_kernel(tsgo_optimizer* opt, int32_t which, int32_t reps, double* us_per_launch, double* bytes_per_launch);
 
 /* Timing probe for the multigrid V-cycle's coarse levels (bench.py's per-kernel table): for every explicit level below
@@ -315,6 +316,35 @@ int tsgo_marginals(tsgo_optimizer* opt, const uint32_t* ids, int32_t n_ids, doub
  * Errors (< 0): those of tsgo_marginals, cov_cap < D * D, and D > 8192 (a 512 MB result). */
 int tsgo_joint_marginals(tsgo_optimizer* opt, const uint32_t* ids, int32_t n_ids, double rel_tol,
                          double* cov_out, int64_t cov_cap, int32_t* dim_out, tsgo_marginal_stats* stats /* may be NULL */);
+
+/* Per-edge residual report: which edges the robust kernels down-weighted, and by how much (what g2o's per-edge chi2() and Ceres' residual
+ * evaluation answer).  Everything is evaluated at the handle's CURRENT estimates under its current tsgo_set_robust setting, by the edge
+ * functions every linearisation runs; odom_jacobian, rules, damping and the fixed list do not enter.  rec_out receives six doubles per edge,
+ * in the edge order of the tsgo_graph the handle was given: (e0, e1, e2, s, rho, w).
+ *   e    the residual (EdgeSe2.h, EdgeSe2Point2d.h and the extensions described at tsgo_graph.e_type); e2 = 0 for LM, virtual landmark and
+ *        landmark prior edges; a virtual landmark edge reports T1 p1 - T2 p2
+ *   s    sum_k inf_k e_k^2 with the RAW information diagonal: the unrobustified chi^2 of the edge
+ *   rho  the class's kernel at s (what the edge adds to chi^2);  w = rho'(s), the scalar that multiplies Omega (1 at s = 0)
+ * stats receives, per edge class, the count, how many edges have w < 1, the sums of s and rho and the worst edge (largest s; among equal
+ * ones the lowest index), and chi2 = the robustified chi^2 (the five rho_sum added in class order: tsgo_linearize's up to summation order).
+ * Either output may be NULL, not both.  rec_out == NULL is the summary-only mode a caller polls between tsgo_optimize calls: no per-edge
+ * buffer is allocated on the device and none is copied back.  precision 64 and 32 (an f32 handle evaluates in f32; the records are
+ * widened).  The state rule of tsgo_marginals holds: the estimates, the solver history and everything the next tsgo_optimize or
+ * tsgo_linearize reads stay bit for bit what they were.  Errors (< 0, text in tsgo_last_error): a NULL handle, both outputs NULL, no graph
+ * set, cap_edges < n_edges with rec_out given, an edge-sharded handle (world > 1: not supported). */
+typedef struct tsgo_edge_class_summary {
+    int64_t edges;          /* edges of this class in the graph */
+    int64_t downweighted;   /* of them, those with w < 1 */
+    double  s_sum, rho_sum; /* sum of s, sum of rho(s) */
+    double  s_max;          /* largest s (0 when the class is empty) */
+    int64_t s_max_edge;     /* its index in tsgo_graph edge order; ties: the lowest index; -1 when the class is empty */
+} tsgo_edge_class_summary;
+typedef struct tsgo_edge_report_stats {
+    tsgo_edge_class_summary cls[5];   /* indexed by tsgo_graph.e_type */
+    double chi2;                      /* sum of the five rho_sum, folded in class order */
+    double ms_total;
+} tsgo_edge_report_stats;
+int tsgo_edge_report(tsgo_optimizer* opt, double* rec_out /* may be NULL */, int64_t cap_edges, tsgo_edge_report_stats* stats /* may be NULL */);
 
 const char* tsgo_last_error(void);
 

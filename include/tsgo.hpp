@@ -177,6 +177,25 @@ public:
         return cov;
     }
 
+    // Per-edge residual report at the current estimates (tsgo_edge_report): six doubles per edge of the graph last handed to Optimize, in
+    // its edge order: (e0, e1, e2, s, rho, w); *stats (if given) receives the per-class summary.  EdgeSummary: the summary alone (no per-edge
+    // buffer anywhere).  Both throw on an error (no graph yet, an edge-sharded handle).
+    std::vector<double> EdgeReport(tsgo_edge_report_stats* stats = nullptr) {
+        tsgo_edge_report_stats s;
+        if (tsgo_edge_report(handle, nullptr, 0, &s)) throw std::runtime_error(tsgo_last_error());
+        int64_t n = 0;
+        for (const tsgo_edge_class_summary& c : s.cls) n += c.edges;
+        std::vector<double> rec((size_t)n * 6);
+        if (tsgo_edge_report(handle, rec.empty() ? nullptr : rec.data(), n, &s)) throw std::runtime_error(tsgo_last_error());
+        if (stats) *stats = s;
+        return rec;
+    }
+    tsgo_edge_report_stats EdgeSummary() {
+        tsgo_edge_report_stats s;
+        if (tsgo_edge_report(handle, nullptr, 0, &s)) throw std::runtime_error(tsgo_last_error());
+        return s;
+    }
+
 private:
     unsigned iterations;
     tsgo_optimizer* handle = nullptr;

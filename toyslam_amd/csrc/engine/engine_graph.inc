@@ -264,6 +264,7 @@
         if (last_set_reused) return refill(g);
         if (int rc = carry_out()) return rc;
         release();
+        drop_report_maps();      // the slot -> input-edge maps of tsgo_edge_report lived in the slabs just released and described the old tables
         BuildOptions bo; bo.rank = cfg.rank; bo.world = cfg.world; bo.lanes_per_pose = cfg.lanes_per_pose; bo.lanes_per_lm = cfg.lanes_per_lm;
         bo.fill_planes = false;
         const std::string err = build_problem(g, bo, pr);

@@ -78,7 +78,8 @@
         return n;
     }
 
-    // which: 0 schur_lm, 1 schur_pose, 2 cg_update, 3 lin_lm, 4 lin_pose, 5 one whole PCG iteration, 6 multigrid setup, 7 the chi^2-only pass (rules = 2)
+    // which: 0 schur_lm, 1 schur_pose, 2 cg_update, 3 lin_lm, 4 lin_pose, 5 one whole PCG iteration, 6 multigrid setup, 7 the chi^2-only pass (rules = 2),
+    // 8 the summary-only pass of tsgo_edge_report (engine_report.inc; reads what 7 reads plus the slot -> edge maps)
     int time_kernel(int which, int reps, double* us, double* bytes) override {
         if (!have_graph_data) return set_error(-3, "tsgo_time_kernel: no graph set");
         HIP_OK(hipSetDevice(cfg.device));
@@ -95,6 +96,10 @@
         // whole iterations are timed with the stopping test disabled: a converged solve turns every kernel into an early exit
         struct TolGuard { double& tol; double keep; ~TolGuard() { tol = keep; } } tol_guard{cfg.pcg_rel_tol, cfg.pcg_rel_tol};
         if (which == 5) cfg.pcg_rel_tol = 0;
+        if (which == 8) {
+            if (cfg.world > 1 || collective()) return set_error(-1, "tsgo_time_kernel: 8 (the edge report's pass): edge-sharded handles (world > 1) are not supported");
+            if (int rc = report_prepare()) return rc;
+        }
         for (int pass = 0; pass < 2; ++pass) {
             const int n = pass == 0 ? 3 : reps;
             HIP_OK(hipEventRecord(ev[0], stream));
@@ -111,6 +116,7 @@
                     case 3: launch_lin_lm(); break;
                     case 4: launch_lin_pose_only(); break;
                     case 7: if (!lm_rules()) return set_error(-1, "tsgo_time_kernel: 7 (the chi^2-only pass) needs a handle created with rules = 2"); launch_chi2(lm_red); break;
+                    case 8: launch_report(nullptr); break;
                     case 6: if (amg_on) { if (int rc = launch_amg_setup()) return rc; } break;
                     default: if (int rc = launch_iteration(0)) return rc; if (int rc = launch_iteration(1)) return rc; break;
                 }
@@ -125,8 +131,8 @@
             }
         }
         cfg.pcg_rel_tol = tol_guard.keep;
-        const double tab[8] = {b_lm, b_pose, b_upd, b_linlm, b_linpose, (amg_on ? 3.0 : 1.0) * (b_lm + b_pose) + b_upd, 0.0, bytes_chi2()};
-        *bytes = tab[std::min(std::max(which, 0), 7)];
+        const double tab[9] = {b_lm, b_pose, b_upd, b_linlm, b_linpose, (amg_on ? 3.0 : 1.0) * (b_lm + b_pose) + b_upd, 0.0, bytes_chi2(), which == 8 ? bytes_report(false) : 0.0};
+        *bytes = tab[std::min(std::max(which, 0), 8)];
         // leave a consistent state behind
         return do_linearize(&chi2);
     }

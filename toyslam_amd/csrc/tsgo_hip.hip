@@ -11,6 +11,7 @@
 //   engine/engine_solve.inc        the Gauss-Newton loop, the PCG drivers, read-outs
 //   engine/engine_probes.inc       timing probes (bench.py)
 //   engine/engine_marginals.inc    tsgo_marginals, tsgo_joint_marginals: batched PCG for blocks of H^-1
+//   engine/engine_report.inc       tsgo_edge_report: per-edge residual records and the per-class summary
 //   engine/engine_testing.inc      tsgo_testing_apply (TSGO_TESTING builds only): the operators PCG applies, read out column by column
 //
 // There is NO CPU fallback in this file: every entry point that computes needs a gfx950 device and
@@ -47,6 +48,7 @@
 #include "tsgo_kernels.h"
 #include "tsgo_lm_kernels.h"
 #include "tsgo_marginal_kernels.h"
+#include "tsgo_report_kernels.h"
 #include "tsgo_sym_kernels.h"
 
 namespace {
@@ -146,6 +148,7 @@ struct IEngine {
     virtual void get_robust(tsgo_robust* out) const = 0;
     virtual int marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, tsgo_marginal_stats* st) = 0;
     virtual int joint_marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, int64_t cov_cap, int* dim_out, tsgo_marginal_stats* st) = 0;
+    virtual int edge_report(double* rec_out, int64_t cap_edges, tsgo_edge_report_stats* st) = 0;
 #ifdef TSGO_TESTING
     virtual int testing_apply(int which, const double* in, double* out, int n_cols) = 0;
 #endif
@@ -430,6 +433,7 @@ template <typename T> struct Engine : IEngine {
 #include "engine/engine_solve.inc"
 #include "engine/engine_probes.inc"
 #include "engine/engine_marginals.inc"
+#include "engine/engine_report.inc"
 #ifdef TSGO_TESTING
 #include "engine/engine_testing.inc"
 #endif
@@ -538,6 +542,10 @@ int tsgo_joint_marginals(tsgo_optimizer* o, const uint32_t* ids, int32_t n_ids, 
                          tsgo_marginal_stats* stats) {
     if (!o) return tsgo::set_error(-1, "tsgo_joint_marginals: null handle");
     return o->eng->joint_marginals(ids, n_ids, rel_tol, cov_out, cov_cap, dim_out, stats);
+}
+int tsgo_edge_report(tsgo_optimizer* o, double* rec_out, int64_t cap_edges, tsgo_edge_report_stats* stats) {
+    if (!o) return tsgo::set_error(-1, "tsgo_edge_report: null handle");
+    return o->eng->edge_report(rec_out, cap_edges, stats);
 }
 void tsgo_reset_history(tsgo_optimizer* o) {
     if (o && o->eng) o->eng->reset_history();

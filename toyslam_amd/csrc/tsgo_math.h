@@ -231,6 +231,32 @@ template <typename T> TSGO_HD void vlm_slot(const VlmLin<T>& o, T* h) {
     h[PP_KAPPA] = o.om0 * o.u0 * o.v0 + o.om1 * o.u1 * o.v1;
 }
 
+// Per-edge report (tsgo_edge_report, include/tsgo.h; tsgo_report_kernels.h): what an edge function above computed, restated as one
+// record (e, s, rho, w) from its output and the edge's RAW weights.  s = sum_k w_k e_k^2 is written term for term as the edge function
+// writes its chi^2, and rho, w come from robustify on that s (w is the scalar that multiplies Omega: never a0 / w0, which is 0 / 0 on a
+// zero weight).  e2 = 0 where the class has two components; a virtual landmark edge reports d as seen from the pose the function was
+// handed first (the edge's first pose at its first endpoint: e = T1 p1 - T2 p2).
+template <typename T> struct EdgeRecord { T e0, e1, e2, s, rho, w; };
+template <typename T, typename K> TSGO_HD EdgeRecord<T> edge_record2(T e0, T e1, T w0, T w1, const K& rk) {
+    EdgeRecord<T> r;
+    r.e0 = e0; r.e1 = e1; r.e2 = T(0);
+    r.s = w0 * e0 * e0 + w1 * e1 * e1;
+    robustify(rk, r.s, r.rho, r.w);
+    return r;
+}
+template <typename T, typename K> TSGO_HD EdgeRecord<T> edge_record3(T e0, T e1, T e2, T w0, T w1, T w2, const K& rk) {
+    EdgeRecord<T> r;
+    r.e0 = e0; r.e1 = e1; r.e2 = e2;
+    r.s = w0 * e0 * e0 + w1 * e1 * e1 + w2 * e2 * e2;
+    robustify(rk, r.s, r.rho, r.w);
+    return r;
+}
+template <typename T, typename K> TSGO_HD EdgeRecord<T> edge_record(const LmLin<T>& o, T w0, T w1, const K& rk) { return edge_record2<T>(o.e0, o.e1, w0, w1, rk); }
+template <typename T, typename K> TSGO_HD EdgeRecord<T> edge_record(const OdomLin<T>& o, const T* w, const K& rk) { return edge_record3<T>(o.e[0], o.e[1], o.e[2], w[0], w[1], w[2], rk); }
+template <typename T, typename K> TSGO_HD EdgeRecord<T> edge_record(const VlmLin<T>& o, T w0, T w1, const K& rk) { return edge_record2<T>(o.d0, o.d1, w0, w1, rk); }
+template <typename T, typename K> TSGO_HD EdgeRecord<T> edge_record(const PosePriorLin<T>& o, T w0, T w1, T w2, const K& rk) { return edge_record3<T>(o.e0, o.e1, o.et, w0, w1, w2, rk); }
+template <typename T, typename K> TSGO_HD EdgeRecord<T> edge_record(const LmPriorLin<T>& o, T w0, T w1, const K& rk) { return edge_record2<T>(o.e0, o.e1, w0, w1, rk); }
+
 // Symmetric 2x2 inverse (xx, xy, yy).  A singular block (vertex without edges) maps to zero, which
 // leaves that vertex where it is (the reference's rank-revealing QR does the same).
 template <typename T> TSGO_HD void inv_sym2(T xx, T xy, T yy, T& ixx, T& ixy, T& iyy) {

@@ -50,6 +50,7 @@ class HipOptimizer:
         self.h = C.c_void_p()
         _lib.check(self.lib, self.lib.tsgo_create(C.byref(cfg), C.byref(self.h)), "tsgo_create")
         self.n_vertices = 0
+        self.n_edges = 0
         self._v_in = None
         self._ids_types = None
 
@@ -79,6 +80,7 @@ class HipOptimizer:
         cg = g.c_struct()
         _lib.check(self.lib, self.lib.tsgo_set_graph(self.h, C.byref(cg)), "tsgo_set_graph")
         self.n_vertices = len(g.v_id)
+        self.n_edges = len(g.e_type)
         self._ids_types = (g.v_id, g.v_type)      # joint_marginals: the row count of each queried id
         self._v_in = g.v_pos.copy() if self.cfg.world > 1 else None    # a shard returns its own landmarks; the others keep their input
 
@@ -170,6 +172,23 @@ class HipOptimizer:
         _lib.check(self.lib, self.lib.tsgo_joint_marginals(self.h, idp, len(ids), float(rel_tol), cov.ctypes.data if D else None, D * D,
                                                             C.byref(dim), C.byref(st)), "tsgo_joint_marginals")
         return cov, offsets, {f: getattr(st, f) for f, _t in st._fields_}
+
+    def edge_report(self, records=True):
+        """Per-edge residual report at the current estimates under the handle's robust setting (tsgo_edge_report): (rec, summary).
+        rec: dict of views over one (E, 6) array in the edge order of the graph given to set_graph — e (E, 3), s, rho, w (E,) — and the
+        array itself as rec["all"]; None with records=False (summary only: no per-edge buffer on the device, nothing copied back).
+        summary: {class: dict(edges, downweighted, s_sum, rho_sum, s_max, s_max_edge)} over _lib.ROBUST_CLASSES, plus "chi2"."""
+        st = _lib.tsgo_edge_report_stats()
+        rec = None
+        if records:
+            arr = np.zeros((self.n_edges, 6))
+            _lib.check(self.lib, self.lib.tsgo_edge_report(self.h, arr.ctypes.data, self.n_edges, C.byref(st)), "tsgo_edge_report")
+            rec = dict(e=arr[:, 0:3], s=arr[:, 3], rho=arr[:, 4], w=arr[:, 5], all=arr)
+        else:
+            _lib.check(self.lib, self.lib.tsgo_edge_report(self.h, None, 0, C.byref(st)), "tsgo_edge_report")
+        summary = {c: {f: getattr(st.cls[k], f) for f, _t in _lib.tsgo_edge_class_summary._fields_} for k, c in enumerate(_lib.ROBUST_CLASSES)}
+        summary["chi2"] = st.chi2
+        return rec, summary
 
     def time_kernel(self, which, reps=50):
         us = C.c_double(); nbytes = C.c_double()
