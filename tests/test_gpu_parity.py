@@ -533,16 +533,20 @@ def test_cycle_storage_16_and_32_give_the_same_answer():
     print("PCG iterations per solve, cycle storage f32 %s, packed half %s" % (list(r32["cg_iters"]), list(r16["cg_iters"])))
 
 
+def _odometry_chain(n_poses):
+    """The poses and ODOM edges of a synthetic graph, first pose fixed: under the analytic ODOM Jacobians a beam of n_poses links."""
+    g = synth.make(n_poses, 13, loop_closures=2, seed=7)
+    keep = g.e_type == 0; pose = g.v_type == 0
+    return GraphArrays(g.v_id[pose], g.v_type[pose], g.v_pos[pose], g.e_type[keep], g.e_ids[keep], g.e_meas[keep], g.e_inf[keep], np.array([0], np.uint32))
+
+
 def test_ill_conditioned_chain_leaves_the_packed_cycle_format_by_itself():
     """An odometry-only chain under the analytic ODOM Jacobians is a 12 000-link beam: thousands of multigrid PCG iterations per
     solve, and coarse operators that are differences of large entries — rounded to the packed format's 11 bits they are no
     longer positive definite (with `cycle_storage = 16` forced and no way out: breakdown, 20 000 block-Jacobi iterations,
     TSGO_STOP_SOLVER; tools/research/hard_chain.py).  The engine recognises such a structure by its first solve (> 64 iterations)
     and moves its cycle to f32 copies: same run as a handle created with cycle_storage = 32."""
-    from toyslam_amd.graph import GraphArrays
-    g = synth.make(12000, 13, loop_closures=2, seed=7)
-    keep = g.e_type == 0; pose = g.v_type == 0
-    g = GraphArrays(g.v_id[pose], g.v_type[pose], g.v_pos[pose], g.e_type[keep], g.e_ids[keep], g.e_meas[keep], g.e_inf[keep], np.array([0], np.uint32))
+    g = _odometry_chain(12000)
     res = {}
     for bits in (32, 16):
         o = HipOptimizer(pcg_rel_tol=1e-10, odom_jacobian="analytic", cycle_storage=bits)
@@ -556,6 +560,34 @@ def test_ill_conditioned_chain_leaves_the_packed_cycle_format_by_itself():
     assert r32["cycle_storage_now"] == 32 and r16["cycle_storage_now"] == 32          # the default handle has switched
     np.testing.assert_allclose(r16["chi2"], r32["chi2"], rtol=1e-6)
     assert util.max_vertex_diff(v16, v32, g.v_type) < 1e-3 * max(1.0, float(np.abs(v32).max()) / 100.0)      # the conditioning of a 12k-link beam
+
+
+def test_a_handle_that_left_the_packed_format_starts_packed_again():
+    """What a hard graph drove the cycle to is forgotten at the next tsgo_set_graph, refill or new structure: the handle starts from the
+    configured (packed) storage again and does, bit for bit, what a fresh one does.  The chain keeps its 12 000 links (0.07 s per solve;
+    chains of 1 000 to 6 000 links leave the packed format too, but their packed and f32 counts lie within a few per cent of each other):
+    its first solve took 1 078 PCG iterations on the packed copies, > 64, converged, and left the cycle in f32 copies without a fallback;
+    a handle created with cycle_storage = 32 takes 952, which is what a refilled handle that had stayed in f32 would take."""
+    chain, small = _odometry_chain(12000), synth.make(600, 8, loop_closures=5, seed=1)
+    cfg = dict(pcg_rel_tol=1e-10, odom_jacobian="analytic")
+    o, fresh = HipOptimizer(**cfg), HipOptimizer(**cfg)
+    try:
+        o.set_graph(chain); r1 = o.optimize(1)
+        print("chain of %d links: first solve %s PCG iterations, cycle storage now %d" % (chain.v_id.size, list(r1["cg_iters"]), r1["cycle_storage_now"]))
+        assert r1["cycle_storage_now"] == 32 and r1["fallbacks"] == 0      # the condition of this test: the chain left the packed format
+        o.set_graph(chain); r2 = o.optimize(1)
+        assert r2["structure_reused"]
+        np.testing.assert_array_equal(r2["chi2"], r1["chi2"])
+        np.testing.assert_array_equal(r2["cg_iters"], r1["cg_iters"])      # packed again, and left at the same solve (a handle still in f32 takes fewer)
+        assert r2["cycle_storage_now"] == 32
+        o.set_graph(small); r3 = o.optimize(3); v3 = o.vertices()
+        fresh.set_graph(small); rf = fresh.optimize(3); vf = fresh.vertices()
+        assert not r3["structure_reused"] and r3["cycle_storage_now"] == 16
+        np.testing.assert_array_equal(r3["chi2"], rf["chi2"])
+        np.testing.assert_array_equal(r3["cg_iters"], rf["cg_iters"])
+        np.testing.assert_array_equal(v3, vf)
+    finally:
+        o.close(); fresh.close()
 
 
 @pytest.mark.parametrize("n_poses,lc", [(3000, 20), (30000, 300)])

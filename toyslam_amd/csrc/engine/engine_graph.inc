@@ -137,9 +137,9 @@
         return false;
     }
 
-    // solver state a fresh engine starts from: whatever was learnt on the previous graph must not leak into this one
+    // solver state a fresh engine starts from (SolverMemory, tsgo_hip.hip): whatever was learnt on the previous graph, cycle format and diagonal raise included, must not leak into this one
     int reset_solver_state() {
-        have_prev = false; n_prev = 0; n_tested = 0; carried = false; predicted_cg = 0; n_decided = 0; n_slow_seen = 0; n_host_slow = 0; ref_us_per_iter = 0; n_paced_slow = 0; std::fill(iters_by_age, iters_by_age + kAgeSlots, 0); lin_count = 0; n_lins = 0; hier_age = -1; iters_fresh = 0; iters_last = 0;
+        mem = fresh_memory();
         const T one = 1;
         { if (int rc_ = copy_sync(one_dev, &one, sizeof(T), hipMemcpyHostToDevice)) return rc_; }
         { if (int rc_ = copy_sync(gscale_dev, &one, sizeof(T), hipMemcpyHostToDevice)) return rc_; }
@@ -157,26 +157,24 @@
     // vertex id when it is not (the slabs are reused by the new tables, so the vectors are parked in an allocation of their own).
     struct Carry { int n = 0, n_tested = 0, P = 0; std::vector<uint32_t> pose_id; double err[kMaxWarm] = {}; } carry;
     T* carry_dev = nullptr; size_t carry_cap = 0;
-    bool carried = false;        // the history came from the previous request: the first warm start made from it is checked (do_solve)
-    int n_carried = 0, n_carry_dropped = 0;
     int carry_out() {
         carry.n = 0;
-        if (!cfg.warm_requests || !have_graph_data || !have_prev || n_prev <= 0 || pr.P <= 0) return 0;
+        if (!cfg.warm_requests || !have_graph_data || !mem.have_prev || mem.n_prev <= 0 || pr.P <= 0) return 0;
         const size_t n = (size_t)pr.P * 3;
-        if ((size_t)n_prev * n > carry_cap) {
+        if ((size_t)mem.n_prev * n > carry_cap) {
             if (carry_dev) { (void)hipFree(carry_dev); carry_dev = nullptr; carry_cap = 0; }
             const size_t want = (size_t)kMaxWarm * (n + n / 4);      // a growing graph comes back a little larger every time
             HIP_OK(hipMalloc((void**)&carry_dev, want * sizeof(T)));
             carry_cap = want;
         }
-        for (int j = 0; j < n_prev; ++j) HIP_OK(hipMemcpyAsync(carry_dev + (size_t)j * n, hist[j], n * sizeof(T), hipMemcpyDeviceToDevice, stream));
+        for (int j = 0; j < mem.n_prev; ++j) HIP_OK(hipMemcpyAsync(carry_dev + (size_t)j * n, hist[j], n * sizeof(T), hipMemcpyDeviceToDevice, stream));
         std::vector<T> e((size_t)kMaxWarm * nbC);
         if (int rc = copy_sync(e.data(), warm_err, e.size() * sizeof(T), hipMemcpyDeviceToHost)) return rc;
         for (int m = 0; m < kMaxWarm; ++m) { double s = 0; for (int k = 0; k < nbC; ++k) s += (double)e[(size_t)m * nbC + k]; carry.err[m] = s; }
         carry.pose_id.resize((size_t)pr.P);
         for (int i = 0; i < pr.P; ++i) carry.pose_id[(size_t)i] = structure.v_id[(size_t)pr.pose_vertex[(size_t)i]];
         HIP_OK(hipStreamSynchronize(stream));
-        carry.P = pr.P; carry.n = n_prev; carry.n_tested = n_tested;
+        carry.P = pr.P; carry.n = mem.n_prev; carry.n_tested = mem.n_tested;
         return 0;
     }
     // after the new tables exist (hist, warm_err allocated; solver state reset): the parked deltas into the new pose numbering
@@ -208,13 +206,13 @@
         for (int m = 0; m < kMaxWarm; ++m) e[(size_t)m * nbC] = (T)carry.err[m];
         if (int rc = copy_sync(warm_err, e.data(), e.size() * sizeof(T), hipMemcpyHostToDevice)) return rc;
         HIP_OK(hipStreamSynchronize(stream));
-        have_prev = true; n_prev = n_old; n_tested = carry.n_tested; carried = true; ++n_carried;      // (a grown graph IS young where it grew: n_lins stays 0)
+        mem.have_prev = true; mem.n_prev = n_old; mem.n_tested = carry.n_tested; mem.carried = true; ++n_carried;      // (a grown graph IS young where it grew: n_lins stays 0)
         return 0;
     }
 
     // tsgo_reset_history: the next tsgo_set_graph starts the solver from nothing, whatever warm_requests says (a pooled handle
     // changing hands: one client's deltas must not seed another client's solves)
-    void reset_history() override { have_prev = false; n_prev = 0; n_tested = 0; carried = false; carry.n = 0; }
+    void reset_history() override { mem.have_prev = false; mem.n_prev = 0; mem.n_tested = 0; mem.carried = false; carry.n = 0; }
 
     int refill(const tsgo_graph& g) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -228,13 +226,8 @@
         return 0;
     }
     int refill_values(const tsgo_graph& g) {
-        // a refilled handle must do, bit for bit, what a fresh one does: the cycle starts from the configured storage again (a
-        // structure that left the packed format leaves it again, at the same solve)
-        if (cy16 != (cfg.cycle_storage != 32)) {
-            cy16 = cfg.cycle_storage != 32;
-            if (cg_graph) { (void)hipGraphExecDestroy(cg_graph); cg_graph = nullptr; }
-        }
-        hier_shift = hier_shift_cfg;      // (... and a hierarchy whose diagonal was raised after a breakdown starts unraised again, do_solve)
+        // the cycle goes back to the configured storage below (reset_solver_state): a replay captured with the other format's kernels goes with it
+        if (mem.cy16 != fresh_memory().cy16 && cg_graph) { (void)hipGraphExecDestroy(cg_graph); cg_graph = nullptr; }
         if (int rc = stage_values(g, true)) return rc;
         if (int rc = stage_priors(g)) return rc;
         keep_prior_weights(g);
@@ -248,10 +241,9 @@
                 if (!rel.empty()) { if (int rc_ = copy_sync(lv[l].rel, stage, rel.size() * sizeof(T), hipMemcpyHostToDevice)) return rc_; }
             }
         }
-        const bool keep = cfg.warm_requests && have_prev && n_prev > 0;      // same structure, same numbering: the history stays where it is
-        const int keep_prev = n_prev, keep_tested = n_tested;
+        const SolverMemory old = mem;      // same structure, same numbering: under warm_requests the history stays where it is
         if (int rc = reset_solver_state()) return rc;
-        if (keep) { have_prev = true; n_prev = keep_prev; n_tested = keep_tested; carried = true; ++n_carried; n_lins = kYoungLins; }      // a continued graph is not a young one
+        if (cfg.warm_requests && old.have_prev && old.n_prev > 0) { mem.have_prev = true; mem.n_prev = old.n_prev; mem.n_tested = old.n_tested; mem.carried = true; ++n_carried; mem.n_lins = kYoungLins; }      // a continued graph is not a young one
         HIP_OK(hipStreamSynchronize(stream));
         return 0;
     }
@@ -363,8 +355,6 @@
         // second step, a connection's second request with this structure: Engine::optimize).  A front-end that grows its graph
         // sends a new structure every time and never pays it.
         optimize_calls_on_tables = 0;
-        cy16 = cfg.cycle_storage != 32;
-        hier_shift = hier_shift_cfg;
         if (say) std::fprintf(stderr, "[tsgo] set_graph: %d slabs (%.0f MB) hold the graph; hipMalloc calls of this handle so far: %d, %.1f ms\n", (int)slabs.size(), slab_total / 1048576.0, n_malloc, ms_in_malloc);
         structure.take(g);
         ms_setup = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -51,7 +51,6 @@
         return 0;
     }
 #define UP(dst, vec) if (int rc = upload_i32(&dst, vec)) return rc
-    bool schur_dev = false;      // level 0's pattern and contribution lists were built on the device (run_device_schur)
     int upload_schur_lists() {
         if (schur_dev) return 0;
         UP(sc_ptr, amg.schur.ptr); UP(sc_optr, amg.schur.od_ptr);
@@ -268,7 +267,6 @@
         if (int rc = dalloc(&rho_part, 16 * 2 * kRhoBlocks)) return rc;
         if (h_rho) (void)hipHostFree(h_rho);
         HIP_OK(hipHostMalloc((void**)&h_rho, sizeof(T) * 16 * 2 * kRhoBlocks));
-        lin_count = 0; hier_age = -1;
         {   // S is symmetric: k_schur_blocks sums the blocks on and above the diagonal, the others are mirrored (half of the set-up's most
             // expensive gather: 137 us per hierarchy build at 100k poses)
             DevLevel<T>& L0 = lv[0];

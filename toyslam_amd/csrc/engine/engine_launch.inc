@@ -24,7 +24,6 @@
     }
     std::string lvl(const char* role, size_t l) const { return std::string(role) + " L" + std::to_string(l); }
     // algorithmic bytes of the table kernels (DESIGN.md section 4) and of the block-row kernels of the cycle
-    double od_live = -1;      // live ODOM slots of this shard (the byte models'), counted once per structure
     double od_slots_live() { if (od_live < 0) { od_live = 0; for (uint32_t e : pr.odom.edge) od_live += e != kNoEdge; } return od_live; }
     double bytes_schur_lm(bool low) const { const double s = low ? 4 : sizeof(T), v = sizeof(T); return (double)pr.n_lm_edges * (4 + 4 * s) + pr.P * 5.0 * v + pr.L * 5.0 * v; }
     double bytes_schur_pose(bool low) { const double s = low ? 4 : sizeof(T), v = sizeof(T); return (double)pr.n_lm_edges * (4 + 4 * s) + pr.L * 2.0 * v + pr.P * 14.0 * v + od_slots_live() * (4 + 6 * v); }
@@ -49,7 +48,7 @@
     PriorArgs<T> lm_prior_args() const { return PriorArgs<T>{pri_l_off, pri_l, pri_lchi, 0}; }
     static PriorArgs<T> no_priors() { return PriorArgs<T>{nullptr, nullptr, nullptr, 0}; }
     static GateArgs<T> no_gate() { return GateArgs<T>{nullptr, nullptr, nullptr, 0, T(0), nullptr, 0}; }
-    // Robust kernels per edge class (tsgo_set_robust): a property of the HANDLE (it survives tsgo_set_graph), read by every launch that
+    // Robust kernels per edge class (tsgo_set_robust): belongs to the HANDLE (it survives tsgo_set_graph; tsgo_hip.hip lists the lifetimes), read by every launch that
     // robustifies.  A setting equal to the default takes the RK = 0 instantiations — the compile-time Huber, exactly what was launched
     // before the setting existed; anything else the RK = 1 ones, which read kind and width from the by-value argument below.
     tsgo_robust robust = default_robust();
@@ -68,7 +67,7 @@
     int set_robust(const tsgo_robust& r) override {
         if (!same_robust(r, default_robust()) && cfg.world > 1)
             return set_error(-1, "tsgo_set_robust: a non-default robust kernel is not supported on an edge-sharded handle (world > 1)");
-        if (!same_robust(r, robust)) hier_age = -1;      // the weights may move wholesale: the next linearisation builds a fresh hierarchy
+        if (!same_robust(r, robust)) mem.hier_age = -1;      // the weights may move wholesale: the next linearisation builds a fresh hierarchy
         robust = r; robust.reserved = 0;
         return 0;
     }
@@ -155,14 +154,14 @@
         const int n_sum = n_upper0 >= 0 ? n_upper0 : L0.nnzA;
         hipLaunchKernelGGL((k_schur_blocks<T>), dim3(grid_for(n_sum)), dim3(kBlock), 0, stream, n_sum, L0.A_row, L0.A_col, sc_ptr, sc_si, sc_sk,
                            sc_optr, sc_os, tp, (const T*)to.dyn, to.slots, (const T*)lmrec, (const T*)ps, (const T*)part, L0.A, pr.rank == 0 ? 1 : 0,
-                           to.idx, oj() ? 1 : 0, (const int*)(n_upper0 >= 0 ? upper0 : nullptr), (const int*)(n_upper0 >= 0 ? lower0 : nullptr), (T)hier_shift);
+                           to.idx, oj() ? 1 : 0, (const int*)(n_upper0 >= 0 ? upper0 : nullptr), (const int*)(n_upper0 >= 0 ? lower0 : nullptr), (T)mem.hier_shift);
         if (int rc = allreduce_h(L0.A, (size_t)L0.nnzA * 9)) return rc;
-        if (explicit0) pick<0, 1>(cy16, [&](auto pk) { launch(k_to_planes<T, pk>, grid_for(L0.n, 8), L0.n, (const int*)L0.A_ptr, (const H*)L0.A, L0.Apm); });
+        if (explicit0) pick<0, 1>(mem.cy16, [&](auto pk) { launch(k_to_planes<T, pk>, grid_for(L0.n, 8), L0.n, (const int*)L0.A_ptr, (const H*)L0.A, L0.Apm); });
         for (size_t l = 0; l < lv.size(); ++l) {
             DevLevel<T>& L = lv[l];
             H* Anext = l + 1 < lv.size() ? lv[l + 1].A : A_last;
             hipLaunchKernelGGL((k_block_inv<T>), dim3(grid_for(L.n)), dim3(kBlock), 0, stream, L.n, L.diag, (const H*)L.A, L.Dinv);
-            pick<0, 1>(cy16, [&](auto pk) {
+            pick<0, 1>(mem.cy16, [&](auto pk) {
                 launch(k_prolongator<T, pk>, grid_for(L.nnzP), L.nnzP, L.P_row, L.p_self, L.ps_ptr, L.ps_x, L.ps_y, (const H*)L.A, (const H*)L.Dinv, (const T*)L.rel, (T)kProlongOmega, L.P,
                        L.p_to_r, L.Rv, (const int*)L.P_ptr, (const int*)L.P_col, (const int*)L.R_ptr, L.Ppm, L.Rpm);
             });
@@ -173,7 +172,7 @@
                 const int* rows_next = packed_next ? (const int*)lv[l + 1].A_row : (const int*)nullptr;
                 const int* ptr_next = packed_next ? (const int*)lv[l + 1].A_ptr : (const int*)nullptr;
                 uint32_t* pm_next = packed_next ? lv[l + 1].Apm : (uint32_t*)nullptr;
-                pick<0, 1>(cy16, [&](auto pk) { launch(k_mirror_pack<T, pk>, grid_for(L.nnzNext), L.nnzNext, (const int*)L.as_mirror, Anext, rows_next, ptr_next, pm_next); });
+                pick<0, 1>(mem.cy16, [&](auto pk) { launch(k_mirror_pack<T, pk>, grid_for(L.nnzNext), L.nnzNext, (const int*)L.as_mirror, Anext, rows_next, ptr_next, pm_next); });
             }
         }
         hipLaunchKernelGGL((k_dense_inverse<T>), dim3(1), dim3(kDenseThreads), 0, stream, nb_last, last_ptr, last_col, (const H*)A_last, inv_last);
@@ -202,7 +201,7 @@
     }
     // A block-row kernel with `lpr` lanes per row over the cycle-format copies: f(LPR, PK, grid, xcd), PK = packed half (1) or f32 (0) blocks
     template <typename F> void pick_block_row(int lpr, int n_rows, F&& f) {
-        pick<4, 8, 16, 32, 64>(lpr, [&](auto lanes) { pick<0, 1>(cy16, [&](auto pk) {
+        pick<4, 8, 16, 32, 64>(lpr, [&](auto lanes) { pick<0, 1>(mem.cy16, [&](auto pk) {
             int xcd = 0;
             const int grid = lpr_grid(n_rows, lanes, &xcd);
             f(lanes, pk, grid, xcd);
@@ -340,7 +339,7 @@
             const int n3 = L.n * 3, nd = lv[nl - 1].n * 3;
             PF((double)n3 * nd * sizeof(float) + (double)(n3 + nd) * cv_bytes(), lvl("t = E^T r of", nl - 2).c_str(), "k_rowdot_wg", tname(), tname_of<V>());
             hipLaunchKernelGGL((k_rowdot_wg<T, V>), dim3(nd), dim3(kBlock), 0, stream, nd, n3, (const float*)tail_Etf, cv(L.r), v(tail_t), s);
-            pick<0, 1>(cy16, [&](auto pk) {
+            pick<0, 1>(mem.cy16, [&](auto pk) {
                 PF(bytes_sweep(L) + (double)n3 * nd * sizeof(float), lvl("cycles of", nl - 2).c_str(), "k_tail_up", tname(), pk, tname_of<V>());
                 launch(k_tail_up<T, pk, V>, L.n, L.n, (const int*)L.A_ptr, (const int*)L.A_col, (const uint32_t*)L.Apm, (const H*)L.Dinv, (const T*)(omega_dev + nl - 2), cv(L.z), nd, (const float*)tail_Gf, cv(tail_t), v(L.z2), s);
             });

@@ -6,7 +6,7 @@
 // State rule: the call linearises at the current estimates (lambda = 0) and builds a fresh hierarchy IN the handle's own buffers, so
 // before it touches anything it copies every byte of the handle's device slabs aside and afterwards copies them back (plus the two host
 // fields these launches write: lambda and the smoother damping per level).  Everything the next tsgo_optimize reads is then what it
-// was, bit for bit; no counter of the solver (n_lins, lin_count, hier_age, the warm-start history, cycle storage, hier_shift) is touched.
+// was, bit for bit; nothing of the solver's memory (Engine::mem: hierarchy age, warm-start history, cycle storage, ...) is touched.
     // Columns per launch chain (research: TSGO_MARGINAL_WIDTH = 1, 8 or 16).  Measured at config 3 (profiles/r06_marginals_timing.jsonl):
     // under the multigrid cycle 16 columns solve 264 columns/s against 139 at 8 and 24 at 1; block-Jacobi batches (thousands of short
     // iterations) run 0.19 ms per iteration at 8 columns and 0.47 at 16, so they take 8.

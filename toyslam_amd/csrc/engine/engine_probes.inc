@@ -34,6 +34,7 @@
         return n;
     }
 
+    struct TolGuard { double& tol; double keep; ~TolGuard() { tol = keep; } };      // puts cfg.pcg_rel_tol back on every way out of a probe that zeroes it
     // One PCG iteration kernel by kernel, in situ: `reps` iterations launched eagerly, the stopping test disabled, an event before
     // every launch (PF()).  Entry k of the result = the k-th launch of an iteration, averaged over the iterations.
     int profile_iteration(int reps, tsgo_prof_entry* out, int cap) override {
@@ -41,7 +42,7 @@
         HIP_OK(hipSetDevice(cfg.device));
         double chi2;
         if (int rc = do_linearize(&chi2)) return rc;      // valid operands, a built hierarchy; state slot 0 says "not done"
-        struct TolGuard { double& tol; double keep; ~TolGuard() { tol = keep; } } tol_guard{cfg.pcg_rel_tol, cfg.pcg_rel_tol};
+        TolGuard tol_guard{cfg.pcg_rel_tol, cfg.pcg_rel_tol};
         cfg.pcg_rel_tol = 0;
         reps = std::max(2, reps + (reps & 1));           // whole pairs: the state ring has two slots
         for (int j = 0; j < 4; ++j) if (int rc = launch_iteration(j & 1)) return rc;        // warm caches and clocks
@@ -87,14 +88,12 @@
         if (int rc = do_linearize(&chi2)) return rc;      // valid operands; state slot 0 says "not done"
         const double s = sizeof(T);
         const double El = (double)pr.n_lm_edges, P = pr.P, L = pr.L;
-        double od = 0; for (uint32_t e : pr.odom.edge) od += e != kNoEdge;
-        const double b_lm = El * (4 + 4 * s) + P * 5 * s + L * 5 * s;
-        const double b_pose = El * (4 + 4 * s) + L * 2 * s + P * (5 + 6 + 3) * s + od * (4 + 3 * s + 3 * s);
+        const double od = od_slots_live(), b_lm = bytes_schur_lm(false), b_pose = bytes_schur_pose(false);
         const double b_upd = P * (3 + 3 + 6 + 4 * 3 * 2 - 3) * s;   // sz, z in; minv in; r p q x in+out (x,r,p,q), z out
         const double b_linlm = El * (4 + 4 * s + 4 * s) + P * 4 * s + L * (2 + 5 + 3) * s;
         const double b_linpose = El * (4 + 4 * s + 4 * s) + L * 7 * s + P * (4 + 18) * s + od * (4 + 9 * s + 3 * s);
         // whole iterations are timed with the stopping test disabled: a converged solve turns every kernel into an early exit
-        struct TolGuard { double& tol; double keep; ~TolGuard() { tol = keep; } } tol_guard{cfg.pcg_rel_tol, cfg.pcg_rel_tol};
+        TolGuard tol_guard{cfg.pcg_rel_tol, cfg.pcg_rel_tol};
         if (which == 5) cfg.pcg_rel_tol = 0;
         if (which == 8) {
             if (cfg.world > 1 || collective()) return set_error(-1, "tsgo_time_kernel: 8 (the edge report's pass): edge-sharded handles (world > 1) are not supported");

@@ -22,13 +22,12 @@
             // ... and a young graph's linearisations move faster than a hierarchy ages (Huber weights switch by the thousand in the first
             // steps from a front-end's estimates: 22 / 23 / 30 iterations on one hierarchy where fresh ones take 22 / 19 / 18 at 100k poses):
             // the first kYoungLins linearisations of a graph share a hierarchy between two at most (profiles/r03z_early_iterations.txt)
-            const int max_age = n_lins < kYoungLins ? std::min(hier_max_age, kYoungMaxAge) : hier_max_age;
-            ++n_lins;
-            const bool refresh = hier_age < 0 || hier_age >= max_age || iters_last > iters_fresh + hier_slack || iters_last > kHierFreshAbove;
+            const int max_age = mem.n_lins < kYoungLins ? std::min(hier_max_age, kYoungMaxAge) : hier_max_age;
+            ++mem.n_lins;
+            const bool refresh = mem.hier_age < 0 || mem.hier_age >= max_age || mem.iters_last > mem.iters_fresh + hier_slack || mem.iters_last > kHierFreshAbove;
             if (refresh) {
-                if (int rc = launch_amg_setup()) return rc;
-                hier_age = 0;
-                if (lin_count++ % kRhoEvery == 0) {
+                if (int rc = rebuild_hierarchy()) return rc;
+                if (mem.lin_count++ % kRhoEvery == 0) {
                     if (int rc = estimate_damping()) return rc;
                     if (int rc = launch_bottom_setup()) return rc;      // the dense bottom operator holds the last level's damping
                     launch_finalize();        // zc = omega_0 Minv r with the fresh omega_0
@@ -45,7 +44,6 @@
 
     // PCG; if the multigrid-preconditioned solve breaks down (indefinite preconditioner), the solve is
     // repeated from the same right-hand side with the block-Jacobi preconditioner.
-    int n_fallbacks = 0, n_hier_retries = 0, n_hier_shifts = 0;
     bool inject_armed = false;
     // Warm start (cfg.warm_start): the Gauss-Newton update takes kStepScale of the solved delta, so (1 - kStepScale) of it
     // is still to go at the next linearisation.  x0 = that remainder, r = b~ - S x0 (one extra product), and the stopping
@@ -59,8 +57,8 @@
         WarmTerms<T> w{};
         warm_coefficients(w);
         for (int j = 0; j < kMaxWarm; ++j) w.v[j] = hist[j];
-        w.n_max = std::max(1, std::min({n_prev, (int)cfg.warm_start, kMaxWarm}));
-        w.n_tested = std::min(n_tested, w.n_max);
+        w.n_max = std::max(1, std::min({mem.n_prev, (int)cfg.warm_start, kMaxWarm}));
+        w.n_tested = std::min(mem.n_tested, w.n_max);
         w.errpart = warm_err; w.nb_err = nbC;
         hipLaunchKernelGGL((k_pack_x<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, x, zc, w, warm_order_dev);
         if (int rc = launch_matvec(0)) return rc;
@@ -69,27 +67,35 @@
                            amg_on ? st[0] : (CgState<T>*)nullptr, (T)(cfg.pcg_rel_tol * cfg.pcg_rel_tol));
         return 0;
     }
+    // The two steps the rungs of do_solve's ladder are made of: the hierarchy rebuilt for the current linearisation (age 0 BEFORE the solve that
+    // follows, which files its count under that age), and the solve repeated from the plain right-hand side (stagnation, 3, is a breakdown, 1).
+    int rebuild_hierarchy() { if (int rc = launch_amg_setup()) return rc; mem.hier_age = 0; return 0; }
+    int solve_again(int* iters, int* fail) {
+        launch_finalize();
+        if (int rc = do_solve_once(iters, fail)) return rc;
+        if (*fail == 3) *fail = 1;
+        return 0;
+    }
     int do_solve(int* iters, int* fail) {
-        const bool warmed = cfg.warm_start && have_prev && step_scale() < 1.0;      // a full step (rules = 1, lr = 1) leaves no remainder to start from
+        const bool warmed = cfg.warm_start && mem.have_prev && step_scale() < 1.0;      // a full step (rules = 1, lr = 1) leaves no remainder to start from
         if (warmed) { if (int rc = launch_warm()) return rc; }
-        if (warmed && carried) {
+        if (warmed && mem.carried) {
             // The history is the previous REQUEST's: it continues this one only if the client sent back the estimates it was
             // returned.  k_warm_scale leaves b'D^-1 b / r0'D^-1 r0, or 1 when the start is no better than zero: then the history
             // is dropped and the solve starts cold (every shard reads the same all-reduced numbers and decides alike).
             T gs = 0;
             if (int rc = copy_sync(&gs, gscale_dev, sizeof(T), hipMemcpyDeviceToHost)) return rc;
-            if (!(gs > T(1))) { launch_finalize(); have_prev = false; n_prev = 0; n_tested = 0; ++n_carry_dropped; n_lins = 1; }      // ... and the graph is a young one after all
+            if (!(gs > T(1))) { launch_finalize(); mem.have_prev = false; mem.n_prev = 0; mem.n_tested = 0; ++n_carry_dropped; mem.n_lins = 1; }      // ... and the graph is a young one after all
         }
-        carried = false;
+        mem.carried = false;
         if (int rc = do_solve_once(iters, fail)) return rc;
-        const bool warm_trace = solve_timing;
-        if (warm_trace && warmed) {
+        if (solve_timing && warmed) {
             int order = 0; T gs = 0; std::vector<T> e((size_t)kMaxWarm * nbC);
             if (int rc = copy_sync(&order, warm_order_dev, sizeof(int), hipMemcpyDeviceToHost)) return rc;
             if (int rc = copy_sync(&gs, gscale_dev, sizeof(T), hipMemcpyDeviceToHost)) return rc;
             if (int rc = copy_sync(e.data(), warm_err, e.size() * sizeof(T), hipMemcpyDeviceToHost)) return rc;
-            std::fprintf(stderr, "[tsgo] warm start: order %d of %d tested, b'D^-1 b / r0'D^-1 r0 = %.3e, %d PCG iterations; prediction errors of the last delta:", order, n_tested, (double)gs, *iters);
-            for (int m = 0; m < n_tested; ++m) { double s = 0; for (int k = 0; k < nbC; ++k) s += (double)e[(size_t)m * nbC + k]; std::fprintf(stderr, " %.3e", s); }
+            std::fprintf(stderr, "[tsgo] warm start: order %d of %d tested, b'D^-1 b / r0'D^-1 r0 = %.3e, %d PCG iterations; prediction errors of the last delta:", order, mem.n_tested, (double)gs, *iters);
+            for (int m = 0; m < mem.n_tested; ++m) { double s = 0; for (int k = 0; k < nbC; ++k) s += (double)e[(size_t)m * nbC + k]; std::fprintf(stderr, " %.3e", s); }
             std::fprintf(stderr, "\n");
         }
         if (say_env && *fail != 0) {      // what the device state says about a solve that failed
@@ -104,70 +110,59 @@
             }
             const double beta = hs.gamma_old != T(0) ? gamma / (double)hs.gamma_old : 0.0;
             std::fprintf(stderr, "[tsgo] solve failed: fail %d after %d iterations (%s preconditioner, %s start, hierarchy age %d): gamma_old %.6e alpha_old %.6e gamma0 %.6e | now gamma = r'z %.6e, delta = z'Sz %.6e, beta %.4e, delta - beta gamma / alpha_old = %.6e\n", *fail, *iters,
-                         amg_on ? "multigrid" : "block-Jacobi", warmed ? "warm" : "cold", hier_age, (double)hs.gamma_old, (double)hs.alpha_old, (double)hs.gamma0, gamma, delta, beta,
+                         amg_on ? "multigrid" : "block-Jacobi", warmed ? "warm" : "cold", mem.hier_age, (double)hs.gamma_old, (double)hs.alpha_old, (double)hs.gamma0, gamma, delta, beta,
                          delta - beta * gamma / (double)hs.alpha_old);
         }
-        if (*fail == 3 && amg_on) *fail = 1;          // stagnation under the multigrid cycle
-        if (amg_on && cy16 && (*fail != 0 || *iters > kPackedCycleMaxIters)) {
+        if (*fail == 3 && amg_on) *fail = 1;          // stagnation under the multigrid cycle (mapped after the trace above, which prints 3)
+        // ---- The ladder: a multigrid solve that broke down (fail 1) is repeated on a hierarchy rebuilt under the next remedy, rung by rung.
+        // Rung 1, packed -> f32: the only rung a solve that SUCCEEDED takes too (by its iteration count); only a failed one is repeated.
+        if (amg_on && mem.cy16 && (*fail != 0 || *iters > kPackedCycleMaxIters)) {
             // Packed half floats round every block of the cycle's operators to 11 bits.  A coarse operator of a nearly singular
             // system (an odometry-only chain under the analytic Jacobians: a 24k-link beam) is a difference of large entries; at
             // that precision it stops being positive definite and the solve breaks down or crawls (20 000 iterations where the
             // f32 copies need 1 500; profiles/r03k_hard_chain.txt).  Such a graph shows itself by its iteration count: from here
-            // on this structure's cycle reads f32 copies (sticky until a new structure arrives), and a solve that failed is
-            // repeated with them.
-            cy16 = false; ++n_cycle_f32_switches;
+            // on its cycle reads f32 copies (until the next tsgo_set_graph), and a solve that failed is repeated with them.
+            mem.cy16 = false; ++n_cycle_f32_switches;
             if (cg_graph) { (void)hipGraphExecDestroy(cg_graph); cg_graph = nullptr; optimize_calls_on_tables = 1; }     // it holds the packed kernels; re-captured at the next tsgo_optimize
             if (say_env) std::fprintf(stderr, "[tsgo] %d PCG iterations (fail %d) with the packed cycle format: this structure's cycle switches to f32 copies\n", *iters, *fail);
-            if (int rc = launch_amg_setup()) return rc;
-            hier_age = 0; iters_fresh = 0;
-            if (*fail != 0) {
-                launch_finalize();
-                if (int rc = do_solve_once(iters, fail)) return rc;
-                if (*fail == 3) *fail = 1;
-            }
+            if (int rc = rebuild_hierarchy()) return rc;
+            mem.iters_fresh = 0;
+            if (*fail != 0) { if (int rc = solve_again(iters, fail)) return rc; }
         }
-        const int age_used = hier_age;
-        if (amg_on) { iters_last = *iters; if (hier_age == 0) iters_fresh = *iters; if (hier_age >= 0) ++hier_age; }
+        const int age_used = mem.hier_age;
+        if (amg_on) { mem.iters_last = *iters; if (mem.hier_age == 0) mem.iters_fresh = *iters; if (mem.hier_age >= 0) ++mem.hier_age; }      // (the solve that stands so far; the rungs below book their own)
         if (*fail == 1 && amg_on && age_used > 0) {
-            // The hierarchy that failed was built for an earlier linearisation (the lag rule).  Before giving the multigrid
-            // cycle up for this solve, build it for THIS one and solve again from the plain right-hand side: on beam-like
-            // odometry chains (analytic Jacobians) a lagged hierarchy can be indefinite where a fresh one takes 1 400 iterations
-            // and block-Jacobi does not finish in 20 000.
+            // Rung 2, stale hierarchy (its solve is booked as a fresh hierarchy's first whether it succeeded or not).  The hierarchy that failed
+            // was built for an earlier linearisation (the lag rule).  Before giving the multigrid cycle up for this solve, build it for THIS one
+            // and solve again: on beam-like odometry chains (analytic Jacobians) a lagged hierarchy can be indefinite where a fresh one takes
+            // 1 400 iterations and block-Jacobi does not finish in 20 000.
             ++n_hier_retries;
-            if (int rc = launch_amg_setup()) return rc;
-            hier_age = 0;
-            launch_finalize();
-            if (int rc = do_solve_once(iters, fail)) return rc;
-            if (*fail == 3) *fail = 1;
-            iters_last = *iters; iters_fresh = *iters; hier_age = 1;
+            if (int rc = rebuild_hierarchy()) return rc;
+            if (int rc = solve_again(iters, fail)) return rc;
+            mem.iters_last = *iters; mem.iters_fresh = *iters; mem.hier_age = 1;
         }
-        // Still broken down (r^T M^-1 r < 0) on a hierarchy built for THIS linearisation, in f32 copies: the hierarchy's level-0 matrix is S rounded
-        // to f32, 6e-8 of its entries — 6e-4 in absolute terms where the smooth bending modes of a map of several hundred thousand poses have an
-        // energy of 1e-6 per pose: the rounded matrix, every Galerkin product made from it and the cycle that inverts them can be INDEFINITE in
-        // those modes (a 372k-pose graph sent again with the estimates that came back: three solves in a row fell back to 15 500 block-Jacobi
-        // iterations; with the hierarchy stored in f64, -DTSGO_HIER_F64, none does: profiles/r04p_indefinite_cycle_f32_hierarchy.txt).  The
-        // remedy keeps f32: the hierarchy's copy of S gets its diagonal raised by 1e-6 (then 1e-5) of itself — positive definite again, for this
-        // structure from here on; the smooth modes are then corrected less by the coarse levels and PCG takes some more iterations (42-63 where
-        // an f64 hierarchy takes 25-34) instead of fifteen thousand.
+        // Rungs 3 and 4, diagonal shifts (skipped under the injection hook; a shift already in force is not repeated; booked only on success).
+        // Still broken down (r^T M^-1 r < 0) on a hierarchy built for THIS linearisation, in f32 copies: its level-0 matrix is S rounded to f32, and
+        // where the smooth bending modes of several hundred thousand poses carry 1e-6 per pose that rounding can leave it, its Galerkin products
+        // and the cycle INDEFINITE (a 372k-pose graph: 15 500 block-Jacobi iterations per solve, profiles/r04p_indefinite_cycle_f32_hierarchy.txt).
+        // The hierarchy's copy of S gets its diagonal raised by 1e-6, then 1e-5, of itself: positive definite again, at some more PCG iterations
+        // (42-63 where an f64 hierarchy takes 25-34).  The raise holds until the next tsgo_set_graph, refill or new structure alike (a refilled
+        // handle does what a fresh one does): a structure that needs it pays the failed solve again on every request.
         for (const double shift : {1e-6, 1e-5}) {
             if (!(*fail == 1 && amg_on) || hook_inject_amg_failure) break;
-            if (hier_shift >= shift) continue;
-            hier_shift = shift; ++n_hier_shifts;
+            if (mem.hier_shift >= shift) continue;
+            mem.hier_shift = shift; ++n_hier_shifts;
             if (say_env) std::fprintf(stderr, "[tsgo] multigrid cycle indefinite on a fresh hierarchy: its level-0 matrix gets its diagonal raised by %.0e from here on\n", shift);
-            if (int rc = launch_amg_setup()) return rc;
-            hier_age = 0;
-            launch_finalize();
-            if (int rc = do_solve_once(iters, fail)) return rc;
-            if (*fail == 3) *fail = 1;
-            if (*fail == 0) { iters_last = *iters; iters_fresh = *iters; hier_age = 1; }
+            if (int rc = rebuild_hierarchy()) return rc;
+            if (int rc = solve_again(iters, fail)) return rc;
+            if (*fail == 0) { mem.iters_last = *iters; mem.iters_fresh = *iters; mem.hier_age = 1; }
         }
         // test hook: TSGO_INJECT_AMG_FAILURE=1 treats the first multigrid solve of every tsgo_optimize call as broken down, so that the
         // block-Jacobi repeat below runs on a graph where the cycle is perfectly healthy (tests/test_gpu_parity.py)
-        const bool inject = hook_inject_amg_failure;
-        if (inject && amg_on && inject_armed) { inject_armed = false; *fail = 1; }
-        if (*fail == 1 && amg_on) {
+        if (hook_inject_amg_failure && amg_on && inject_armed) { inject_armed = false; *fail = 1; }
+        if (*fail == 1 && amg_on) {      // Last rung, block-Jacobi: cycle and replay are set aside for this one solve
             ++n_fallbacks;
-            hier_age = -1;                               // whatever went wrong, start from a fresh hierarchy next time
+            mem.hier_age = -1;                               // whatever went wrong, start from a fresh hierarchy next time
             const bool keep = amg_on; hipGraphExec_t g = cg_graph;
             amg_on = false; cg_graph = nullptr;          // eager block-Jacobi launches
             launch_finalize();
@@ -184,10 +179,6 @@
     // exit at once, 43 us) instead of the two or three a predicted burst over-provisions, an under-provisioned burst (the device idle
     // while the host enqueues more: 0.4 ms) cannot happen, and the iteration count and failure flag arrive with the report: the stream is
     // not drained at the end of the solve — the back-substitution queues up behind the last exits (profiles/r03z_paced_eager.txt).
-    double ref_us_per_iter = 0;        // the device's time per iteration as the burst path measured it (the structure's first solves)
-    int n_paced_slow = 0;
-    uint32_t paced_base = 0;           // sequence numbers grow ACROSS solves: a gate of an earlier solve that is still queued when a retry
-                                       // starts the next one (pace_lead > 1, hierarchy / block-Jacobi repeats) reports a number <= base and is ignored
     int do_solve_paced(int* iters, int* fail) {
         uint64_t* hw = reinterpret_cast<uint64_t*>(h_flag);
         if (paced_base > 0x70000000u) {      // (wrap-around: once per 4e9 iterations) nothing may be in flight when the numbering restarts
@@ -218,14 +209,12 @@
             }
         }
         paced_base = base + (uint32_t)launched;
-        *iters = (int)(w & 0x0fffffffu); *fail = (int)((w >> 28) & 7);
+        solve_done((int)(w & 0x0fffffffu), (int)((w >> 28) & 7), iters, fail);
         const double wall = since();
         if (timing) std::fprintf(stderr, "[tsgo] solve (paced): %d iterations launched, done reported after %d at %.0f us\n", launched, *iters, wall);
-        predicted_cg = *iters;
-        if (amg_on && hier_age >= 0 && hier_age < kAgeSlots) iters_by_age[hier_age] = *fail ? 0 : *iters;
         // a host that cannot stay ahead shows as iterations that take longer than the burst path measured: then the handle goes over to replay
-        if (cfg.use_graphs == 2 && *iters >= 8 && !*fail && ref_us_per_iter > 0 && !hook_force_paced) {
-            if (wall / *iters > 1.3 * ref_us_per_iter) { if (++n_paced_slow >= 3) host_slow = true; } else n_paced_slow = 0;
+        if (cfg.use_graphs == 2 && *iters >= 8 && !*fail && mem.ref_us_per_iter > 0 && !hook_force_paced) {
+            if (wall / *iters > 1.3 * mem.ref_us_per_iter) { if (++mem.n_paced_slow >= 3) host_slow = true; } else mem.n_paced_slow = 0;
         }
         return 0;
     }
@@ -234,9 +223,14 @@
     bool paced() const {
         if (!amg_on || cg_graph || collective() || cfg.use_graphs == 1 || prof_on || h_flag == nullptr) return false;
         if (hook_force_paced) return true;       // test hook (TSGO_TESTING builds): the paced path from the first solve on
-        return n_decided >= kDecideSolves && 2 * n_slow_seen <= kDecideSolves && !host_slow;
+        return mem.n_decided >= kDecideSolves && 2 * mem.n_slow_seen <= kDecideSolves && !host_slow;
     }
 
+    void solve_done(int n, int failed, int* iters, int* fail) {      // what every solve ends with: the caller's verdict, the next burst's predictors
+        *iters = n; *fail = failed;
+        mem.predicted_cg = n;
+        if (amg_on && mem.hier_age >= 0 && mem.hier_age < kAgeSlots) mem.iters_by_age[mem.hier_age] = failed ? 0 : n;
+    }
     // PCG until the device state says done.  The state ring is at slot 0 on entry and on exit.
     int do_solve_once(int* iters, int* fail) {
         if (paced()) return do_solve_paced(iters, fail);
@@ -249,8 +243,8 @@
         // drift, so that burst stops at 90 %.
         // Under the lag rule the counts repeat from one hierarchy to the next (15 15 16 17 | 15 15 16 17 at 100k poses): the best
         // predictor of a solve is the solve of the same age on the previous hierarchy.
-        const int by_age = (amg_on && hier_age >= 0 && hier_age < kAgeSlots) ? iters_by_age[hier_age] : 0;
-        const int pred = amg_on ? (by_age > 0 ? by_age : (hier_age == 0 && iters_fresh > 0 ? iters_fresh : predicted_cg + 1)) : predicted_cg;
+        const int by_age = (amg_on && mem.hier_age >= 0 && mem.hier_age < kAgeSlots) ? mem.iters_by_age[mem.hier_age] : 0;
+        const int pred = amg_on ? (by_age > 0 ? by_age : (mem.hier_age == 0 && mem.iters_fresh > 0 ? mem.iters_fresh : mem.predicted_cg + 1)) : mem.predicted_cg;
         int burst = amg_on ? std::max(1, (pred + 1 + ch - 1) / ch) : std::max(1, (int)(0.9 * pred) / ch);
         const bool timing = solve_timing;
         const auto w0 = std::chrono::steady_clock::now();
@@ -266,10 +260,10 @@
             if (!cg_graph && amg_on && burst >= 4 && dev_us_per_iter > 0) {      // an eager burst of >= 8 iterations: was the host well ahead of the device?
                 const double host_us_per_iter = t_enq / (burst * ch);
                 const double share = host_us_per_iter / dev_us_per_iter;
-                if (n_decided < kDecideSolves) {      // the structure's first solves settle it (within a bench's warm-up, a request's first iterations): no flip in mid-run
-                    n_slow_seen += share > kHostSlowFraction;
-                    if (++n_decided == kDecideSolves && 2 * n_slow_seen > kDecideSolves) host_slow = true;
-                } else if (share > 0.95) { if (++n_host_slow >= 3) host_slow = true; } else n_host_slow = 0;      // later only outright starvation (a profiler attached, cores taken away)
+                if (mem.n_decided < kDecideSolves) {      // the structure's first solves settle it (within a bench's warm-up, a request's first iterations): no flip in mid-run
+                    mem.n_slow_seen += share > kHostSlowFraction;
+                    if (++mem.n_decided == kDecideSolves && 2 * mem.n_slow_seen > kDecideSolves) host_slow = true;
+                } else if (share > 0.95) { if (++mem.n_host_slow >= 3) host_slow = true; } else mem.n_host_slow = 0;      // later only outright starvation (a profiler attached, cores taken away)
             }
             if (cg_graph) replayed = true;
             burst = 1;
@@ -279,10 +273,8 @@
             if (h_state->done) break;
             if (launched > cfg.pcg_max_iters + 2 * ch) return set_error(-20, "PCG did not terminate");
         }
-        *iters = h_state->iters; *fail = h_state->fail;
-        predicted_cg = h_state->iters;
-        if (amg_on && h_state->iters >= 4 && !h_state->fail) { dev_us_per_iter = since() / h_state->iters; if (!cg_graph) ref_us_per_iter = ref_us_per_iter > 0 ? std::min(ref_us_per_iter, dev_us_per_iter) : dev_us_per_iter; }      // (an upper bound: the solve's wall time over its iterations)
-        if (amg_on && hier_age >= 0 && hier_age < kAgeSlots) iters_by_age[hier_age] = h_state->fail ? 0 : h_state->iters;
+        if (amg_on && h_state->iters >= 4 && !h_state->fail) { dev_us_per_iter = since() / h_state->iters; if (!cg_graph) mem.ref_us_per_iter = mem.ref_us_per_iter > 0 ? std::min(mem.ref_us_per_iter, dev_us_per_iter) : dev_us_per_iter; }      // (an upper bound: the solve's wall time over its iterations)
+        solve_done(h_state->iters, h_state->fail, iters, fail);
         return 0;
     }
 
@@ -295,12 +287,12 @@
             WarmTerms<T> w{};
             warm_coefficients(w);
             for (int j = 0; j + 1 < kMaxWarm; ++j) w.v[j] = hist[j + 1];
-            w.n_max = std::min({n_prev, (int)cfg.warm_start, kMaxWarm - 1});      // orders that can be tested on this delta
+            w.n_max = std::min({mem.n_prev, (int)cfg.warm_start, kMaxWarm - 1});      // orders that can be tested on this delta
             hipLaunchKernelGGL((k_save_x<T>), dim3(nbC), dim3(kBlock), 0, stream, P, (const T*)x, zc, hist[0], w, warm_err);
-            n_tested = w.n_max; have_prev = true; n_prev = std::min(n_prev + 1, kMaxWarm);
+            mem.n_tested = w.n_max; mem.have_prev = true; mem.n_prev = std::min(mem.n_prev + 1, kMaxWarm);
         } else {      // a probe (step 0) leaves nothing to carry over
             hipLaunchKernelGGL((k_pack_x<T>), dim3(nbC), dim3(kBlock), 0, stream, P, x, zc, WarmTerms<T>{}, (int*)nullptr);
-            have_prev = false; n_prev = 0; n_tested = 0;
+            mem.have_prev = false; mem.n_prev = 0; mem.n_tested = 0;
         }
         if (tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
             launch(k_schur_lm<T, g, 1, 0>, nbL, tl, zc, lmrec, (const T*)ninv, tvec, st[0], step, dl, npart + nbC, (const float*)nullptr, (float*)nullptr, no_gate(), T(0), (T*)nullptr);
@@ -343,7 +335,7 @@
         T* norm_p = lm_red; T* norm_l = lm_red + nbC; T* pred_p = norm_l + nl; T* pred_l = pred_p + nbC; T* chi = pred_l + nl;
         launch(k_lm_state<T, 0>, grid_for(std::max(P, L)), P, L, ps, theta, lmrec, snap_ps, snap_theta, snap_lm);
         hipLaunchKernelGGL((k_pack_x<T>), dim3(nbC), dim3(kBlock), 0, stream, P, x, zc, WarmTerms<T>{}, (int*)nullptr);
-        have_prev = false; n_prev = 0; n_tested = 0;
+        mem.have_prev = false; mem.n_prev = 0; mem.n_tested = 0;
         if (nl > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
             launch(k_schur_lm<T, g, 2, 0>, nbL, tl, zc, lmrec, (const T*)ninv, tvec, st[0], T(1), dl, norm_l, (const float*)nullptr, (float*)nullptr, no_gate(), (T)lam, pred_l);
         });
@@ -362,12 +354,21 @@
         launch(k_lm_state<T, 1>, grid_for(std::max(pr.P, pr.L)), pr.P, pr.L, ps, theta, lmrec, snap_ps, snap_theta, snap_lm);
         return 0;
     }
+    int end_step_timing(tsgo_stats& s) {      // ev[0..2] stand before a step's linearisation, solve and update: closes the update, waits, adds the device times
+        float ms = 0;
+        HIP_OK(hipEventRecord(ev[3], stream));
+        HIP_OK(hipEventSynchronize(ev[3]));
+        HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1])); s.ms_linearize += ms;
+        HIP_OK(hipEventElapsedTime(&ms, ev[1], ev[2])); s.ms_solve += ms;
+        HIP_OK(hipEventElapsedTime(&ms, ev[2], ev[3])); s.ms_update += ms;
+        return 0;
+    }
     // The loop.  One trial = linearise (H + lambda I, b zeroed at fixed vertices), solve, tentative full step, decide; a rejected trial is
     // followed by a fresh linearisation at the restored point: lambda is baked into the landmark inverses and the pose diagonals.
     int lm_loop(int iterations, tsgo_stats& s) {
         double lam = std::min(std::max(cfg.lm_lambda0, kLmLambdaMin), kLmLambdaMax), nu = 2;
         for (int it = 0; it < iterations; ++it) {
-            double err = 0; float ms = 0;
+            double err = 0;
             HIP_OK(hipEventRecord(ev[0], stream));
             lambda = lam;
             if (int rc = do_linearize(&err)) return rc;
@@ -384,11 +385,7 @@
             if (fail != 0) { s.stop_reason = TSGO_STOP_SOLVER; break; }
             double np2 = 0, nl2 = 0, pred = 0, trial = 0;
             if (int rc = do_lm_step(lam, &np2, &nl2, &pred, &trial)) return rc;
-            HIP_OK(hipEventRecord(ev[3], stream));
-            HIP_OK(hipEventSynchronize(ev[3]));
-            HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1])); s.ms_linearize += ms;
-            HIP_OK(hipEventElapsedTime(&ms, ev[1], ev[2])); s.ms_solve += ms;
-            HIP_OK(hipEventElapsedTime(&ms, ev[2], ev[3])); s.ms_update += ms;
+            if (int rc = end_step_timing(s)) return rc;
             s.last_delta_norm = std::sqrt(np2 + nl2);
             const double gain = pred != 0 ? (err - trial) / pred : 0.0;
             if (traced) { s.lm_pred[it] = pred; s.lm_chi2_trial[it] = trial; s.lm_gain[it] = gain; }
@@ -406,38 +403,17 @@
         return 0;
     }
 
-    int optimize_calls_on_tables = 0;       // tsgo_optimize calls since the tables were built (lazy hipGraph capture, see set_graph)
-    int optimize(int iterations, tsgo_stats* out) override {
-        if (!have_graph_data) return set_error(-3, "tsgo_optimize: no graph set");
-        HIP_OK(hipSetDevice(cfg.device));
-        // use_graphs 1: the PCG iterations are replayed from a captured hipGraph (from the second tsgo_optimize on these tables on).  2
-        // (default): eager launches while the host thread enqueues an iteration in well under the time the device takes to run it
-        // (3 us per launch against 7 on an EPYC 9575F: eager is then 1-3 % FASTER than the replay and steadier, profiles/r03z_eager_vs_graph.txt);
-        // a host that cannot keep that distance (busy cores, a slow clock, a profiler; or a graph of 10k poses, whose iteration the device runs in 99 us)
-        // is noticed by do_solve_once and the handle goes over to replay.
-        if (hook_force_host_slow) host_slow = true;      // test hook (TSGO_TESTING builds)
-        const bool want_graph = cfg.use_graphs == 1 || (cfg.use_graphs == 2 && (host_slow || !amg_on));      // (block-Jacobi PCG is two short kernels per iteration, thousands of times: always replayed)
-        if (want_graph && !collective() && !cg_graph && optimize_calls_on_tables >= 1) { if (int rc = capture_cg_graph()) return rc; }
-        inject_armed = true;
-        ++optimize_calls_on_tables;
-        tsgo_stats s; std::memset(&s, 0, sizeof(s));
-        s.n_pose = pr.P; s.n_lm = pr.L_total; s.n_odom_edges = pr.n_odom_edges_total; s.n_lm_edges = pr.n_lm_edges_total;
-        s.ms_setup = ms_setup; s.structure_reused = last_set_reused ? 1 : 0;
+    // rules 0 and 1: Gauss-Newton with the reference's stop rules (OptimizerCpu.h:80-180 / graph_optimizer.py:24-92)
+    int gn_loop(int iterations, tsgo_stats& s) {
         double prevErr = -1; int penalty = 0;
         bool nl2_whole = true;        // sharded: last_delta_norm holds every rank's landmark part (see landmark_norm_allreduce)
         double np2_last = 0, nl2_last = 0;
-        const int fallbacks0 = n_fallbacks, dropped0 = n_carry_dropped;
-        const bool started_carried = carried;
-        replayed = false;
-        s.stop_reason = TSGO_STOP_CAP;
-        const auto wall0 = std::chrono::steady_clock::now();
         // rules = 1 (graph_optimizer.py:24-31): lambda starts at 1e-3 on every call
         const double lam_max = 1e1, lam_min = 1e-6, lam_fac = 1.1;
         double lam = 1e-3;
         const double step = step_scale();
-        if (lm_rules()) { if (int rc = lm_loop(iterations, s)) return rc; }
-        for (int it = 0; it < (lm_rules() ? 0 : iterations); ++it) {      // rules 0 and 1
-            double err = 0; float ms = 0;
+        for (int it = 0; it < iterations; ++it) {
+            double err = 0;
             HIP_OK(hipEventRecord(ev[0], stream));
             if (py_rules()) {
                 // lambda follows the chi^2 of THIS linearisation (:41-42), which the linearisation itself needs: it is run with the
@@ -467,11 +443,7 @@
             if (fail != 0) { s.stop_reason = TSGO_STOP_SOLVER; break; }       // breakdown, or pcg_max_iters reached without convergence: no step is taken
             double np2 = 0, nl2 = 0;
             if (int rc = do_backsub_update((T)step, &np2, &nl2)) return rc;   // :159-165 / graph_optimizer.py:66-75
-            HIP_OK(hipEventRecord(ev[3], stream));
-            HIP_OK(hipEventSynchronize(ev[3]));
-            HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1])); s.ms_linearize += ms;
-            HIP_OK(hipEventElapsedTime(&ms, ev[1], ev[2])); s.ms_solve += ms;
-            HIP_OK(hipEventElapsedTime(&ms, ev[2], ev[3])); s.ms_update += ms;
+            if (int rc = end_step_timing(s)) return rc;
             nl2_whole = !collective();
             const bool last = it + 1 == iterations;
             const bool plateau = !py_rules() && std::fabs(err - prevErr) < kPlateauTol;
@@ -489,12 +461,37 @@
         }
         if (!nl2_whole) {             // the loop ended before its last update's landmark norm was summed (worse / solver stop)
             if (int rc = landmark_norm_allreduce(&nl2_last)) return rc;
-            s.last_delta_norm = (py_rules() ? step_scale() : 1.0) * std::sqrt(np2_last + nl2_last);
+            s.last_delta_norm = (py_rules() ? step : 1.0) * std::sqrt(np2_last + nl2_last);
         }
+        return 0;
+    }
+
+    int optimize(int iterations, tsgo_stats* out) override {
+        if (!have_graph_data) return set_error(-3, "tsgo_optimize: no graph set");
+        HIP_OK(hipSetDevice(cfg.device));
+        // use_graphs 1: the PCG iterations are replayed from a captured hipGraph (from the second tsgo_optimize on these tables on).  2
+        // (default): eager launches while the host thread enqueues an iteration in well under the time the device takes to run it
+        // (3 us per launch against 7 on an EPYC 9575F: eager is then 1-3 % FASTER than the replay and steadier, profiles/r03z_eager_vs_graph.txt);
+        // a host that cannot keep that distance (busy cores, a slow clock, a profiler; or a graph of 10k poses, whose iteration the device runs in 99 us)
+        // is noticed by do_solve_once and the handle goes over to replay.
+        if (hook_force_host_slow) host_slow = true;      // test hook (TSGO_TESTING builds)
+        const bool want_graph = cfg.use_graphs == 1 || (cfg.use_graphs == 2 && (host_slow || !amg_on));      // (block-Jacobi PCG is two short kernels per iteration, thousands of times: always replayed)
+        if (want_graph && !collective() && !cg_graph && optimize_calls_on_tables >= 1) { if (int rc = capture_cg_graph()) return rc; }
+        inject_armed = true;
+        ++optimize_calls_on_tables;
+        tsgo_stats s; std::memset(&s, 0, sizeof(s));
+        s.n_pose = pr.P; s.n_lm = pr.L_total; s.n_odom_edges = pr.n_odom_edges_total; s.n_lm_edges = pr.n_lm_edges_total;
+        s.ms_setup = ms_setup; s.structure_reused = last_set_reused ? 1 : 0;
+        const int fallbacks0 = n_fallbacks, dropped0 = n_carry_dropped;
+        const bool started_carried = mem.carried;
+        replayed = false;
+        s.stop_reason = TSGO_STOP_CAP;
+        const auto wall0 = std::chrono::steady_clock::now();
+        if (int rc = lm_rules() ? lm_loop(iterations, s) : gn_loop(iterations, s)) return rc;
         s.pcg_fallbacks = n_fallbacks - fallbacks0;
         s.history_carried = started_carried ? (n_carry_dropped > dropped0 ? 2 : 1) : 0;
         s.graph_replay = replayed ? 1 : 0;
-        s.cycle_storage_now = amg_on ? (cy16 ? 16 : 32) : 0;
+        s.cycle_storage_now = amg_on ? (mem.cy16 ? 16 : 32) : 0;
         s.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
         if (out) *out = s;
         return 0;

@@ -3,12 +3,12 @@
 // the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h.
 //
 // One translation unit; the engine class is laid out over this file and engine/*.inc (each included inside the class body):
-//   this file                      members, configuration / environment (host/knobs.h), device slabs and upload helpers; the C ABI at the end
+//   this file                      members (what the solver learns grouped by lifetime: SolverMemory), configuration / environment (host/knobs.h), device slabs and upload helpers; the C ABI at the end
 //   engine/engine_hierarchy.inc    the multigrid hierarchy on the device: patterns, symbolic products, dense bottom operators
-//   engine/engine_graph.inc        tsgo_set_graph: tables, value staging, structure re-use, solver history across requests
+//   engine/engine_graph.inc        tsgo_set_graph: tables, value staging, structure re-use, where SolverMemory starts afresh, solver history across requests
 //   engine/engine_launch.inc       every kernel launch of a linearisation / a hierarchy build / a PCG iteration
 //   engine/engine_collective.inc   the all-reduces of an edge-sharded run
-//   engine/engine_solve.inc        the Gauss-Newton loop, the PCG drivers, read-outs
+//   engine/engine_solve.inc        the Gauss-Newton and Levenberg-Marquardt loops, the PCG drivers and the retry ladder (do_solve), read-outs
 //   engine/engine_probes.inc       timing probes (bench.py)
 //   engine/engine_marginals.inc    tsgo_marginals, tsgo_joint_marginals: batched PCG for blocks of H^-1
 //   engine/engine_report.inc       tsgo_edge_report: per-edge residual records and the per-class summary
@@ -233,7 +233,6 @@ template <typename T> struct Engine : IEngine {
             fixed.assign(g.fixed, g.fixed + g.n_fixed);
         }
     } structure;
-    int structure_reuses = 0;
     bool last_set_reused = false;
     std::vector<double> lm_values;                 // per LM edge: (zx, zy, w0, w1), scratch of stage_values
     T* stage = nullptr; size_t stage_cap = 0;      // pinned staging for everything that goes to the device in type T
@@ -257,19 +256,44 @@ template <typename T> struct Engine : IEngine {
     T *snap_ps = nullptr, *snap_theta = nullptr, *snap_lm = nullptr, *lm_red = nullptr, *h_lm = nullptr;
     int nbP = 0, nbL = 0, nbC = 0;
     bool fuse_post_smooth = true;      // the level-0 post-smoothing in the epilogue of the cycle's second product (research: TSGO_FUSE_POST=0 = k_smooth0)
-    double hier_shift_cfg = 0;         // what a graph starts with (0; research: TSGO_HIER_SHIFT)
-    double hier_shift = 0;             // relative raise of the diagonal of the hierarchy's level-0 matrix (research: TSGO_HIER_SHIFT; do_solve sets it after a breakdown)
+    double hier_shift_cfg = 0;         // the hier_shift a graph starts with (0; research: TSGO_HIER_SHIFT)
     bool fold_gate = true;             // the stopping rule in workgroup 0 of the iteration's first product (research: TSGO_FOLD_GATE=0 = its own kernel)
-    hipGraphExec_t cg_graph = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    int predicted_cg = 0;
-    double dev_us_per_iter = 0;        // wall time of the last multigrid solve over its iterations
-    bool host_slow = false;            // use_graphs = 2: the host thread has been seen to enqueue too slowly for eager launches (do_solve_once)
-    int n_host_slow = 0, n_decided = 0, n_slow_seen = 0;
     static constexpr int kDecideSolves = 3;
     bool replayed = false;             // the last tsgo_optimize replayed captured iterations (tsgo_stats.graph_replay)
+    // ---- What the solver learns while it runs has one of three lifetimes; a new member goes into one of the three groups.
+    // 1. Forgotten at EVERY tsgo_set_graph, refill or new structure (a refilled handle does, bit for bit, what a fresh one does): reset_solver_state()
+    //    assigns fresh_memory(); refill_values() and carry_in() then put the warm-start history back under warm_requests.
     static constexpr int kAgeSlots = 16;
-    int iters_by_age[kAgeSlots] = {};      // PCG iterations of the last solve that ran on a hierarchy of that age (do_solve_once's burst)
+    struct SolverMemory {
+        bool have_prev = false;            // warm start: hist[0] holds the pose delta of the previous solve
+        int n_prev = 0;                    // ... how many consecutive deltas are held
+        int n_tested = 0;                  // ... orders 1..n_tested of the extrapolation have an error in warm_err (k_save_x)
+        bool carried = false;              // ... the history came from the previous request: the first warm start made from it is checked (do_solve)
+        int predicted_cg = 0;              // burst prediction (do_solve_once): PCG iterations of the last solve,
+        int iters_by_age[kAgeSlots] = {};  // ... of the last solve that ran on a hierarchy of that age,
+        int iters_fresh = 0, iters_last = 0;   // ... of the last solve on a fresh hierarchy and of the last multigrid solve (do_linearize's refresh rule too)
+        int hier_age = -1;                 // hierarchy age: linearisations the hierarchy has served; -1: no valid hierarchy
+        int lin_count = 0;                 // ... hierarchy builds so far (the damping estimate is refreshed at every kRhoEvery-th)
+        int n_lins = 0;                    // ... linearisations of this graph so far
+        int n_decided = 0, n_slow_seen = 0, n_host_slow = 0, n_paced_slow = 0;   // eager / replay / paced: what do_solve_once and do_solve_paced have counted
+        double ref_us_per_iter = 0;        // ... the device's time per iteration as the burst path measured it (the graph's first solves)
+        bool cy16 = true;                  // a hard graph (do_solve): the cycle's copies of A_l, P_l, R_l are packed half floats (20 B per block; f32: 36 B), tsgo_config.cycle_storage until a solve shows it too ill-conditioned for 11-bit blocks
+        double hier_shift = 0;             // ... relative raise of the diagonal of the hierarchy's level-0 matrix: hier_shift_cfg until a breakdown
+    } mem;
+    SolverMemory fresh_memory() const { SolverMemory m; m.cy16 = cfg.cycle_storage != 32; m.hier_shift = hier_shift_cfg; return m; }
+    // 2. Belongs to the TABLES: reset where set_graph builds a new structure, kept by a refill.  (With the report maps, engine_report.inc.)
+    int optimize_calls_on_tables = 0;  // tsgo_optimize calls since the tables were built (lazy hipGraph capture, see set_graph)
+    hipGraphExec_t cg_graph = nullptr; // (also dropped when the cycle leaves or re-enters the packed format: it holds those kernels)
+    double od_live = -1;               // live ODOM slots of this shard (the byte models'), counted once per structure (od_slots_live)
+    bool schur_dev = false;            // level 0's pattern and contribution lists were built on the device (run_device_schur)
+    // 3. Belongs to the HANDLE: never reset.  (With tsgo_robust robust, engine_launch.inc.)
+    int n_fallbacks = 0, n_hier_retries = 0, n_hier_shifts = 0, n_cycle_f32_switches = 0, n_carried = 0, n_carry_dropped = 0, structure_reuses = 0;
+    uint32_t paced_base = 0;           // sequence numbers grow ACROSS solves: a gate of an earlier solve that is still queued when a retry
+                                       // starts the next one (pace_lead > 1, hierarchy / block-Jacobi repeats) reports a number <= base and is ignored
+    // (these two survive tsgo_set_graph while the counters that derive them — n_decided, n_slow_seen, n_host_slow, n_paced_slow — do not)
+    double dev_us_per_iter = 0;        // wall time of the last multigrid solve over its iterations
+    bool host_slow = false;            // use_graphs = 2: the host thread has been seen to enqueue too slowly for eager launches (do_solve_once)
     // multigrid preconditioner.  Edge-sharded runs use it too: every rank holds the whole hierarchy (patterns from the whole graph,
     // level-0 blocks all-reduced, everything below computed redundantly); only the level-0 contribution lists are per shard
     bool amg_on = false;
@@ -285,13 +309,8 @@ template <typename T> struct Engine : IEngine {
     T *omega_dev = nullptr, *one_dev = nullptr, *gscale_dev = nullptr, *pw_a = nullptr, *pw_b = nullptr, *rho_part = nullptr;
     T* h_rho = nullptr;                 // pinned
     std::vector<double> omega_host;    // smoother damping per level (diagnostics)
-    int lin_count = 0;
-    int n_lins = 0;                    // linearisations of this graph so far (reset with the solver state)
-    int hier_age = -1, hier_max_age = kHierMaxAge, hier_slack = kHierSlack, iters_fresh = 0, iters_last = 0;   // -1: no valid hierarchy
+    int hier_max_age = kHierMaxAge, hier_slack = kHierSlack;
     T* hist[kMaxWarm] = {};            // pose deltas of the last solves, newest first (warm start)
-    bool have_prev = false;            // hist[0] holds the pose delta of the previous solve
-    int n_prev = 0;                    // how many consecutive deltas are held
-    int n_tested = 0;                  // orders 1..n_tested of the warm start's extrapolation have an error in warm_err (k_save_x)
     T* warm_err = nullptr;             // [kMaxWarm][nbC]
     int* warm_order_dev = nullptr;     // the order the last warm start took (diagnostics)
     // Coefficients of every extrapolation order (k_pack_x): row m-1 = (-1)^j C(m, j+1) a^(j+1), a = 1 - step.
@@ -312,10 +331,7 @@ template <typename T> struct Engine : IEngine {
         return coarse_sweeps != kCoarseSweeps ? (lv[l].n <= kSmallLevelRows ? kSmallLevelSweeps : coarse_sweeps) : sweeps_per_side(l, lv[l].n);
     }
     bool low_cycle = true;     // f32 slot planes for the Schur products inside the multigrid cycle
-    bool cy16 = true;          // the cycle-format copies of A_l, P_l, R_l as packed half floats (20 B per block) or f32 (36 B): tsgo_config.cycle_storage,
-                               // until a solve on this structure shows that the graph is too ill-conditioned for 11-bit blocks (do_solve)
-    int n_cycle_f32_switches = 0;
-    size_t cyw() const { return cy16 ? (size_t)kCyWordsF16 : (size_t)kCyWordsF32; }
+    size_t cyw() const { return mem.cy16 ? (size_t)kCyWordsF16 : (size_t)kCyWordsF32; }
     // the cycle's vectors below level 0 (DevLevel::r / z / res / z2, r_last / z_last, tail_t) hold CV<T>; cyc64 = T instead (testing builds:
     // TSGO_CYCLE_VEC64, host/knobs.h).  Fixed for the handle's life: the buffers are sized by it.
     bool cyc64 = false;
@@ -336,7 +352,6 @@ template <typename T> struct Engine : IEngine {
         if (const char* e = TSGO_RESEARCH_ENV("TSGO_SWEEPS_LIST")) for (const char* q = e; *q;) { sweeps_list.push_back(std::max(1, std::min(4, atoi(q)))); while (*q && *q != ',') ++q; if (*q == ',') ++q; }
         explicit0 = c.cycle_level0 != 0;
         cyc64 = TSGO_CYCLE_VEC64();
-        cy16 = c.cycle_storage != 32;
         if (const char* e = TSGO_RESEARCH_ENV("TSGO_HOST_PRODUCTS")) device_products = atoi(e) == 0;
         if (const char* e = TSGO_RESEARCH_ENV("TSGO_SYM_DECLINE")) sym_decline = atoi(e);
         if (const char* e = TSGO_RESEARCH_ENV("TSGO_HIER_MAX_AGE")) hier_max_age = std::max(1, atoi(e));
@@ -344,11 +359,12 @@ template <typename T> struct Engine : IEngine {
         if (const char* e = TSGO_RESEARCH_ENV("TSGO_PACE_LEAD")) pace_lead = std::max(1, atoi(e));
         if (const char* e = TSGO_RESEARCH_ENV("TSGO_LPR_XCD")) lpr_xcd = atoi(e) != 0;
         if (const char* e = TSGO_RESEARCH_ENV("TSGO_FOLD_GATE")) fold_gate = atoi(e) != 0;
-        if (const char* e = TSGO_RESEARCH_ENV("TSGO_HIER_SHIFT")) hier_shift = hier_shift_cfg = atof(e);
+        if (const char* e = TSGO_RESEARCH_ENV("TSGO_HIER_SHIFT")) hier_shift_cfg = atof(e);
         if (const char* e = TSGO_RESEARCH_ENV("TSGO_FUSE_POST")) fuse_post_smooth = atoi(e) != 0;
         hook_inject_amg_failure = TSGO_RESEARCH_ENV("TSGO_INJECT_AMG_FAILURE") != nullptr;
         hook_force_host_slow = TSGO_RESEARCH_ENV("TSGO_FORCE_HOST_SLOW") != nullptr;
         hook_force_paced = TSGO_RESEARCH_ENV("TSGO_FORCE_PACED") != nullptr;
+        mem = fresh_memory();
     }
 
     ~Engine() override { release(); for (Slab& sl : slabs) (void)hipFree(sl.base); if (carry_dev) (void)hipFree(carry_dev); if (stage) (void)hipHostFree(stage); if (stream) (void)hipStreamDestroy(stream); if (stream2) (void)hipStreamDestroy(stream2); for (auto& e : ev) if (e) (void)hipEventDestroy(e); for (auto& m : prof) (void)hipEventDestroy(m.e); }
