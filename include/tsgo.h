@@ -346,6 +346,42 @@ typedef struct tsgo_edge_report_stats {
 } tsgo_edge_report_stats;
 int tsgo_edge_report(tsgo_optimizer* opt, double* rec_out /* may be NULL */, int64_t cap_edges, tsgo_edge_report_stats* stats /* may be NULL */);
 
+/* Gate candidate edges by Mahalanobis distance: should this loop closure, this landmark match, this GNSS fix go INTO the graph?  (What
+ * tsgo_edge_report answers for the edges already in it.)  The n candidates come in the encoding of tsgo_graph (e_type, 2 ids, 9 e_meas,
+ * 3 e_inf per candidate); they are not in the graph and are not added to it.  Everything is evaluated at the handle's current estimates:
+ *   e      the residual of the edge function the linearisation runs for that type (0 ODOM, 1 LM, 2 virtual landmark, 3 pose prior,
+ *          4 landmark prior with id2 == id1); s = e^T Omega e with the raw information diagonal: what tsgo_edge_report would say for the
+ *          edge if it were in the graph.  Robust kernels are not applied to the candidate itself.
+ *   J      = [A | B], the analytic Jacobians of that residual under the reference's vertex update.  ODOM candidates take the
+ *          odom_jacobian = 1 Jacobians (tsgo_config) whatever the handle's setting: the constants -I / +I are not the derivative of
+ *          anything.  LM: A = [-R^T | (ppy, -ppx)], B = R^T.  Virtual landmark and priors: as described at tsgo_graph.e_type.
+ *   Sigma  the joint marginal of the candidate's one or two vertices, exactly the tsgo_joint_marginals block: the same H (the handle's
+ *          robust weights, the gauge, the priors, the handle's odom_jacobian, no damping).
+ *   S      = J Sigma J^T + Omega^-1, d2 = e^T S^-1 e, logdet = ln det S, dof = 3 for types 0 and 3, 2 for types 1, 2 and 4: d2 is
+ *          chi^2-distributed with dof degrees of freedom when the candidate is consistent with the graph (accept at the 99 % quantile:
+ *          11.345 for 3, 9.210 for 2).  A gate cannot reject what the graph's own uncertainty allows: after a long stretch of pure
+ *          odometry Sigma is large and false closures pass.
+ * rec_out receives 8 doubles per candidate, in input order: (e0, e1, e2, s, d2, dof, logdet, status); e2 = 0 where dof = 2.  status is 0,
+ * or 1 when the Cholesky factorisation of S fails (S not positive definite): then d2 and logdet are NaN and stats->not_pd counts the
+ * candidate.  innov_out (may be NULL) receives S, row-major in the leading dof x dof of 9 doubles per candidate, the rest 0, exactly
+ * symmetric.  The distinct vertices of the candidates are solved once (3 columns a pose, 2 a landmark, however many candidates share
+ * the vertex), a batch of columns per launch chain as tsgo_joint_marginals does, every batch but the last full: stats->solve.columns =
+ * 3 (distinct poses) + 2 (distinct landmarks).  rel_tol <= 0: the handle's pcg_rel_tol.  A repeated call gives the same bits.  n == 0
+ * returns 0 and solves nothing.  The state rule of tsgo_marginals holds: nothing the next tsgo_optimize reads changes.
+ * Errors (< 0, text in tsgo_last_error; the candidates are validated completely before anything is launched, the handle stays usable):
+ * those of tsgo_marginals (NULL handle, no graph, precision = 32, world > 1, neither a fixed vertex nor a full pose prior, an unknown
+ * vertex id); an unknown e_type; a vertex of the wrong kind for the type (LM needs a pose, then a landmark); id1 == id2 on a binary type
+ * or id1 != id2 on a unary one; an information entry on a used axis that is not finite and > 0 (Omega^-1 must exist); a non-invertible
+ * ODOM measurement; n < 0 or n > 2^20 (the device holds 36 doubles per candidate); rec_out == NULL with n > 0. */
+typedef struct tsgo_gate_stats {
+    int32_t candidates, vertices;      /* candidates given; distinct vertices they touch */
+    int32_t not_pd, reserved;          /* candidates whose innovation covariance was not positive definite (status = 1) */
+    tsgo_marginal_stats solve;         /* the batched solve: columns, batches, batch_width, iterations, fallbacks, ms */
+    double ms_total, ms_readout;       /* whole call; device time of the gate's own kernels (read-out after every batch, evaluation) */
+} tsgo_gate_stats;
+int tsgo_gate_edges(tsgo_optimizer* opt, int32_t n, const uint32_t* e_type, const uint32_t* e_ids, const double* e_meas, const double* e_inf, double rel_tol,
+                    double* rec_out, double* innov_out /* 9 per candidate, may be NULL */, tsgo_gate_stats* stats /* may be NULL */);
+
 const char* tsgo_last_error(void);
 
 /* ---- host-only: wire codec (libtsgo_host.so and libtsgo_hip.so) ---------------------------------

@@ -196,6 +196,19 @@ public:
         return s;
     }
 
+    // Mahalanobis gate of candidate edges (tsgo_gate_edges): the EDGES of `candidates` (its vertices are ignored; the ids refer to the
+    // graph last handed to Optimize) against the joint marginal of their vertices.  Eight doubles per candidate, in its edge order:
+    // (e0, e1, e2, s, d2, dof, logdet, status); *innovation (if given) receives S, 9 doubles per candidate.  Nothing is added to the graph.
+    // Throws on an error (those of Marginals, a candidate that is not a valid edge of the graph's vertices).
+    std::vector<double> GateEdges(const Graph& candidates, std::vector<double>* innovation = nullptr, tsgo_gate_stats* stats = nullptr) {
+        const tsgo_graph c = candidates.View();
+        std::vector<double> rec((size_t)c.n_edges * 8);
+        if (innovation) innovation->assign((size_t)c.n_edges * 9, 0.0);
+        if (tsgo_gate_edges(handle, c.n_edges, c.e_type, c.e_ids, c.e_meas, c.e_inf, 0.0, rec.data(), innovation ? innovation->data() : nullptr, stats))
+            throw std::runtime_error(tsgo_last_error());
+        return rec;
+    }
+
 private:
     unsigned iterations;
     tsgo_optimizer* handle = nullptr;

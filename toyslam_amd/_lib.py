@@ -46,6 +46,11 @@ class tsgo_edge_report_stats(C.Structure):
     _fields_ = [("cls", tsgo_edge_class_summary * 5), ("chi2", C.c_double), ("ms_total", C.c_double)]
 
 
+class tsgo_gate_stats(C.Structure):
+    _fields_ = [("candidates", C.c_int32), ("vertices", C.c_int32), ("not_pd", C.c_int32), ("reserved", C.c_int32),
+                ("solve", tsgo_marginal_stats), ("ms_total", C.c_double), ("ms_readout", C.c_double)]
+
+
 ROBUST_KERNELS = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}      # TSGO_ROBUST_*
 ROBUST_CLASSES = ("odom", "lm", "virtual", "pose_prior", "lm_prior")            # = tsgo_graph.e_type 0 .. 4
 
@@ -83,7 +88,7 @@ HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_last_error",
                 "tsgo_synth_truth", "tsgo_synth_free", "tsgo_layout_probe", "tsgo_amg_probe", "tsgo_amg_probe_shard"]
 DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_graph", "tsgo_reset_history", "tsgo_optimize", "tsgo_get_vertices",
                   "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
-                  "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust", "tsgo_edge_report"]
+                  "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust", "tsgo_edge_report", "tsgo_gate_edges"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
 
@@ -133,6 +138,7 @@ def _declare_device(L):
     L.tsgo_set_robust.argtypes = [vp, C.POINTER(tsgo_robust)]
     L.tsgo_get_robust.argtypes = [vp, C.POINTER(tsgo_robust)]
     L.tsgo_edge_report.argtypes = [vp, vp, C.c_int64, C.POINTER(tsgo_edge_report_stats)]
+    L.tsgo_gate_edges.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_double, vp, vp, C.POINTER(tsgo_gate_stats)]
 
 
 def _declare_testing(L):

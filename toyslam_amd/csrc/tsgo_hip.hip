@@ -12,6 +12,7 @@
 //   engine/engine_probes.inc       timing probes (bench.py)
 //   engine/engine_marginals.inc    tsgo_marginals, tsgo_joint_marginals: batched PCG for blocks of H^-1
 //   engine/engine_report.inc       tsgo_edge_report: per-edge residual records and the per-class summary
+//   engine/engine_gate.inc         tsgo_gate_edges: candidate edges against the joint marginal of their vertices (Mahalanobis gate)
 //   engine/engine_testing.inc      tsgo_testing_apply (TSGO_TESTING builds only): the operators PCG applies, read out column by column
 //
 // There is NO CPU fallback in this file: every entry point that computes needs a gfx950 device and
@@ -45,6 +46,7 @@
 #include "host/parallel.h"
 #include "host/problem.h"
 #include "tsgo_amg_kernels.h"
+#include "tsgo_gate_kernels.h"
 #include "tsgo_kernels.h"
 #include "tsgo_lm_kernels.h"
 #include "tsgo_marginal_kernels.h"
@@ -149,6 +151,8 @@ struct IEngine {
     virtual int marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, tsgo_marginal_stats* st) = 0;
     virtual int joint_marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, int64_t cov_cap, int* dim_out, tsgo_marginal_stats* st) = 0;
     virtual int edge_report(double* rec_out, int64_t cap_edges, tsgo_edge_report_stats* st) = 0;
+    virtual int gate_edges(int n, const uint32_t* e_type, const uint32_t* e_ids, const double* e_meas, const double* e_inf, double rel_tol, double* rec_out,
+                           double* innov_out, tsgo_gate_stats* st) = 0;
 #ifdef TSGO_TESTING
     virtual int testing_apply(int which, const double* in, double* out, int n_cols) = 0;
 #endif
@@ -449,6 +453,7 @@ template <typename T> struct Engine : IEngine {
 #include "engine/engine_solve.inc"
 #include "engine/engine_probes.inc"
 #include "engine/engine_marginals.inc"
+#include "engine/engine_gate.inc"
 #include "engine/engine_report.inc"
 #ifdef TSGO_TESTING
 #include "engine/engine_testing.inc"
@@ -562,6 +567,11 @@ int tsgo_joint_marginals(tsgo_optimizer* o, const uint32_t* ids, int32_t n_ids, 
 int tsgo_edge_report(tsgo_optimizer* o, double* rec_out, int64_t cap_edges, tsgo_edge_report_stats* stats) {
     if (!o) return tsgo::set_error(-1, "tsgo_edge_report: null handle");
     return o->eng->edge_report(rec_out, cap_edges, stats);
+}
+int tsgo_gate_edges(tsgo_optimizer* o, int32_t n, const uint32_t* e_type, const uint32_t* e_ids, const double* e_meas, const double* e_inf, double rel_tol,
+                    double* rec_out, double* innov_out, tsgo_gate_stats* stats) {
+    if (!o) return tsgo::set_error(-1, "tsgo_gate_edges: null handle");
+    return o->eng->gate_edges(n, e_type, e_ids, e_meas, e_inf, rel_tol, rec_out, innov_out, stats);
 }
 void tsgo_reset_history(tsgo_optimizer* o) {
     if (o && o->eng) o->eng->reset_history();

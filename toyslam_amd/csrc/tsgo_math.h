@@ -104,19 +104,30 @@ template <typename T> struct OdomLin { T a[3], e[3], rho; };
 //   b_1 = [h; -ht + kt],  b_2 = [-h; -kt]   with h = M^T Omega_t e_t, ht = q^T Omega_t e_t, kt = kappa a2 e_th
 // (M = I, q = 0, kappa = 1 gives back the constant-Jacobian blocks: K = diag(a0, a1), w = a2, b = +-a e.)
 template <typename T> struct OdomBlocks { T k00, k01, k11, g0, g1, s, w, h0, h1, ht, kt; };
+// The Jacobians themselves (M row-major, q, kappa): A = [[-M, q], [0 0 -kappa]], B = [[M, 0], [0 0 kappa]].  odom_blocks forms its
+// products from them; tsgo_gate_edges (tsgo_gate_kernels.h) needs A and B as matrices.
+template <typename T> struct OdomJac { T m00, m01, m10, m11, q0, q1, kappa; };
 
 template <typename T>
-TSGO_HD OdomBlocks<T> odom_blocks(const OdomLin<T>& o, T x1, T y1, T c1, T s1, T x2, T y2, T c2, T s2, const T* mi) {
-    OdomBlocks<T> b;
+TSGO_HD OdomJac<T> odom_jacobians(T x1, T y1, T c1, T s1, T x2, T y2, T c2, T s2, const T* mi) {
+    OdomJac<T> j;
     const T dx = x2 - x1, dy = y2 - y1;
     const T px = c1 * dx + s1 * dy, py = c1 * dy - s1 * dx;
-    const T m00 = mi[0] * c1 - mi[1] * s1, m01 = mi[0] * s1 + mi[1] * c1, m10 = mi[3] * c1 - mi[4] * s1, m11 = mi[3] * s1 + mi[4] * c1;
-    const T q0 = mi[0] * py - mi[1] * px, q1 = mi[3] * py - mi[4] * px;
+    j.m00 = mi[0] * c1 - mi[1] * s1; j.m01 = mi[0] * s1 + mi[1] * c1; j.m10 = mi[3] * c1 - mi[4] * s1; j.m11 = mi[3] * s1 + mi[4] * c1;
+    j.q0 = mi[0] * py - mi[1] * px; j.q1 = mi[3] * py - mi[4] * px;
     const T cc = c1 * c2 + s1 * s2, ss = c1 * s2 - s1 * c2;
     const T d00 = mi[0] * cc + mi[1] * ss, d10 = mi[3] * cc + mi[4] * ss;
     const T e00 = -mi[0] * ss + mi[1] * cc, e10 = -mi[3] * ss + mi[4] * cc;
     const T den = d00 * d00 + d10 * d10;
-    const T kappa = den > T(0) ? (d00 * e10 - d10 * e00) / den : T(0);      // a padding slot of the device table has mi = 0 (and zero weights)
+    j.kappa = den > T(0) ? (d00 * e10 - d10 * e00) / den : T(0);      // a padding slot of the device table has mi = 0 (and zero weights)
+    return j;
+}
+
+template <typename T>
+TSGO_HD OdomBlocks<T> odom_blocks(const OdomLin<T>& o, T x1, T y1, T c1, T s1, T x2, T y2, T c2, T s2, const T* mi) {
+    OdomBlocks<T> b;
+    const OdomJac<T> j = odom_jacobians<T>(x1, y1, c1, s1, x2, y2, c2, s2, mi);
+    const T m00 = j.m00, m01 = j.m01, m10 = j.m10, m11 = j.m11, q0 = j.q0, q1 = j.q1, kappa = j.kappa;
     const T a0 = o.a[0], a1 = o.a[1], a2 = o.a[2];
     b.k00 = m00 * m00 * a0 + m10 * m10 * a1; b.k01 = m00 * m01 * a0 + m10 * m11 * a1; b.k11 = m01 * m01 * a0 + m11 * m11 * a1;
     b.g0 = m00 * a0 * q0 + m10 * a1 * q1; b.g1 = m01 * a0 * q0 + m11 * a1 * q1;

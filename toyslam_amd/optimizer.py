@@ -190,6 +190,34 @@ class HipOptimizer:
         summary["chi2"] = st.chi2
         return rec, summary
 
+    def gate_edges(self, e_type, e_ids=None, e_meas=None, e_inf=None, rel_tol=0.0, innovation=False):
+        """Mahalanobis gate of candidate edges against the joint marginal of their vertices (tsgo_gate_edges).  The candidates come as
+        the four edge arrays of a graph (e_type (K,), e_ids (K, 2), e_meas (K, 9), e_inf (K, 3)), or as one object that has them as
+        attributes (a GraphArrays whose edges are the candidates); they are not added to the graph.  Returns (res, stats): res a dict of
+        arrays in candidate order — e (K, 3), s, d2, logdet (K,), dof, status (K,) integers, with innovation=True also innov (K, 3, 3),
+        S in the leading dof x dof — and stats a dict of tsgo_gate_stats (its `solve` a dict of tsgo_marginal_stats).  Accept a
+        candidate when d2 is below the chi^2 quantile of its dof (99 %: 11.345 for 3, 9.210 for 2).  rel_tol <= 0: the handle's
+        pcg_rel_tol."""
+        if e_ids is None:
+            e_type, e_ids, e_meas, e_inf = e_type.e_type, e_type.e_ids, e_type.e_meas, e_type.e_inf
+        e_type = np.ascontiguousarray(np.asarray(e_type, dtype=np.uint32).reshape(-1))
+        K = len(e_type)
+        e_ids = np.ascontiguousarray(np.asarray(e_ids, dtype=np.uint32).reshape(K, 2))
+        e_meas = np.ascontiguousarray(np.asarray(e_meas, dtype=np.float64).reshape(K, 9))
+        e_inf = np.ascontiguousarray(np.asarray(e_inf, dtype=np.float64).reshape(K, 3))
+        rec = np.zeros((K, 8))
+        innov = np.zeros((K, 3, 3)) if innovation else None
+        st = _lib.tsgo_gate_stats()
+        ptr = (lambda a: a.ctypes.data) if K else (lambda a: None)
+        _lib.check(self.lib, self.lib.tsgo_gate_edges(self.h, K, ptr(e_type), ptr(e_ids), ptr(e_meas), ptr(e_inf), float(rel_tol), ptr(rec),
+                                                       innov.ctypes.data if innovation and K else None, C.byref(st)), "tsgo_gate_edges")
+        res = dict(e=rec[:, 0:3], s=rec[:, 3], d2=rec[:, 4], dof=rec[:, 5].astype(np.int64), logdet=rec[:, 6], status=rec[:, 7].astype(np.int64))
+        if innovation:
+            res["innov"] = innov
+        stats = {f: getattr(st, f) for f, _t in st._fields_ if f not in ("solve", "reserved")}
+        stats["solve"] = {f: getattr(st.solve, f) for f, _t in st.solve._fields_}
+        return res, stats
+
     def time_kernel(self, which, reps=50):
         us = C.c_double(); nbytes = C.c_double()
         _lib.check(self.lib, self.lib.tsgo_time_kernel(self.h, which, reps, C.byref(us), C.byref(nbytes)),
