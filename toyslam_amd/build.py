@@ -11,6 +11,10 @@ HOST_SRC = ["host/problem.cpp", "host/amg.cpp", "host/codec.cpp", "host/synth.cp
 HIP_SO = os.path.join(HERE, "libtsgo_hip.so")
 HOST_SO = os.path.join(HERE, "libtsgo_host.so")
 HIP_TESTING_SO = os.path.join(HERE, "libtsgo_hip_testing.so")
+HIP_PLAIN_SO = os.path.join(HERE, "libtsgo_hip_plain.so")
+# Kernarg preload (gfx950): the command processor hands the first dwords of a kernel's arguments over in SGPRs before the wave starts
+# (the compiler clamps 16 to the 14 dwords left beside the kernarg pointer); csrc/tsgo_kernels.h, "Argument heads".
+PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 SERVER = os.path.join(HERE, "graph_optimizer")
 
 
@@ -41,20 +45,27 @@ def build_host(force=False):
     return HOST_SO
 
 
-def build_hip(force=False):
-    if force or _newer(HIP_SO, _all_sources()):
-        cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result",
-               "-o", HIP_SO, "tsgo_hip.hip"] + HOST_SRC + ["-lrccl", "-lpthread"]
+def _hip_library(out, extra, force):
+    """One hipcc command line for every build of the device library: `extra` is all that tells them apart."""
+    if force or _newer(out, _all_sources()):
+        cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result"] + extra + [
+               "-o", out, "tsgo_hip.hip"] + HOST_SRC + ["-lrccl", "-lpthread"]
         subprocess.check_call(cmd, cwd=CSRC)
-    return HIP_SO
+    return out
+
+
+def build_hip(force=False):
+    return _hip_library(HIP_SO, PRELOAD, force)
 
 
 def build_hip_testing(force=False):
-    if force or _newer(HIP_TESTING_SO, _all_sources()):
-        cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result", "-DTSGO_TESTING",
-               "-o", HIP_TESTING_SO, "tsgo_hip.hip"] + HOST_SRC + ["-lrccl", "-lpthread"]
-        subprocess.check_call(cmd, cwd=CSRC)
-    return HIP_TESTING_SO
+    return _hip_library(HIP_TESTING_SO, ["-DTSGO_TESTING"] + PRELOAD, force)
+
+
+def build_hip_plain(force=False):
+    """The product library's sources WITHOUT kernarg preload: the B side of A/B measurements and of the bitwise comparison
+    (tests/test_gpu_kernarg_preload.py, tests/test_kernarg_heads.py).  Not a product binary: build_all does not build it."""
+    return _hip_library(HIP_PLAIN_SO, [], force)
 
 
 def build_server(force=False):
@@ -62,7 +73,7 @@ def build_server(force=False):
     if not os.path.exists(src):
         return None
     if force or _newer(SERVER, _all_sources()):
-        cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-result", "-o", SERVER,
+        cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-result"] + PRELOAD + ["-o", SERVER,
                "host/server.cpp", "tsgo_hip.hip"] + HOST_SRC + ["-lrccl", "-lpthread"]
         subprocess.check_call(cmd, cwd=CSRC)
     return SERVER
@@ -79,4 +90,4 @@ def build_all(force=False):
 
 
 if __name__ == "__main__":
-    print(build_all(force=True))
+    print(build_all(force=True), build_hip_plain(force=True))

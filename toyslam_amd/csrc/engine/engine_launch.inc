@@ -22,6 +22,12 @@
     template <typename... P, typename... A> void launch(void (*kernel)(P...), int grid, A&&... args) {
         kernel<<<dim3(grid), dim3(kBlock), 0, stream>>>(std::forward<A>(args)...);
     }
+    // A table kernel with an argument head (tsgo_kernels.h, "Argument heads"): the walked table's row offsets, slice and vertex counts and
+    // the grid's eighth under the XCD map go first, as plain arguments; `args` continue the head and then list everything else
+    template <typename... P, typename... A> void launch_table(void (*kernel)(P...), int grid, const Table<T>& tb, A&&... args) {
+        launch(kernel, grid, tb.row_off, tb.n_slices, tb.n_vertices, xcd8(tb.xcd, grid), std::forward<A>(args)...);
+    }
+    static int xcd8(int xcd, int grid) { return xcd ? grid / 8 : 0; }      // what the kernels' xcd8 argument takes: gridDim.x / 8, or 0 for round-robin
     std::string lvl(const char* role, size_t l) const { return std::string(role) + " L" + std::to_string(l); }
     // algorithmic bytes of the table kernels (DESIGN.md section 4) and of the block-row kernels of the cycle
     double od_slots_live() { if (od_live < 0) { od_live = 0; for (uint32_t e : pr.odom.edge) od_live += e != kNoEdge; } return od_live; }
@@ -80,14 +86,14 @@
         const int zf = (py_rules() || lm_rules()) ? 1 : 0;
         if (tl.n_slices == 0) return;
         pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick<0, 1>(rk(), [&](auto rk) {
-            launch(k_lin_lm<T, g, pri, rk>, nbL, tl, ps, lmrec, gauge_l, ninv, (T)lambda, zf, pri ? lm_prior_args() : no_priors(), robust_args());
+            launch_table(k_lin_lm<T, g, pri, rk>, nbL, tl, zf, lmrec, (const T*)ps, (const T*)gauge_l, ninv, tl, (T)lambda, pri ? lm_prior_args() : no_priors(), robust_args());
         }); }); });
     }
     void launch_lin_pose_only() {       // (tsgo_time_kernel too)
         const int zf = (py_rules() || lm_rules()) ? 1 : 0;
         pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick<0, 1>(rk(), [&](auto rk) {
-            launch(k_lin_pose<T, g, general, pri, rk>, nbP, tp, to, ps, lmrec, gauge_p, pr.pose_first, pr.pose_last, part, part + (size_t)pr.P * 18, (T)lambda, zf,
-                   general ? odom_analytic_flag() : 0, pri ? pose_prior_args() : no_priors(), robust_args());
+            launch_table(k_lin_pose<T, g, general, pri, rk>, nbP, tp, zf, (const T*)ps, (const T*)lmrec, to.row_off, (const T*)gauge_p, tp, to, pr.pose_first, pr.pose_last, part,
+                         part + (size_t)pr.P * 18, (T)lambda, general ? odom_analytic_flag() : 0, pri ? pose_prior_args() : no_priors(), robust_args());
         }); }); }); });
     }
     // rules = 2: robustified chi^2 at the current estimates, nbP partials into `out` (tsgo_lm_kernels.h; tsgo_time_kernel 7 too).  One launch,
@@ -120,8 +126,9 @@
     void launch_schur_lm(int slot, bool low, const GateArgs<T>* gate, const char* wh) {
         pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(low, [&](auto lo) {
             PF(bytes_schur_lm(lo) + (gate ? 2.0 * nbC * sizeof(T) : 0.0), gate ? "stopping rule + in-cycle product" : wh, "k_schur_lm", tname(), g, 0, lo);
-            if (tl.n_slices > 0) launch(k_schur_lm<T, g, 0, lo>, nbL, tl, zc, lmrec, (const T*)ninv, tvec, st[slot], T(0), dl, npart,
-                                        lo ? (const float*)zc32 : nullptr, lo ? tvec32 : nullptr, lo && gate ? *gate : no_gate(), T(0), (T*)nullptr);
+            const GateArgs<T> ga = lo && gate ? *gate : no_gate();      // the head carries the state once: the gate's own where there is one (launch_iteration: st[slot])
+            if (tl.n_slices > 0) launch_table(k_schur_lm<T, g, 0, lo>, nbL, tl, ga.st ? ga.n : 0, ga.st ? ga.st : st[slot], (const T*)ninv, ga.rdr_part, ga.bpart, tl, (const T*)zc, lmrec, tvec,
+                                              T(0), dl, npart, lo ? (const float*)zc32 : nullptr, lo ? tvec32 : nullptr, ga, T(0), (T*)nullptr);
         }); });
     }
     void launch_schur_pose(int slot, bool low, const T* rvec, T* rz_part, bool post_smooth, bool as_residual, const char* wh) {
@@ -129,9 +136,16 @@
             PF(bytes_schur_pose(lo) + (post_smooth ? pr.P * (6 + 3 + 3 + 3) * (double)sizeof(T) : 0.0), post_smooth ? "in-cycle product + post-smoothing L0" : wh, "k_schur_pose", tname(), g, lo, general);
             const T* pm_ = post_smooth ? (const T*)minv : (const T*)nullptr;      // the level-0 post-smoothing in this pass's epilogue (k_schur_pose)
             const T* pr_ = (post_smooth || as_residual) ? (const T*)r : (const T*)nullptr;      // ... or sbuf = r - S z (as_residual: the cycle's first product)
-            launch(k_schur_pose<T, g, lo, general>, nbP, tp, to, zc, tvec, dp, pr.pose_first, pr.pose_last, sbuf, sbuf + (size_t)pr.P * 3, st[slot], rvec, rz_part,
-                   lo ? (const float*)zc32 : nullptr, lo ? (const float*)tvec32 : nullptr, pm_, pr_, lo ? (const T*)omega_dev : nullptr, lo ? zc : nullptr);
+            launch_table(k_schur_pose<T, g, lo, general>, nbP, tp, (const CgState<T>*)st[slot], (const T*)zc, lo ? (const float*)zc32 : nullptr, to.row_off, tp, to, (const T*)tvec, (const T*)dp,
+                         pr.pose_first, pr.pose_last, sbuf, sbuf + (size_t)pr.P * 3, rvec, rz_part, lo ? (const float*)tvec32 : nullptr, pm_, pr_, lo ? (const T*)omega_dev : nullptr, lo ? zc : nullptr);
         }); }); });
+    }
+    // the warm start's two kernels: what they read of `w` before their first vector load goes in their plain heads (and is read from there alone)
+    void launch_pack_x(const WarmTerms<T>& w, int* order_out) {
+        hipLaunchKernelGGL((k_pack_x<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, w.n_max, w.n_tested, w.nb_err, w.errpart, x, zc, order_out, w);
+    }
+    void launch_save_x(const WarmTerms<T>& w, T* xsave, T* errpart) {
+        hipLaunchKernelGGL((k_save_x<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, w.n_max, (const T*)x, zc, xsave, errpart, w);
     }
     static int grid_for(int n, int per_thread_lanes = 1) { return std::max(1, (int)(((size_t)n * per_thread_lanes + kBlock - 1) / kBlock)); }
 
@@ -212,7 +226,7 @@
         DevLevel<T>& L = lv[level];
         pick_block_row(lpr, L.n, [&](auto lanes, auto pk, int grid, int xcd) {
             PF(bytes_sweep(L), lvl(role, level).c_str(), "k_bcsr_residual", tname(), lanes, MODE, 1, pk, tname_of<V>());
-            launch(k_bcsr_residual<T, lanes, MODE, 1, pk, V>, grid, L.n, L.A_ptr, L.A_col, (const void*)L.Apm, rhs, cur, (const H*)L.Dinv, out, omega, s, xcd);
+            launch(k_bcsr_residual<T, lanes, MODE, 1, pk, V>, grid, L.n, xcd8(xcd, grid), s, L.A_ptr, L.A_col, (const void*)L.Apm, cur, rhs, (const H*)L.Dinv, out, omega);
         });
     }
     // restriction of level `level` (SUB 1: of va - vb, two fine vectors), with the first pre-sweep of the level below where dinv_next is given
@@ -220,7 +234,7 @@
         DevLevel<T>& L = lv[level];
         pick_block_row(lpr, L.n_agg, [&](auto lanes, auto pk, int grid, int xcd) {
             PF(bytes_transfer(L, SUB ? 2 : 1, level == 0), lvl("restrict from", level).c_str(), "k_restrict", tname(), lanes, SUB, pk, tname_of<VI>(), tname_of<VO>());
-            launch(k_restrict<T, lanes, SUB, pk, VI, VO>, grid, L.n_agg, L.R_ptr, L.R_col, (const uint32_t*)L.Rpm, va, vb, rc, dinv_next, z_next, omega, s, xcd);
+            launch(k_restrict<T, lanes, SUB, pk, VI, VO>, grid, L.n_agg, xcd8(xcd, grid), s, L.R_ptr, L.R_col, (const uint32_t*)L.Rpm, va, vb, rc, dinv_next, z_next, omega);
         });
     }
     template <typename VE, typename VZ> void launch_prolong(size_t level, const VE* e, VZ* z, int zs, const CgState<T>* s) {
@@ -228,7 +242,7 @@
         float* z32 = (level == 0 && low_cycle && !explicit0) ? zc32 : (float*)nullptr;      // level 0 prolongs into the pose records: keep their f32 copy current
         pick_block_row(lanes_for((double)L.nnzP / std::max(1, L.n)), L.n, [&](auto lanes, auto pk, int grid, int xcd) {
             PF(bytes_transfer(L, 2, level == 0), lvl("prolong into", level).c_str(), "k_prolong_add", tname(), lanes, pk, tname_of<VE>(), tname_of<VZ>());
-            launch(k_prolong_add<T, lanes, pk, VE, VZ>, grid, L.n, L.P_ptr, L.P_col, (const uint32_t*)L.Ppm, e, z, zs, s, z32, xcd);
+            launch(k_prolong_add<T, lanes, pk, VE, VZ>, grid, L.n, xcd8(xcd, grid), s, L.P_ptr, L.P_col, (const uint32_t*)L.Ppm, e, z, zs, z32);
         });
     }
 
@@ -245,7 +259,7 @@
             const int lprA = lanes_for((double)L.nnzA / std::max(1, L.n));
             for (int it = 0; it < kRhoSteps; ++it) {
                 pick<4, 8, 16, 32, 64>(lprA, [&](auto lanes) {     // the block-indexed matrix (PM = 0): level 0 has no cycle-format copy
-                    launch(k_bcsr_residual<T, lanes, 2, 0>, grid_for(L.n, lanes), L.n, L.A_ptr, L.A_col, (const void*)L.A, (const T*)a, (const T*)a, (const H*)L.Dinv, b, (const T*)omega_dev, (const CgState<T>*)st[0], 0);
+                    launch(k_bcsr_residual<T, lanes, 2, 0>, grid_for(L.n, lanes), L.n, 0, (const CgState<T>*)st[0], L.A_ptr, L.A_col, (const void*)L.A, (const T*)a, (const T*)a, (const H*)L.Dinv, b, (const T*)omega_dev);
                 });
                 std::swap(a, b);
             }
@@ -283,7 +297,7 @@
         DevLevel<T>& L = lv[0];
         pick_block_row(lanes_for_sweep((double)L.nnzA / std::max(1, L.n), L.n), L.n, [&](auto lanes, auto pk, int grid, int xcd) {
             PF(bytes_sweep(L), "in-cycle product (explicit)", "k_bcsr_apply", tname(), lanes, pk);
-            launch(k_bcsr_apply<T, lanes, pk>, grid, L.n, L.A_ptr, L.A_col, (const uint32_t*)L.Apm, (const T*)zc, kPoseRec, sbuf, (const CgState<T>*)st[slot], xcd);
+            launch(k_bcsr_apply<T, lanes, pk>, grid, L.n, xcd8(xcd, grid), (const CgState<T>*)st[slot], L.A_ptr, L.A_col, (const uint32_t*)L.Apm, (const T*)zc, kPoseRec, sbuf);
         });
         return 0;
     }
@@ -341,7 +355,7 @@
             hipLaunchKernelGGL((k_rowdot_wg<T, V>), dim3(nd), dim3(kBlock), 0, stream, nd, n3, (const float*)tail_Etf, cv(L.r), v(tail_t), s);
             pick<0, 1>(mem.cy16, [&](auto pk) {
                 PF(bytes_sweep(L) + (double)n3 * nd * sizeof(float), lvl("cycles of", nl - 2).c_str(), "k_tail_up", tname(), pk, tname_of<V>());
-                launch(k_tail_up<T, pk, V>, L.n, L.n, (const int*)L.A_ptr, (const int*)L.A_col, (const uint32_t*)L.Apm, (const H*)L.Dinv, (const T*)(omega_dev + nl - 2), cv(L.z), nd, (const float*)tail_Gf, cv(tail_t), v(L.z2), s);
+                launch(k_tail_up<T, pk, V>, L.n, L.n, nd, s, (const int*)L.A_ptr, (const float*)tail_Gf, cv(tail_t), (const int*)L.A_col, (const uint32_t*)L.Apm, cv(L.z), (const H*)L.Dinv, (const T*)(omega_dev + nl - 2), v(L.z2));
             });
         } else if (dense_bottom) {      // z2 = B r: pre-sweep, coarse correction through the dense inverse and post-sweep of the last explicit level at once
             DevLevel<T>& L = lv[nl - 1];
@@ -429,6 +443,6 @@
     void launch_cg_update(int slot) {
         const T tol2 = (T)(cfg.pcg_rel_tol * cfg.pcg_rel_tol);
         PF(pr.P * (3 + 3 + 6 + 4 * 3 * 2) * (double)sizeof(T), "vector step", "k_cg_update", tname());
-        hipLaunchKernelGGL((k_cg_update<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, sbuf, sbuf + (size_t)pr.P * 3, nbP, gpart[slot], nbC,
-                           gpart[slot ^ 1], st[slot], st[slot ^ 1], minv, r, p, q, x, zc, tol2, cfg.pcg_max_iters, (const T*)gscale_dev);
+        hipLaunchKernelGGL((k_cg_update<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, nbP, (const CgState<T>*)st[slot], (const T*)(sbuf + (size_t)pr.P * 3), (const T*)gpart[slot], nbC,
+                           (const T*)sbuf, gpart[slot ^ 1], st[slot ^ 1], minv, r, p, q, x, zc, tol2, cfg.pcg_max_iters, (const T*)gscale_dev);
     }

@@ -108,8 +108,8 @@
                     case 1: launch_schur_pose(0, false, (const T*)nullptr, (T*)nullptr, false, false, ""); break;
                     case 2: {   // state slot 1 is never written here, slot 0 stays "iters = 0, not done"
                         const T tol2 = (T)0;
-                        hipLaunchKernelGGL((k_cg_update<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, sbuf, sbuf + (size_t)pr.P * 3, nbP, gpart[0], nbC,
-                                           gpart[1], st[0], st[1], minv, r, p, q, x, zc, tol2, 1 << 30, (const T*)one_dev);
+                        hipLaunchKernelGGL((k_cg_update<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, nbP, (const CgState<T>*)st[0], (const T*)(sbuf + (size_t)pr.P * 3), (const T*)gpart[0], nbC,
+                                           (const T*)sbuf, gpart[1], st[1], minv, r, p, q, x, zc, tol2, 1 << 30, (const T*)one_dev);
                         break;
                     }
                     case 3: launch_lin_lm(); break;

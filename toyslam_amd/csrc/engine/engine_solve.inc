@@ -60,7 +60,7 @@
         w.n_max = std::max(1, std::min({mem.n_prev, (int)cfg.warm_start, kMaxWarm}));
         w.n_tested = std::min(mem.n_tested, w.n_max);
         w.errpart = warm_err; w.nb_err = nbC;
-        hipLaunchKernelGGL((k_pack_x<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, x, zc, w, warm_order_dev);
+        launch_pack_x(w, warm_order_dev);
         if (int rc = launch_matvec(0)) return rc;
         hipLaunchKernelGGL((k_warm_residual<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, (const T*)sbuf, (const T*)minv, r, zc, (const T*)(amg_on ? omega_dev : one_dev), npart, amg_on && low_cycle ? zc32 : (float*)nullptr);
         hipLaunchKernelGGL((k_warm_scale<T>), dim3(1), dim3(kBlock), 0, stream, nbC, (const T*)gpart[0], (const T*)npart, amg_on ? (T*)nullptr : gpart[0], gscale_dev,
@@ -288,14 +288,14 @@
             warm_coefficients(w);
             for (int j = 0; j + 1 < kMaxWarm; ++j) w.v[j] = hist[j + 1];
             w.n_max = std::min({mem.n_prev, (int)cfg.warm_start, kMaxWarm - 1});      // orders that can be tested on this delta
-            hipLaunchKernelGGL((k_save_x<T>), dim3(nbC), dim3(kBlock), 0, stream, P, (const T*)x, zc, hist[0], w, warm_err);
+            launch_save_x(w, hist[0], warm_err);
             mem.n_tested = w.n_max; mem.have_prev = true; mem.n_prev = std::min(mem.n_prev + 1, kMaxWarm);
         } else {      // a probe (step 0) leaves nothing to carry over
-            hipLaunchKernelGGL((k_pack_x<T>), dim3(nbC), dim3(kBlock), 0, stream, P, x, zc, WarmTerms<T>{}, (int*)nullptr);
+            launch_pack_x(WarmTerms<T>{}, (int*)nullptr);
             mem.have_prev = false; mem.n_prev = 0; mem.n_tested = 0;
         }
         if (tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
-            launch(k_schur_lm<T, g, 1, 0>, nbL, tl, zc, lmrec, (const T*)ninv, tvec, st[0], step, dl, npart + nbC, (const float*)nullptr, (float*)nullptr, no_gate(), T(0), (T*)nullptr);
+            launch_table(k_schur_lm<T, g, 1, 0>, nbL, tl, 0, st[0], (const T*)ninv, (const T*)nullptr, (const T*)nullptr, tl, (const T*)zc, lmrec, tvec, step, dl, npart + nbC, (const float*)nullptr, (float*)nullptr, no_gate(), T(0), (T*)nullptr);
         });
         hipLaunchKernelGGL((k_pose_update<T>), dim3(nbC), dim3(kBlock), 0, stream, P, x, ps, theta, step, npart);
         const int nl = tl.n_slices > 0 ? nbL : 0;
@@ -334,10 +334,10 @@
         const int P = pr.P, L = pr.L, nl = lm_nl();
         T* norm_p = lm_red; T* norm_l = lm_red + nbC; T* pred_p = norm_l + nl; T* pred_l = pred_p + nbC; T* chi = pred_l + nl;
         launch(k_lm_state<T, 0>, grid_for(std::max(P, L)), P, L, ps, theta, lmrec, snap_ps, snap_theta, snap_lm);
-        hipLaunchKernelGGL((k_pack_x<T>), dim3(nbC), dim3(kBlock), 0, stream, P, x, zc, WarmTerms<T>{}, (int*)nullptr);
+        launch_pack_x(WarmTerms<T>{}, (int*)nullptr);
         mem.have_prev = false; mem.n_prev = 0; mem.n_tested = 0;
         if (nl > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
-            launch(k_schur_lm<T, g, 2, 0>, nbL, tl, zc, lmrec, (const T*)ninv, tvec, st[0], T(1), dl, norm_l, (const float*)nullptr, (float*)nullptr, no_gate(), (T)lam, pred_l);
+            launch_table(k_schur_lm<T, g, 2, 0>, nbL, tl, 0, st[0], (const T*)ninv, (const T*)nullptr, (const T*)nullptr, tl, (const T*)zc, lmrec, tvec, T(1), dl, norm_l, (const float*)nullptr, (float*)nullptr, no_gate(), (T)lam, pred_l);
         });
         launch(k_pose_update_lm<T>, nbC, P, (const T*)x, ps, theta, (const T*)part, (T)lam, norm_p, pred_p);
         launch_chi2(chi);

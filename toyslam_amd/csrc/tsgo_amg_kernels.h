@@ -437,22 +437,24 @@ __global__ __launch_bounds__(kBlock) void k_mirror_pack(int n_blocks, const int*
 // length of the dependent-load chain, so LPR lanes share one block row (one 3x3 block per lane per
 // trip, 72 contiguous bytes per lane) and finish with an LPR-lane xor-shuffle sum.
 
+// The block-row kernels' arguments begin with a plain head (tsgo_kernels.h, "Argument heads"): n, xcd8, st, the row pointer, the column
+// and matrix words and the gathered vector — what is needed until the first dependent vector load is out — and the epilogue's operands behind.
 // Block-row kernels of the big levels take the XCD-aware workgroup map of the table kernels (xcd_block(), tsgo_kernels.h): an XCD walks a
 // contiguous eighth of the rows, so the vector entries a row gathers (its neighbours': nearby rows) are fetched into ONE L2 instead of all
-// eight (PMC, round 3: k_restrict from level 0 fetched 1.74x its algorithmic bytes, k_prolong_add 1.48x).  xcd = 0: round-robin, as before.
-__device__ __forceinline__ int lpr_block(int xcd) { return xcd ? xcd_block() : (int)blockIdx.x; }
+// eight (PMC, round 3: k_restrict from level 0 fetched 1.74x its algorithmic bytes, k_prolong_add 1.48x).  xcd8 = 0: round-robin, as before.
+__device__ __forceinline__ int lpr_block(int xcd8) { return xcd8 ? xcd_block(xcd8) : (int)blockIdx.x; }      // xcd8: 0, or gridDim.x / 8
 
 // MODE 0: out = r - A z.   MODE 1: out = z + omega Dinv (r - A z)  (smoothing sweep).
 // MODE 2: out = Dinv A z  (power iteration for the smoother's damping).
 // PM: A is the cycle-format copy (above; PK = its encoding); otherwise the block-indexed f32 / HT matrix.
 // V: the vector (and accumulation) type, T by default; the cycle's levels >= 1 run it in CV<T>.
 template <typename T, int LPR, int MODE, int PM = 1, int PK = 0, typename V = T>
-__global__ __launch_bounds__(kBlock) void k_bcsr_residual(int n, const int* __restrict__ ptr, const int* __restrict__ col,
-                                                          const void* __restrict__ Av, const V* __restrict__ r, const V* __restrict__ z,
-                                                          const HT<T>* __restrict__ Dinv, V* __restrict__ out,
-                                                          const T* __restrict__ omega_ptr, const CgState<T>* __restrict__ st, int xcd = 0) {
+__global__ __launch_bounds__(kBlock) void k_bcsr_residual(int n, int xcd8, const CgState<T>* __restrict__ st, const int* __restrict__ ptr,
+                                                          const int* __restrict__ col, const void* __restrict__ Av, const V* __restrict__ z,
+                                                          const V* __restrict__ r, const HT<T>* __restrict__ Dinv, V* __restrict__ out,
+                                                          const T* __restrict__ omega_ptr) {
     const int done = MODE != 2 ? st->done : 0;
-    const int g = (lpr_block(xcd) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
+    const int g = (lpr_block(xcd8) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
     // LPR == 64: the row is wave-uniform, its bounds come through the scalar cache (one dependent round trip shorter)
     const int i = LPR == 64 ? __builtin_amdgcn_readfirstlane(g < n ? g : n - 1) : (g < n ? g : n - 1);
     V s0 = 0, s1 = 0, s2 = 0;
@@ -511,10 +513,10 @@ __global__ __launch_bounds__(kBlock) void k_bcsr_residual(int n, const int* __re
 // out = A z with z stored at row stride `zs` (research, TSGO_CYCLE_EXPLICIT0: the explicit level-0 matrix in place of the
 // implicit Schur product inside the cycle; z is the pose-record array zc, stride kPoseRec).  A plane-major (cycle format).
 template <typename T, int LPR, int PK>
-__global__ __launch_bounds__(kBlock) void k_bcsr_apply(int n, const int* __restrict__ ptr, const int* __restrict__ col, const uint32_t* __restrict__ A,
-                                                       const T* __restrict__ z, int zs, T* __restrict__ out, const CgState<T>* __restrict__ st, int xcd = 0) {
+__global__ __launch_bounds__(kBlock) void k_bcsr_apply(int n, int xcd8, const CgState<T>* __restrict__ st, const int* __restrict__ ptr, const int* __restrict__ col,
+                                                       const uint32_t* __restrict__ A, const T* __restrict__ z, int zs, T* __restrict__ out) {
     const int done = st->done;
-    const int g = (lpr_block(xcd) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
+    const int g = (lpr_block(xcd8) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
     const int i = g < n ? g : n - 1;
     T s0 = 0, s1 = 0, s2 = 0;
     int p0 = ptr[i];
@@ -538,13 +540,13 @@ __global__ __launch_bounds__(kBlock) void k_bcsr_apply(int n, const int* __restr
 // z_next = Dinv_next rc in the same pass.  SUB: v = a - b (level 0: r - S z, never materialised).
 // VI / VO: the fine (input) and coarse (output) vector types; sums in the wider of the two (level 0 -> 1: T in, CV<T> out).
 template <typename T, int LPR, int SUB, int PK = 0, typename VI = T, typename VO = T>
-__global__ __launch_bounds__(kBlock) void k_restrict(int n_agg, const int* __restrict__ rptr, const int* __restrict__ rcol,
-                                                     const uint32_t* __restrict__ Rv, const VI* __restrict__ va,
+__global__ __launch_bounds__(kBlock) void k_restrict(int n_agg, int xcd8, const CgState<T>* __restrict__ st, const int* __restrict__ rptr,
+                                                     const int* __restrict__ rcol, const uint32_t* __restrict__ Rv, const VI* __restrict__ va,
                                                      const VI* __restrict__ vb, VO* __restrict__ rc, const HT<T>* __restrict__ dinv_next,
-                                                     VO* __restrict__ z_next, const T* __restrict__ omega_ptr, const CgState<T>* __restrict__ st, int xcd = 0) {
+                                                     VO* __restrict__ z_next, const T* __restrict__ omega_ptr) {
     using A = decltype(VI(0) + VO(0));
     const int done = st->done;
-    const int g = (lpr_block(xcd) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
+    const int g = (lpr_block(xcd8) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
     const int a = g < n_agg ? g : n_agg - 1;
     A s0 = 0, s1 = 0, s2 = 0;
     int p0 = rptr[a];
@@ -583,12 +585,12 @@ __global__ __launch_bounds__(kBlock) void k_restrict(int n_agg, const int* __res
 // z_i += sum_a P_ia e_a; z has row stride `zs` (3 on coarse levels, kPoseRec for zc).  VE / VZ: the coarse and fine vector types
 // (into level 0: CV<T> in, T out); sums in the wider of the two.
 template <typename T, int LPR, int PK = 0, typename VE = T, typename VZ = T>
-__global__ __launch_bounds__(kBlock) void k_prolong_add(int n, const int* __restrict__ pptr, const int* __restrict__ pcol,
-                                                        const uint32_t* __restrict__ P, const VE* __restrict__ e, VZ* __restrict__ z, int zs,
-                                                        const CgState<T>* __restrict__ st, float* __restrict__ z32 = nullptr, int xcd = 0) {
+__global__ __launch_bounds__(kBlock) void k_prolong_add(int n, int xcd8, const CgState<T>* __restrict__ st, const int* __restrict__ pptr,
+                                                        const int* __restrict__ pcol, const uint32_t* __restrict__ P, const VE* __restrict__ e,
+                                                        VZ* __restrict__ z, int zs, float* __restrict__ z32 = nullptr) {
     using A = decltype(VE(0) + VZ(0));
     const int done = st->done;
-    const int g = (lpr_block(xcd) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
+    const int g = (lpr_block(xcd8) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
     const int i = g < n ? g : n - 1;
     A s0 = 0, s1 = 0, s2 = 0;
     int p0 = pptr[i];
@@ -871,9 +873,9 @@ __global__ __launch_bounds__(kBlock) void k_rowdot_wg(int n_rows, int n_cols, co
 // z_i = 2 z1_i - omega D_i^-1 sum_j A_ij z1_j + sum_m G[3i..3i+2][m] t[m]: one WORKGROUP per block row (A in the cycle format): the
 // row's blocks a lane each, the three dense rows of G spread over all 256 threads
 template <typename T, int PK, typename V = T>
-__global__ __launch_bounds__(kBlock) void k_tail_up(int n, const int* __restrict__ ptr, const int* __restrict__ col, const uint32_t* __restrict__ Apm, const HT<T>* __restrict__ Dinv,
-                                                    const T* __restrict__ omega_ptr, const V* __restrict__ z1, int nd, const float* __restrict__ Gf, const V* __restrict__ t,
-                                                    V* __restrict__ z, const CgState<T>* __restrict__ st) {
+__global__ __launch_bounds__(kBlock) void k_tail_up(int n, int nd, const CgState<T>* __restrict__ st, const int* __restrict__ ptr, const float* __restrict__ Gf,
+                                                    const V* __restrict__ t, const int* __restrict__ col, const uint32_t* __restrict__ Apm, const V* __restrict__ z1,
+                                                    const HT<T>* __restrict__ Dinv, const T* __restrict__ omega_ptr, V* __restrict__ z) {
     __shared__ V red6[kWavesPerBlock * 6];
     const int done = st->done;
     const int i = blockIdx.x;

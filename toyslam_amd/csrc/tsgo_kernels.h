@@ -72,21 +72,34 @@ template <typename T> struct Table {       // one SELL table on the device
 // record (pose records, landmark vectors) live in ONE L2 instead of being pulled into all eight
 // (profiles/r01a: 1.7x over-fetch on k_schur_lm).  Grids are rounded up to a multiple of 8; only speed
 // depends on the placement guess, never correctness.
-__device__ __forceinline__ int xcd_block() { return (int)((blockIdx.x % 8u) * (gridDim.x / 8u) + blockIdx.x / 8u); }
+// xcd_block(eighth): for the kernels whose argument head carries the grid's eighth (xcd8 = gridDim.x / 8 under the map, 0 for
+// round-robin): gridDim.x itself is a hidden kernel argument that would be fetched from memory.
+__device__ __forceinline__ int xcd_block(int eighth) { return (int)((blockIdx.x % 8u) * (unsigned)eighth + blockIdx.x / 8u); }
+__device__ __forceinline__ int xcd_block() { return xcd_block((int)(gridDim.x / 8u)); }
 
 // ---- accessors of the table kernels: values in, values out -------------------------------------------------------------------------
 // Where a thread stands: its slice (through the XCD map when the table asks for it), its lane, the vertex its group of G lanes works on,
 // whether the slice exists, and whether the lane is the group's head (the one that writes the vertex's result and folds its priors).
 struct Walk { int slice, lane, vertex, live, head; };
-template <int G, typename T> __device__ __forceinline__ Walk walk_of(const Table<T>& tb) {
+template <int G> __device__ __forceinline__ Walk walk_of(int n_slices, int xcd8) {      // xcd8: 0, or gridDim.x / 8 under the XCD map
     Walk w;
-    w.slice = (tb.xcd ? xcd_block() : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
-    w.live = w.slice < tb.n_slices;
+    w.slice = (xcd8 ? xcd_block(xcd8) : (int)blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+    w.live = w.slice < n_slices;
     w.lane = threadIdx.x & 63;
     w.vertex = w.slice * (64 / G) + w.lane / G;
     w.head = (w.lane % G) == 0;
     return w;
 }
+// (a table kernel without an argument head hands over its Table's: table_xcd8)
+template <typename T> __device__ __forceinline__ int table_xcd8(const Table<T>& tb) { return tb.xcd ? (int)(gridDim.x / 8u) : 0; }
+
+// Argument heads.  The command processor of gfx950 delivers the first 14 dwords of a kernel's arguments in SGPRs before the wave starts
+// (kernarg preload, the build's -amdgpu-kernarg-preload-count), but only the leading run of PLAIN arguments: it stops at the first
+// by-value aggregate.  The kernels launched per PCG iteration or per Gauss-Newton step therefore begin with what they need before their
+// first vector load is issued, as pointers and ints (a pointer is 2 dwords and 8-byte aligned); the aggregates come behind.  The table
+// kernels of that set start with the walked table's (row_off, n_slices, n_vertices, xcd8) — xcd8: the grid's eighth under the XCD map,
+// else 0; Engine::launch_table lists them — and read those four from the head alone: the copies inside their Table argument are not
+// used.  tools/kernarg_heads.py checks the assembly.
 
 // LM slot k: what was measured (static planes), what the linearisation left (dyn, or dyn32 under LOW), and the store of both copies.
 template <typename T> struct LmMeas { T zx, zy, w0, w1; };
@@ -169,7 +182,7 @@ template <typename T> __device__ __forceinline__ T block_sum_array(const T* a, i
 // b^T D^-1 b, sets st->done when the residual meets the tolerance, and — eager launches — tells the host thread in ONE aligned 8-byte
 // store that the seq-th launched iteration has started and what it saw (seq | done | fail | iterations completed; Engine::do_solve_paced).
 template <typename T> struct GateArgs { CgState<T>* st; const T* rdr_part; const T* bpart; int n; T tol2; int* host_flag; int seq; };
-template <typename T> __device__ __forceinline__ void iter_gate_body(const GateArgs<T> g, T* red) {
+template <typename T> __device__ __forceinline__ int iter_gate_body(const GateArgs<T> g, T* red) {      // thread 0 returns the verdict (done)
     const int done = g.st->done, iters = g.st->iters, fail0 = g.st->fail;
     T a = 0, b = 0;                                  // the partials are on their way while the state is looked at
     for (int k = threadIdx.x; k < g.n; k += kBlock) { a += g.rdr_part[k]; b += g.bpart[k]; }
@@ -183,6 +196,7 @@ template <typename T> __device__ __forceinline__ void iter_gate_body(const GateA
     if (g.host_flag && threadIdx.x == 0)      // ONE aligned 8-byte store: the host never sees the fields of two gates mixed
         *reinterpret_cast<volatile unsigned long long*>(g.host_flag) =
             ((unsigned long long)(unsigned)g.seq << 32) | ((unsigned long long)(done_now ? 1u : 0u) << 31) | ((unsigned long long)((unsigned)fail_now & 7u) << 28) | (unsigned long long)((unsigned)iters & 0x0fffffffu);
+    return done_now;
 }
 
 // Unary priors (edge types 3 and 4, include/tsgo.h), folded in by the lane that writes a vertex's result, in input order, in the world
@@ -221,20 +235,21 @@ template <typename T, typename K> __device__ __forceinline__ T pose_prior_fold(c
 // workgroup into pa.lm_chi (every wave reaches the workgroup sum: none leaves early)
 // RK = 1: the robust kernels of classes LM and landmark prior from ra (RobustArgs above)
 template <typename T, int G, int PRI = 0, int RK = 0>
-__global__ __launch_bounds__(kBlock) void k_lin_lm(Table<T> tb, const T* __restrict__ ps, T* __restrict__ lmrec,
-                                                   const T* __restrict__ gauge_l, T* __restrict__ ninv, T lambda, int zero_fixed,
+__global__ __launch_bounds__(kBlock) void k_lin_lm(const uint32_t* __restrict__ row_off, int n_slices, int n_vertices, int xcd8, int zero_fixed,
+                                                   T* __restrict__ lmrec, const T* __restrict__ ps, const T* __restrict__ gauge_l,
+                                                   T* __restrict__ ninv, Table<T> tb, T lambda,
                                                    const PriorArgs<T> pa = PriorArgs<T>{nullptr, nullptr, nullptr, 0},
                                                    const RobustArgs<T> ra = RobustArgs<T>{}) {
-    const Walk wk = walk_of<G>(tb);
+    const Walk wk = walk_of<G>(n_slices, xcd8);
     const int slice = wk.slice, lane = wk.lane, l = wk.vertex, live = wk.live;
     if (!PRI && !live) return;
     const auto rk_lm = robust_class<RK>(ra, kClassLm);
-    const bool valid = l < tb.n_vertices;      // (false on every lane of a wave past the last slice)
-    const int lc = valid ? l : tb.n_vertices - 1;
+    const bool valid = l < n_vertices;      // (false on every lane of a wave past the last slice)
+    const int lc = valid ? l : n_vertices - 1;
     const T lx = lmrec[(size_t)lc * kLmRec], ly = lmrec[(size_t)lc * kLmRec + 1];
     T dxx = 0, dxy = 0, dyy = 0, g0 = 0, g1 = 0;
     T chi = 0;
-    const uint32_t r0 = live ? tb.row_off[slice] : 0u, r1 = live ? tb.row_off[slice + 1] : 0u;
+    const uint32_t r0 = live ? row_off[slice] : 0u, r1 = live ? row_off[slice + 1] : 0u;
     for (uint32_t row = r0; row < r1; ++row) {
         const size_t k = (size_t)row * 64 + lane;
         const uint32_t i = tb.idx[k];
@@ -290,25 +305,26 @@ __global__ __launch_bounds__(kBlock) void k_lin_lm(Table<T> tb, const T* __restr
 // priors' chi^2 partials (pa.lm_chi, left by k_lin_lm<.., 1>) in workgroup 0's partial.  The host lists only the priors of owned poses.
 // RK = 1: the robust kernels of classes LM, ODOM, virtual landmark and pose prior from ra (RobustArgs above)
 template <typename T, int G, int OJ = 0, int PRI = 0, int RK = 0>
-__global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, const T* __restrict__ ps,
-                                                     const T* __restrict__ lmrec, const T* __restrict__ gauge_p,
-                                                     int pose_first, int pose_last, T* __restrict__ part,
-                                                     T* __restrict__ chi_part, T lambda, int zero_fixed, int odom_analytic = 0,
+__global__ __launch_bounds__(kBlock) void k_lin_pose(const uint32_t* __restrict__ row_off, int n_slices, int n_vertices, int xcd8, int zero_fixed,
+                                                     const T* __restrict__ ps, const T* __restrict__ lmrec,
+                                                     const uint32_t* __restrict__ od_row_off, const T* __restrict__ gauge_p,
+                                                     Table<T> tb, Table<T> od, int pose_first, int pose_last, T* __restrict__ part,
+                                                     T* __restrict__ chi_part, T lambda, int odom_analytic = 0,
                                                      const PriorArgs<T> pa = PriorArgs<T>{nullptr, nullptr, nullptr, 0},
                                                      const RobustArgs<T> ra = RobustArgs<T>{}) {
     __shared__ T red[kWavesPerBlock];
-    const Walk wk = walk_of<G>(tb);
+    const Walk wk = walk_of<G>(n_slices, xcd8);
     const int slice = wk.slice, lane = wk.lane, i = wk.vertex;
-    const bool live = wk.live, valid = live && i < tb.n_vertices;
+    const bool live = wk.live, valid = live && i < n_vertices;
     const auto rk_lm = robust_class<RK>(ra, kClassLm), rk_odom = robust_class<RK>(ra, kClassOdom);
     T chi = 0;
     if (live) {
-        const int ic = valid ? i : tb.n_vertices - 1;
+        const int ic = valid ? i : n_vertices - 1;
         const T x0 = ps[(size_t)ic * 4], y0 = ps[(size_t)ic * 4 + 1], c = ps[(size_t)ic * 4 + 2], s = ps[(size_t)ic * 4 + 3];
         T sA0 = 0, sA1 = 0, sAv0 = 0, sAv1 = 0, sVV = 0, ge0 = 0, ge1 = 0, get = 0;
         T K00 = 0, K01 = 0, K11 = 0, Kv0 = 0, Kv1 = 0, vKv = 0, wu0 = 0, wu1 = 0, wut = 0;
         {
-            const uint32_t r0 = tb.row_off[slice], r1 = tb.row_off[slice + 1];
+            const uint32_t r0 = row_off[slice], r1 = row_off[slice + 1];
             for (uint32_t row = r0; row < r1; ++row) {
                 const size_t k = (size_t)row * 64 + lane;
                 const uint32_t l = tb.idx[k];
@@ -338,7 +354,7 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(Table<T> tb, Table<T> od, c
         T od01 = 0, od02 = 0, od12 = 0;        // off-diagonal entries of the pose's ODOM diagonal block: analytic Jacobians only
         {
             const size_t S = od.slots;
-            const uint32_t r0 = od.row_off[slice], r1 = od.row_off[slice + 1];
+            const uint32_t r0 = od_row_off[slice], r1 = od_row_off[slice + 1];
             for (uint32_t row = r0; row < r1; ++row) {
                 const size_t k = (size_t)row * 64 + lane;
                 const uint32_t raw = od.idx[k];
@@ -473,30 +489,44 @@ __global__ __launch_bounds__(kBlock) void k_pose_finalize(int P, const T* __rest
 //   with g_l = D_l u recovered from the inverse block already in registers, one partial per workgroup into pred_part.
 // HOT KERNEL 1 of the PCG iteration.
 template <typename T, int G, int MODE, int LOW = 0>
-__global__ __launch_bounds__(kBlock) void k_schur_lm(Table<T> tb, const T* __restrict__ zc, T* __restrict__ lmrec,
-                                                     const T* __restrict__ ninv, T* __restrict__ t, const CgState<T>* __restrict__ st,
-                                                     T step, T* __restrict__ dl_out, T* __restrict__ norm_part,
+__global__ __launch_bounds__(kBlock) void k_schur_lm(const uint32_t* __restrict__ row_off, int n_slices, int n_vertices, int xcd8, int gate_n,
+                                                     CgState<T>* st, const T* __restrict__ ninv, const T* __restrict__ gate_rdr,
+                                                     const T* __restrict__ gate_b, Table<T> tb, const T* __restrict__ zc,
+                                                     T* __restrict__ lmrec, T* __restrict__ t, T step, T* __restrict__ dl_out, T* __restrict__ norm_part,
                                                      const float* __restrict__ zc32 = nullptr, float* __restrict__ t32 = nullptr,
                                                      const GateArgs<T> gate = GateArgs<T>{nullptr, nullptr, nullptr, 0, T(0), nullptr, 0},
                                                      T lambda = T(0), T* __restrict__ pred_part = nullptr) {
     __shared__ T red[kWavesPerBlock];
-    // The iteration's stopping rule rides in workgroup 0 of its first product (gate.st set): one launch fewer per iteration.  The other
-    // workgroups do not wait for the verdict: a solve that has just converged runs this one pass for nothing (its output is scratch) and
-    // every later kernel of the iteration sees st->done.
-    if (MODE == 0 && gate.st != nullptr && blockIdx.x == 0) iter_gate_body<T>(gate, red);
+    __shared__ int verdict;
+    // The iteration's stopping rule rides in workgroup 0 of its first product (gate_n > 0; the state it judges and sets is st, its
+    // partials gate_rdr / gate_b, the rest of GateArgs in `gate`): one launch fewer per iteration.  st is neither const nor __restrict__:
+    // workgroup 0 writes st->done in the very launch whose other workgroups read it.  Workgroup 0 hands the verdict to all of its waves
+    // through LDS: in the launch that finds the solve converged, ALL of workgroup 0 now leaves early (before, its waves read the flag each
+    // for itself and most computed their slices for nothing).  The other workgroups do not wait for the verdict: they read the flag with a
+    // relaxed atomic load and may see the value of before or after the gate; both are tolerated: a solve that has just converged runs this
+    // one pass for nothing (its output is scratch: nothing reads t once st->done is set) or skips it, and every later kernel of the
+    // iteration sees st->done.
     // the flag of a finished solve is requested here and tested after the loads that depend on the arguments alone (row bounds,
     // the vertex's inverse block) are on their way: tested first, it adds a scalar round trip in front of the first vector load
-    const int done = MODE == 0 ? st->done : 0;
-    const Walk wk = walk_of<G>(tb);
+    int done = 0;
+    if (MODE == 0 && gate_n > 0 && blockIdx.x == 0) {
+        const int d = iter_gate_body<T>(GateArgs<T>{st, gate_rdr, gate_b, gate_n, gate.tol2, gate.host_flag, gate.seq}, red);
+        if (threadIdx.x == 0) verdict = d;
+        __syncthreads();
+        done = __builtin_amdgcn_readfirstlane(verdict);
+    } else if (MODE == 0) done = __hip_atomic_load(&st->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const Walk wk = walk_of<G>(n_slices, xcd8);
     const int slice = wk.slice, lane = wk.lane, l = wk.vertex;
     T nrm = 0, prd = 0;
     if (wk.live) {
         T acc0 = 0, acc1 = 0;
-        const uint32_t r0 = tb.row_off[slice], r1 = tb.row_off[slice + 1];
+        uint32_t r0 = row_off[slice];
+        const uint32_t r1 = row_off[slice + 1];
         // the inverse block this vertex needs at the very end is requested first: its latency hides behind the rows
-        const int lq = (l < tb.n_vertices) ? l : tb.n_vertices - 1;
+        const int lq = (l < n_vertices) ? l : n_vertices - 1;
         const auto n01 = ld2<T>(ninv + (size_t)lq * kNinvRec);
         T n2 = ninv[(size_t)lq * kNinvRec + 2];
+        issue_before_exit(r0);      // (the row bounds too: with the flag's request at the very top, the compiler otherwise sinks them below the test)
         issue_before_exit(n2);
         if (done) return;
         // UB rows are walked at a time with every load of the batch issued before any use: a wave's time is
@@ -526,7 +556,7 @@ __global__ __launch_bounds__(kBlock) void k_schur_lm(Table<T> tb, const T* __res
             }
         }
         acc0 = group_sum<T, G>(acc0); acc1 = group_sum<T, G>(acc1);
-        if (l < tb.n_vertices && wk.head) {
+        if (l < n_vertices && wk.head) {
             T* lr = lmrec + (size_t)l * kLmRec;
             const T ixx = n01.x, ixy = n01.y, iyy = n2;
             const T t0 = ixx * acc0 + ixy * acc1, t1 = ixy * acc0 + iyy * acc1;
@@ -564,12 +594,13 @@ __global__ __launch_bounds__(kBlock) void k_schur_lm(Table<T> tb, const T* __res
 // KB schur_pose: per pose — out = Hpp v - W t (this shard's share), partial dot (out, v).
 // HOT KERNEL 2 of the PCG iteration.
 template <typename T, int G, int LOW = 0, int OJ = 0>
-__global__ __launch_bounds__(kBlock) void k_schur_pose(Table<T> tb, Table<T> od, const T* __restrict__ zc,
-                                                       const T* __restrict__ t, const T* __restrict__ dp,
+__global__ __launch_bounds__(kBlock) void k_schur_pose(const uint32_t* __restrict__ row_off, int n_slices, int n_vertices, int xcd8,
+                                                       const CgState<T>* __restrict__ st, const T* __restrict__ zc,
+                                                       const float* __restrict__ zc32, const uint32_t* __restrict__ od_row_off,
+                                                       Table<T> tb, Table<T> od, const T* __restrict__ t, const T* __restrict__ dp,
                                                        int pose_first, int pose_last, T* __restrict__ out,
-                                                       T* __restrict__ dot_part, const CgState<T>* __restrict__ st,
-                                                       const T* __restrict__ rvec, T* __restrict__ rz_part,
-                                                       const float* __restrict__ zc32 = nullptr, const float* __restrict__ t32 = nullptr,
+                                                       T* __restrict__ dot_part, const T* __restrict__ rvec, T* __restrict__ rz_part,
+                                                       const float* __restrict__ t32 = nullptr,
                                                        const T* __restrict__ post_minv = nullptr, const T* __restrict__ post_r = nullptr,
                                                        const T* __restrict__ post_omega = nullptr, T* __restrict__ zc_post = nullptr) {
     __shared__ T red[kWavesPerBlock];
@@ -578,16 +609,18 @@ __global__ __launch_bounds__(kBlock) void k_schur_pose(Table<T> tb, Table<T> od,
     // its operands from the f32 copies (zc32), so writing the f64 records it does not read is no race; the f32 copies are rewritten by
     // k_cg_step before anything reads them again.
     const int done = st->done;      // requested now, tested after the first argument-only loads are in flight (see k_schur_lm)
-    const Walk wk = walk_of<G>(tb);
+    const Walk wk = walk_of<G>(n_slices, xcd8);
     const int slice = wk.slice, lane = wk.lane, i = wk.vertex, live = wk.live;
     T dot = 0, rz = 0;
     if (!live && done) return;      // workgroup-uniform: done is, and the other waves of the group leave below
     if (live) {
-        const bool valid = i < tb.n_vertices;
-        const int ic = valid ? i : tb.n_vertices - 1;
+        const bool valid = i < n_vertices;
+        const int ic = valid ? i : n_vertices - 1;
         const PoseVec<T> zi = pose_vec<T, LOW>(zc, zc32, ic);
         T v0 = zi.v0, v1 = zi.v1, v2 = zi.v2, c = zi.c, s = zi.s;
-        const uint32_t lm_r0 = tb.row_off[slice], lm_r1 = tb.row_off[slice + 1];
+        uint32_t lm_r0 = row_off[slice];
+        const uint32_t lm_r1 = row_off[slice + 1];
+        issue_before_exit(lm_r0);      // (the row bounds too, as in k_schur_lm)
         issue_before_exit(v0);
         if (done) return;
         // the pose's own diagonal block and residual entry are used at the very end: asked for first
@@ -627,7 +660,7 @@ __global__ __launch_bounds__(kBlock) void k_schur_pose(Table<T> tb, Table<T> od,
         T o0 = 0, o1 = 0, o2 = 0;
         {
             const size_t S = od.slots;
-            const uint32_t r0 = od.row_off[slice], r1 = od.row_off[slice + 1];
+            const uint32_t r0 = od_row_off[slice], r1 = od_row_off[slice + 1];
             for (uint32_t row = r0; row < r1; ++row) {
                 const size_t k = (size_t)row * 64 + lane;
                 const uint32_t raw = od.idx[k];
@@ -677,10 +710,9 @@ __global__ __launch_bounds__(kBlock) void k_schur_pose(Table<T> tb, Table<T> od,
 // order, then:  beta = gamma/gamma_old, alpha = gamma/(delta - beta*gamma/alpha_old),
 //   p = z + beta p,  q = S z + beta q,  x += alpha p,  r -= alpha q,  z = M^-1 r.
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_cg_update(int P, const T* __restrict__ sz, const T* __restrict__ dot_part,
-                                                      int n_dot, const T* __restrict__ gpart_in, int n_g,
-                                                      T* __restrict__ gpart_out, const CgState<T>* __restrict__ st_in,
-                                                      CgState<T>* __restrict__ st_out, const T* __restrict__ minv,
+__global__ __launch_bounds__(kBlock) void k_cg_update(int P, int n_dot, const CgState<T>* __restrict__ st_in, const T* __restrict__ dot_part,
+                                                      const T* __restrict__ gpart_in, int n_g, const T* __restrict__ sz,
+                                                      T* __restrict__ gpart_out, CgState<T>* __restrict__ st_out, const T* __restrict__ minv,
                                                       T* __restrict__ r, T* __restrict__ p, T* __restrict__ q,
                                                       T* __restrict__ x, T* __restrict__ zc, T tol2, int max_iters,
                                                       const T* __restrict__ gamma0_scale) {
@@ -750,14 +782,16 @@ template <typename T> struct WarmTerms {
 // x -> zc[.][0..2] (the landmark pass reads its vector from zc).  w.n_max = 0: plain copy of x into zc.  Otherwise x = the
 // prediction of the order with the smallest tested error (order 1 when nothing has been tested yet) first.
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_pack_x(int P, T* __restrict__ x, T* __restrict__ zc, const WarmTerms<T> w, int* __restrict__ order_out) {
+__global__ __launch_bounds__(kBlock) void k_pack_x(int P, int n_max, int n_tested, int nb_err, const T* __restrict__ errpart, T* __restrict__ x,
+                                                   T* __restrict__ zc, int* __restrict__ order_out, const WarmTerms<T> w) {
+    // (n_max, n_tested, nb_err, errpart: w's, in the plain head; read from there alone)
     __shared__ T red[kWavesPerBlock];
     const int i = blockIdx.x * kBlock + threadIdx.x;
-    int m = w.n_max > 0 ? 1 : 0;
-    if (w.n_max > 0 && w.n_tested > 0) {          // every workgroup sums the same partials in the same order: one choice
-        T best = block_sum_array<T>(w.errpart, w.nb_err, red);
-        for (int j = 1; j < w.n_tested && j < w.n_max; ++j) {
-            const T e = block_sum_array<T>(w.errpart + (size_t)j * w.nb_err, w.nb_err, red);
+    int m = n_max > 0 ? 1 : 0;
+    if (n_max > 0 && n_tested > 0) {          // every workgroup sums the same partials in the same order: one choice
+        T best = block_sum_array<T>(errpart, nb_err, red);
+        for (int j = 1; j < n_tested && j < n_max; ++j) {
+            const T e = block_sum_array<T>(errpart + (size_t)j * nb_err, nb_err, red);
             if (e * kWarmMargin < best) { best = e; m = j + 1; }
         }
     }
@@ -778,7 +812,7 @@ __global__ __launch_bounds__(kBlock) void k_pack_x(int P, T* __restrict__ x, T* 
 // The solved delta x -> zc[.][0..2] and -> xsave (the newest entry of the warm start's history), and what every order would
 // have made of predicting it from the deltas before it (w.v, newest first; orders 1..w.n_max): errpart[m-1][block].
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_save_x(int P, const T* __restrict__ x, T* __restrict__ zc, T* __restrict__ xsave, const WarmTerms<T> w, T* __restrict__ errpart) {
+__global__ __launch_bounds__(kBlock) void k_save_x(int P, int n_max, const T* __restrict__ x, T* __restrict__ zc, T* __restrict__ xsave, T* __restrict__ errpart, const WarmTerms<T> w) {      // (n_max: w's, in the plain head; read from there alone)
     __shared__ T red[kWavesPerBlock];
     const int i = blockIdx.x * kBlock + threadIdx.x;
     T err[kMaxWarm];
@@ -792,10 +826,10 @@ __global__ __launch_bounds__(kBlock) void k_save_x(int P, const T* __restrict__ 
             xsave[(size_t)i * 3 + k] = v;
             T u[kMaxWarm];
 #pragma unroll
-            for (int j = 0; j < kMaxWarm; ++j) u[j] = j < w.n_max ? w.v[j][(size_t)i * 3 + k] : T(0);
+            for (int j = 0; j < kMaxWarm; ++j) u[j] = j < n_max ? w.v[j][(size_t)i * 3 + k] : T(0);
 #pragma unroll
             for (int m = 0; m < kMaxWarm; ++m) {
-                if (m < w.n_max) {
+                if (m < n_max) {
                     T p = 0;
 #pragma unroll
                     for (int j = 0; j <= m; ++j) p += w.c[m][j] * u[j];
@@ -804,7 +838,7 @@ __global__ __launch_bounds__(kBlock) void k_save_x(int P, const T* __restrict__ 
             }
         }
     }
-    for (int m = 0; m < w.n_max; ++m) {
+    for (int m = 0; m < n_max; ++m) {
         const T total = block_sum<T>(err[m], red);
         if (threadIdx.x == 0) errpart[(size_t)m * gridDim.x + blockIdx.x] = total;
     }

@@ -14,7 +14,7 @@ namespace tsgo {
 template <typename T, int G, int RK = 0>
 __global__ __launch_bounds__(kBlock) void k_chi2_lm_prior(Table<T> tb, const T* __restrict__ lmrec, const PriorArgs<T> pa, const RobustArgs<T> ra) {
     __shared__ T red[kWavesPerBlock];
-    const Walk wk = walk_of<G>(tb);
+    const Walk wk = walk_of<G>(tb.n_slices, table_xcd8(tb));
     const int l = wk.vertex;
     T chi = 0;
     if (wk.live && l < tb.n_vertices && wk.head) {
@@ -42,7 +42,7 @@ template <typename T, int G, int OJ = 0, int PRI = 0, int RK = 0>
 __global__ __launch_bounds__(kBlock) void k_chi2(Table<T> tb, Table<T> od, const T* __restrict__ ps, const T* __restrict__ lmrec,
                                                  T* __restrict__ chi_part, const PriorArgs<T> pa, const RobustArgs<T> ra) {
     __shared__ T red[kWavesPerBlock];
-    const Walk wk = walk_of<G>(tb);
+    const Walk wk = walk_of<G>(tb.n_slices, table_xcd8(tb));
     const int slice = wk.slice, lane = wk.lane, i = wk.vertex;
     const bool valid = wk.live && i < tb.n_vertices;
     const auto rk_lm = robust_class<RK>(ra, kClassLm), rk_odom = robust_class<RK>(ra, kClassOdom);

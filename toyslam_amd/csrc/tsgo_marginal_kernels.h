@@ -49,7 +49,7 @@ template <typename T, int G, int NV>
 __global__ __launch_bounds__(kBlock) void k_mb_schur_lm(Table<T> tb, const T* __restrict__ v, const T* __restrict__ ps, const T* __restrict__ ninv,
                                                         T* __restrict__ t, const int* __restrict__ stop) {
     if (*stop) return;
-    const Walk wk = walk_of<G>(tb);
+    const Walk wk = walk_of<G>(tb.n_slices, table_xcd8(tb));
     if (!wk.live) return;
     const int slice = wk.slice, lane = wk.lane, l = wk.vertex;
     T acc[NV][2];
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kBlock) void k_mb_schur_pose(Table<T> tb, Table<T> 
                                                           const T* __restrict__ rvec, T* __restrict__ dot_part, const int* __restrict__ stop) {
     __shared__ T red[kWavesPerBlock * NV];
     if (*stop) return;      // workgroup-uniform
-    const Walk wk = walk_of<G>(tb);
+    const Walk wk = walk_of<G>(tb.n_slices, table_xcd8(tb));
     const int slice = wk.slice, lane = wk.lane, i = wk.vertex;
     T o[NV][3];
 #pragma unroll

@@ -58,7 +58,7 @@ template <typename T, int G, int RK = 0>
 __global__ __launch_bounds__(kBlock) void k_edge_report_lm_prior(Table<T> tb, const T* __restrict__ lmrec, const uint32_t* __restrict__ pri_edge,
                                                                  T* __restrict__ rec, ReportPartial<T>* __restrict__ out, const PriorArgs<T> pa, const RobustArgs<T> ra) {
     __shared__ ReportPartial<T> red[kWavesPerBlock];
-    const Walk wk = walk_of<G>(tb);
+    const Walk wk = walk_of<G>(tb.n_slices, table_xcd8(tb));
     const int l = wk.vertex;
     ReportAcc<T> acc;
     if (wk.live && l < tb.n_vertices && wk.head) {
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(kBlock) void k_edge_report(Table<T> tb, Table<T> od
                                                         const uint32_t* __restrict__ pp_edge, T* __restrict__ rec, ReportPartial<T>* __restrict__ out,
                                                         const PriorArgs<T> pa, const RobustArgs<T> ra) {
     __shared__ ReportPartial<T> red[kWavesPerBlock][kEdgeClasses];
-    const Walk wk = walk_of<G>(tb);
+    const Walk wk = walk_of<G>(tb.n_slices, table_xcd8(tb));
     const int slice = wk.slice, lane = wk.lane, i = wk.vertex;
     const bool valid = wk.live && i < tb.n_vertices;
     const auto rk_lm = robust_class<RK>(ra, kClassLm), rk_odom = robust_class<RK>(ra, kClassOdom);
