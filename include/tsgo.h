@@ -382,6 +382,42 @@ typedef struct tsgo_gate_stats {
 int tsgo_gate_edges(tsgo_optimizer* opt, int32_t n, const uint32_t* e_type, const uint32_t* e_ids, const double* e_meas, const double* e_inf, double rel_tol,
                     double* rec_out, double* innov_out /* 9 per candidate, may be NULL */, tsgo_gate_stats* stats /* may be NULL */);
 
+/* Initial estimates from an odometry spanning tree (what g2o's computeInitialGuess and GTSAM's initializers offer):
+ * the estimates that ODOMETRY ALONE implies, before the first tsgo_optimize, or as what tsgo_gate_edges and tsgo_edge_report judge closures
+ * against.  Every other loop of the engine is a local method and needs a start near the optimum.
+ *   The tree depends on the graph's structure and the mask only, never on information values.  An edge is usable when e_type == 0, id1 != id2
+ *   and (odom_mask == NULL or odom_mask[e] != 0); the mask has one byte per edge of the graph (n_mask must equal n_edges; entries of non-ODOM
+ *   edges are ignored); edge types 1-4 never enter the tree.  Breadth-first search from the fixed pose vertices (in order of first occurrence
+ *   in the fixed list, depth 0, all in the FIFO queue at the start); a popped vertex scans its usable incident edges in increasing input edge
+ *   index and an unvisited other endpoint becomes its child through that edge.  When the queue runs empty and poses remain unvisited, the
+ *   unvisited pose with the lowest input vertex index becomes a root (it keeps its estimate: roots_free) and the search goes on.  Roots
+ *   and fixed vertices are never written.
+ *   TSGO_INIT_POSES: along a tree edge with measurement M (row-major 3x3), theta = atan2(M10, M00), t = (M02, M12); a child that is the edge's
+ *   id2 gets T_child = T_parent o (t, theta), a child that is id1 gets T_parent o (t, theta)^-1: for a rigid M the edge's ODOM residual is
+ *   zero afterwards.  The handle keeps M^-1, not M: (t, theta) is taken from M^-1 inverted back in f64 with its last row taken as (0, 0, 1),
+ *   so a measurement that is not a rigid transform gets what that gives.  On the device: one record per pose, ceil(log2(depth_max + 1))
+ *   pointer-jumping passes (no atomics, no host round trip), then the write exactly as a pose update writes (cos, sin of atan2(s, c)).
+ *   TSGO_INIT_LANDMARKS (after the poses when both are asked for, from the current poses otherwise): every non-fixed landmark with at least one
+ *   LM edge whose two information entries are both > 0 becomes the plain mean of t_pose + R_pose (r cos phi, r sin phi) over those edges;
+ *   every other landmark stays bit for bit.
+ * The call changes estimates: it leaves the solver as a tsgo_set_graph that only refills values does (no multigrid hierarchy is valid, and
+ * the warm start's history is dropped even under warm_requests: a jump does not continue it); what belongs to the handle (tsgo_set_robust)
+ * stays.  The same call twice gives the same bits, and the second changes none (the roots did not move).
+ * Errors (< 0, text in tsgo_last_error; everything is validated before anything is launched, the handle stays usable): a NULL handle, no
+ * graph set, `what` outside 0..3, n_mask != n_edges with a mask given, precision = 32, an edge-sharded handle (world > 1). */
+typedef struct tsgo_init_stats {
+    int64_t poses_set, landmarks_set;       /* estimates overwritten */
+    int64_t roots_fixed, roots_free;        /* trees rooted at a fixed pose / at a free pose that kept its estimate */
+    int64_t edges_usable, tree_edges;       /* ODOM edges the tree could use / did use (= poses_set when poses are set) */
+    int64_t landmarks_unobserved;           /* non-fixed landmarks without a usable LM edge: left as they were */
+    int32_t depth_max, rounds;              /* deepest tree node; composition passes run on the device (0 when poses are not set) */
+    double ms_total, ms_tree, ms_device;    /* whole call; host tree build; hipEvent time of the kernels */
+} tsgo_init_stats;
+#define TSGO_INIT_POSES 1
+#define TSGO_INIT_LANDMARKS 2
+int tsgo_init_estimates(tsgo_optimizer* opt, int32_t what /* 0 = both */, const uint8_t* odom_mask /* may be NULL */,
+                        int64_t n_mask, tsgo_init_stats* stats /* may be NULL */);
+
 const char* tsgo_last_error(void);
 
 /* ---- host-only: wire codec (libtsgo_host.so and libtsgo_hip.so) ---------------------------------
@@ -448,6 +484,13 @@ int tsgo_amg_probe(const tsgo_graph* g, tsgo_amg_info* out);
  * are per shard): out->schur_contribs = landmark-pair terms THIS shard sums, *odom_contribs_out = its odometry terms.
  * Over all ranks both add up to the unsharded counts. */
 int tsgo_amg_probe_shard(const tsgo_graph* g, int32_t rank, int32_t world, tsgo_amg_info* out, int64_t* odom_contribs_out);
+
+/* ---- host-only: the spanning tree of tsgo_init_estimates alone ------------------------------------------
+ * Per vertex in tsgo_graph order: the parent's position in the vertex arrays, the input edge that joins them (-1 for roots and for
+ * landmarks) and the depth (0 for roots, -1 for landmarks); any output may be NULL.  stats receives roots_fixed, roots_free, edges_usable,
+ * tree_edges, depth_max and rounds = ceil(log2(depth_max + 1)); its other fields are 0.  Reads v_id, v_type, e_type, e_ids and fixed only. */
+int tsgo_init_tree(const tsgo_graph* g, const uint8_t* odom_mask, int64_t n_mask,
+                   int32_t* parent_out, int32_t* edge_out, int32_t* depth_out, tsgo_init_stats* stats);
 
 #ifdef __cplusplus
 }

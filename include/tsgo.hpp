@@ -209,6 +209,26 @@ public:
         return rec;
     }
 
+    // Initial estimates from an odometry spanning tree (tsgo_init_estimates), for the graph last handed to Optimize or SetGraph: poses
+    // composed along the tree from the fixed poses, landmarks as the mean of their observations.  what: TSGO_INIT_POSES | TSGO_INIT_LANDMARKS
+    // (0 = both); odom_mask: empty = every ODOM edge may enter the tree, otherwise one byte per edge of the graph.  The graph's positions are
+    // updated in place when `graph` is given.  Throws on an error (no graph yet, a mask of the wrong length, precision 32).
+    tsgo_init_stats InitEstimates(Graph* graph = nullptr, int what = 0, const std::vector<uint8_t>& odom_mask = std::vector<uint8_t>()) {
+        tsgo_init_stats s;
+        if (tsgo_init_estimates(handle, what, odom_mask.empty() ? nullptr : odom_mask.data(), (int64_t)odom_mask.size(), &s)) throw std::runtime_error(tsgo_last_error());
+        if (graph) {
+            std::vector<double> out(graph->VertexCount() * 3);
+            if (tsgo_get_vertices(handle, out.data())) throw std::runtime_error(tsgo_last_error());
+            graph->SetPositions(out);
+        }
+        return s;
+    }
+    // Hands the graph to the handle without optimising it (what InitEstimates, EdgeReport or GateEdges need before a first Optimize).
+    void SetGraph(const Graph& graph) {
+        const tsgo_graph g = graph.View();
+        if (tsgo_set_graph(handle, &g)) throw std::runtime_error(tsgo_last_error());
+    }
+
 private:
     unsigned iterations;
     tsgo_optimizer* handle = nullptr;

@@ -226,11 +226,20 @@
         return 0;
     }
     int refill_values(const tsgo_graph& g) {
-        // the cycle goes back to the configured storage below (reset_solver_state): a replay captured with the other format's kernels goes with it
-        if (mem.cy16 != fresh_memory().cy16 && cg_graph) { (void)hipGraphExecDestroy(cg_graph); cg_graph = nullptr; }
         if (int rc = stage_values(g, true)) return rc;
         if (int rc = stage_priors(g)) return rc;
         keep_prior_weights(g);
+        const SolverMemory old = mem;      // same structure, same numbering: under warm_requests the history stays where it is
+        if (int rc = restart_on_new_estimates()) return rc;
+        if (cfg.warm_requests && old.have_prev && old.n_prev > 0) { mem.have_prev = true; mem.n_prev = old.n_prev; mem.n_tested = old.n_tested; mem.carried = true; ++n_carried; mem.n_lins = kYoungLins; }      // a continued graph is not a young one
+        HIP_OK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    // New estimates on the tables the handle holds (a refill; tsgo_init_estimates): pr.pose_xyt is current, the device state written or on its
+    // way.  The multigrid lever arms follow the estimates and the solver starts from nothing.
+    int restart_on_new_estimates() {
+        // the cycle goes back to the configured storage below (reset_solver_state): a replay captured with the other format's kernels goes with it
+        if (mem.cy16 != fresh_memory().cy16 && cg_graph) { (void)hipGraphExecDestroy(cg_graph); cg_graph = nullptr; }
         if (amg_on) {           // the rigid-mode lever arms follow the new estimates (host/amg.h: refresh_amg_geometry)
             refresh_amg_geometry(pr.pose_xyt, amg);
             HIP_OK(hipStreamSynchronize(stream));
@@ -241,11 +250,7 @@
                 if (!rel.empty()) { if (int rc_ = copy_sync(lv[l].rel, stage, rel.size() * sizeof(T), hipMemcpyHostToDevice)) return rc_; }
             }
         }
-        const SolverMemory old = mem;      // same structure, same numbering: under warm_requests the history stays where it is
-        if (int rc = reset_solver_state()) return rc;
-        if (cfg.warm_requests && old.have_prev && old.n_prev > 0) { mem.have_prev = true; mem.n_prev = old.n_prev; mem.n_tested = old.n_tested; mem.carried = true; ++n_carried; mem.n_lins = kYoungLins; }      // a continued graph is not a young one
-        HIP_OK(hipStreamSynchronize(stream));
-        return 0;
+        return reset_solver_state();
     }
 
     int set_graph(const tsgo_graph& g) override {

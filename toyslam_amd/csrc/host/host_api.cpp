@@ -3,6 +3,7 @@
 #include "errors.h"
 #include "problem.h"
 #include "amg.h"
+#include "init_tree.h"
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -74,4 +75,22 @@ extern "C" int tsgo_amg_probe(const tsgo_graph* g, tsgo_amg_info* out) {
 extern "C" int tsgo_amg_probe_shard(const tsgo_graph* g, int32_t rank, int32_t world, tsgo_amg_info* out, int64_t* odom_contribs_out) {
     if (!g || !out || world < 1 || rank < 0 || rank >= world) return tsgo::set_error(-1, "tsgo_amg_probe_shard: bad argument");
     return amg_probe(g, rank, world, out, odom_contribs_out);
+}
+
+extern "C" int tsgo_init_tree(const tsgo_graph* g, const uint8_t* odom_mask, int64_t n_mask, int32_t* parent_out, int32_t* edge_out, int32_t* depth_out,
+                              tsgo_init_stats* stats) {
+    if (!g) return tsgo::set_error(-1, "tsgo_init_tree: null argument");
+    tsgo::InitTree t;
+    const std::string err = tsgo::build_init_tree(*g, odom_mask, n_mask, t);
+    if (!err.empty()) return tsgo::set_error(-2, "tsgo_init_tree: " + err);
+    const size_t n = (size_t)g->n_vertices;
+    if (parent_out && n) std::memcpy(parent_out, t.parent.data(), n * sizeof(int32_t));
+    if (edge_out && n) std::memcpy(edge_out, t.edge.data(), n * sizeof(int32_t));
+    if (depth_out && n) std::memcpy(depth_out, t.depth.data(), n * sizeof(int32_t));
+    if (stats) {      // the tree's own counts; what only a device call knows stays 0
+        std::memset(stats, 0, sizeof(*stats));
+        stats->roots_fixed = t.roots_fixed; stats->roots_free = t.roots_free; stats->edges_usable = t.edges_usable; stats->tree_edges = t.tree_edges;
+        stats->depth_max = t.depth_max; stats->rounds = t.rounds();
+    }
+    return 0;
 }

@@ -1,6 +1,6 @@
 // tsgo_hip.hip — device side of the C ABI in include/tsgo.h: buffers, launches, the Gauss-Newton
 // loop with the reference's stop rules (remote/optimizer/OptimizerCpu.h:80-180), hipGraph replay of
-// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h.
+// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_init_kernels.h.
 //
 // One translation unit; the engine class is laid out over this file and engine/*.inc (each included inside the class body):
 //   this file                      members (what the solver learns grouped by lifetime: SolverMemory), configuration / environment (host/knobs.h), device slabs and upload helpers; the C ABI at the end
@@ -13,6 +13,7 @@
 //   engine/engine_marginals.inc    tsgo_marginals, tsgo_joint_marginals: batched PCG for blocks of H^-1
 //   engine/engine_report.inc       tsgo_edge_report: per-edge residual records and the per-class summary
 //   engine/engine_gate.inc         tsgo_gate_edges: candidate edges against the joint marginal of their vertices (Mahalanobis gate)
+//   engine/engine_init.inc         tsgo_init_estimates: estimates from an odometry spanning tree (pointer jumping), landmarks from their observations
 //   engine/engine_testing.inc      tsgo_testing_apply (TSGO_TESTING builds only): the operators PCG applies, read out column by column
 //
 // There is NO CPU fallback in this file: every entry point that computes needs a gfx950 device and
@@ -42,11 +43,13 @@
 #endif
 #include "host/amg.h"
 #include "host/errors.h"
+#include "host/init_tree.h"
 #include "host/knobs.h"
 #include "host/parallel.h"
 #include "host/problem.h"
 #include "tsgo_amg_kernels.h"
 #include "tsgo_gate_kernels.h"
+#include "tsgo_init_kernels.h"
 #include "tsgo_kernels.h"
 #include "tsgo_lm_kernels.h"
 #include "tsgo_marginal_kernels.h"
@@ -153,6 +156,7 @@ struct IEngine {
     virtual int edge_report(double* rec_out, int64_t cap_edges, tsgo_edge_report_stats* st) = 0;
     virtual int gate_edges(int n, const uint32_t* e_type, const uint32_t* e_ids, const double* e_meas, const double* e_inf, double rel_tol, double* rec_out,
                            double* innov_out, tsgo_gate_stats* st) = 0;
+    virtual int init_estimates(int what, const uint8_t* mask, int64_t n_mask, tsgo_init_stats* st) = 0;
 #ifdef TSGO_TESTING
     virtual int testing_apply(int which, const double* in, double* out, int n_cols) = 0;
 #endif
@@ -455,6 +459,7 @@ template <typename T> struct Engine : IEngine {
 #include "engine/engine_marginals.inc"
 #include "engine/engine_gate.inc"
 #include "engine/engine_report.inc"
+#include "engine/engine_init.inc"
 #ifdef TSGO_TESTING
 #include "engine/engine_testing.inc"
 #endif
@@ -572,6 +577,10 @@ int tsgo_gate_edges(tsgo_optimizer* o, int32_t n, const uint32_t* e_type, const 
                     double* rec_out, double* innov_out, tsgo_gate_stats* stats) {
     if (!o) return tsgo::set_error(-1, "tsgo_gate_edges: null handle");
     return o->eng->gate_edges(n, e_type, e_ids, e_meas, e_inf, rel_tol, rec_out, innov_out, stats);
+}
+int tsgo_init_estimates(tsgo_optimizer* o, int32_t what, const uint8_t* odom_mask, int64_t n_mask, tsgo_init_stats* stats) {
+    if (!o) return tsgo::set_error(-1, "tsgo_init_estimates: null handle");
+    return o->eng->init_estimates(what, odom_mask, n_mask, stats);
 }
 void tsgo_reset_history(tsgo_optimizer* o) {
     if (o && o->eng) o->eng->reset_history();

@@ -218,6 +218,20 @@ class HipOptimizer:
         stats["solve"] = {f: getattr(st.solve, f) for f, _t in st.solve._fields_}
         return res, stats
 
+    def init_estimates(self, mask=None, poses=True, landmarks=True):
+        """Initial estimates from an odometry spanning tree (tsgo_init_estimates): poses composed along the tree from its roots (the
+        fixed poses; a component without one keeps its lowest-index pose), then landmarks as the mean of their observations.  mask: one
+        entry per edge of the graph, nonzero = this ODOM edge may enter the tree (entries of other edges are ignored); None = every ODOM
+        edge.  Returns tsgo_init_stats as a dict.  The estimates change; the solver restarts as after a set_graph that refills values."""
+        what = (_lib.INIT_POSES if poses else 0) | (_lib.INIT_LANDMARKS if landmarks else 0)
+        if what == 0:
+            raise ValueError("init_estimates: poses and landmarks are both False")
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        st = _lib.tsgo_init_stats()
+        _lib.check(self.lib, self.lib.tsgo_init_estimates(self.h, what, None if m is None else m.ctypes.data, 0 if m is None else len(m), C.byref(st)),
+                   "tsgo_init_estimates")
+        return {f: getattr(st, f) for f, _t in st._fields_}
+
     def time_kernel(self, which, reps=50):
         us = C.c_double(); nbytes = C.c_double()
         _lib.check(self.lib, self.lib.tsgo_time_kernel(self.h, which, reps, C.byref(us), C.byref(nbytes)),
