@@ -418,6 +418,39 @@ typedef struct tsgo_init_stats {
 int tsgo_init_estimates(tsgo_optimizer* opt, int32_t what /* 0 = both */, const uint8_t* odom_mask /* may be NULL */,
                         int64_t n_mask, tsgo_init_stats* stats /* may be NULL */);
 
+/* Edit edge weights in place on the device (g2o's edge `level`; what a caller-side IRLS, GNC or switchable-constraints loop needs per
+ * round): replace the information diagonal of n edges of the graph the handle holds.
+ *   edge_idx   positions in the edge arrays of the tsgo_graph the handle was given (the numbering of tsgo_edge_report), or NULL for "all
+ *              edges in order" (then n must equal n_edges)
+ *   e_inf      3 doubles per LISTED edge, in list order, the encoding of tsgo_graph.e_inf; the entry an edge's type does not use (the third
+ *              of LM, virtual landmark and landmark prior edges) is ignored
+ * After the call every table of the handle holds, bit for bit, what a same-structure tsgo_set_graph whose graph differs from the held one
+ * only in those e_inf rows would hold: the stored value is (T)value in the handle's precision (64 and 32).  Nothing else on the device is
+ * written: the estimates keep their bits, which a tsgo_set_graph (it takes them from the host, through cos / sin) cannot offer.  A zero
+ * information is legal: the edge then contributes exactly nothing to H, b and chi^2, and tsgo_edge_report gives it s = 0, rho = 0, w = 1.
+ * If the edits leave a vertex with no information at all, or the graph disconnected, the result is what tsgo_set_graph would make of that
+ * graph: the caller's responsibility there and here.
+ *   Solver state: the rule of tsgo_set_robust.  A call with n > 0 makes the next linearisation build a fresh multigrid hierarchy; the warm
+ *   start's history and everything else the solver learnt stay, and so does the robust setting.  n == 0 returns 0 and changes nothing.
+ *   Lifetime: the edit belongs to the values, not to the handle: the next tsgo_set_graph, refill or rebuild, replaces every weight with
+ *   what it carries.
+ * tsgo_get_edge_information: what the handle holds now, 3 doubles per edge in input order, widened from the handle's precision; an entry
+ * the edge's type does not use comes back as 0.
+ * Errors (< 0, text in tsgo_last_error; everything is validated before anything is uploaded or launched, the handle is exactly as before):
+ * a NULL handle; no graph set; n < 0; e_inf == NULL with n > 0; edge_idx == NULL with n != n_edges (n > 0); an index outside [0, n_edges);
+ * an index listed twice; an entry on an axis the edge's type uses that is not finite or is negative; an edge-sharded handle (world > 1),
+ * for either call; cap_edges < n_edges or e_inf_out == NULL with edges to return (get). */
+typedef struct tsgo_edge_info_stats {
+    int64_t edges_listed;        /* n */
+    int64_t edges_by_class[5];   /* of them, per tsgo_graph.e_type */
+    int32_t maps_built;          /* 1 when this call built and uploaded the edge -> slot map of the structure, 0 when it was there */
+    int32_t reserved;            /* 0 */
+    double ms_total, ms_host, ms_device;   /* whole call; validation + map + staging; hipEvent time of the kernel */
+} tsgo_edge_info_stats;
+int tsgo_set_edge_information(tsgo_optimizer* opt, int64_t n, const int64_t* edge_idx /* may be NULL */, const double* e_inf,
+                              tsgo_edge_info_stats* stats /* may be NULL */);
+int tsgo_get_edge_information(tsgo_optimizer* opt, double* e_inf_out, int64_t cap_edges);
+
 const char* tsgo_last_error(void);
 
 /* ---- host-only: wire codec (libtsgo_host.so and libtsgo_hip.so) ---------------------------------

@@ -223,6 +223,25 @@ public:
         }
         return s;
     }
+    // Edit edge weights in place (tsgo_set_edge_information): `edges` are positions in the edge order of the graph last handed to Optimize or
+    // SetGraph (the numbering of EdgeReport), `inf` three doubles per listed edge; an empty `edges` with 3 * EdgeCount values is "every edge
+    // in order".  Zeros switch an edge off.  The estimates and the robust setting stay; the next Optimize(graph) or SetGraph replaces every
+    // weight with what the graph carries.  EdgeInformation: what the handle holds now, three doubles per edge.  Both throw on an error (no
+    // graph yet, an index out of range or listed twice, a negative or non-finite value, an edge-sharded handle).
+    void SetEdgeInformation(const std::vector<int64_t>& edges, const std::vector<double>& inf, tsgo_edge_info_stats* stats = nullptr) {
+        if (!edges.empty() && inf.size() != edges.size() * 3) throw std::runtime_error("SetEdgeInformation: three values per listed edge");
+        if (tsgo_set_edge_information(handle, (int64_t)(inf.size() / 3), edges.empty() ? nullptr : edges.data(), inf.empty() ? nullptr : inf.data(), stats))
+            throw std::runtime_error(tsgo_last_error());
+    }
+    std::vector<double> EdgeInformation() {
+        tsgo_edge_report_stats s;
+        if (tsgo_edge_report(handle, nullptr, 0, &s)) throw std::runtime_error(tsgo_last_error());
+        int64_t n = 0;
+        for (const tsgo_edge_class_summary& c : s.cls) n += c.edges;
+        std::vector<double> inf((size_t)n * 3);
+        if (tsgo_get_edge_information(handle, inf.empty() ? nullptr : inf.data(), n)) throw std::runtime_error(tsgo_last_error());
+        return inf;
+    }
     // Hands the graph to the handle without optimising it (what InitEstimates, EdgeReport or GateEdges need before a first Optimize).
     void SetGraph(const Graph& graph) {
         const tsgo_graph g = graph.View();

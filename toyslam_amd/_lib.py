@@ -59,6 +59,11 @@ class tsgo_init_stats(C.Structure):
 INIT_POSES, INIT_LANDMARKS = 1, 2      # TSGO_INIT_*
 
 
+class tsgo_edge_info_stats(C.Structure):
+    _fields_ = [("edges_listed", C.c_int64), ("edges_by_class", C.c_int64 * 5), ("maps_built", C.c_int32), ("reserved", C.c_int32),
+                ("ms_total", C.c_double), ("ms_host", C.c_double), ("ms_device", C.c_double)]
+
+
 ROBUST_KERNELS = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}      # TSGO_ROBUST_*
 ROBUST_CLASSES = ("odom", "lm", "virtual", "pose_prior", "lm_prior")            # = tsgo_graph.e_type 0 .. 4
 
@@ -96,7 +101,8 @@ HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_last_error",
                 "tsgo_synth_truth", "tsgo_synth_free", "tsgo_layout_probe", "tsgo_amg_probe", "tsgo_amg_probe_shard", "tsgo_init_tree"]
 DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_graph", "tsgo_reset_history", "tsgo_optimize", "tsgo_get_vertices",
                   "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
-                  "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust", "tsgo_edge_report", "tsgo_gate_edges", "tsgo_init_estimates"]
+                  "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust", "tsgo_edge_report", "tsgo_gate_edges", "tsgo_init_estimates",
+                  "tsgo_set_edge_information", "tsgo_get_edge_information"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
 
@@ -149,6 +155,8 @@ def _declare_device(L):
     L.tsgo_edge_report.argtypes = [vp, vp, C.c_int64, C.POINTER(tsgo_edge_report_stats)]
     L.tsgo_gate_edges.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_double, vp, vp, C.POINTER(tsgo_gate_stats)]
     L.tsgo_init_estimates.argtypes = [vp, C.c_int32, vp, C.c_int64, C.POINTER(tsgo_init_stats)]
+    L.tsgo_set_edge_information.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(tsgo_edge_info_stats)]
+    L.tsgo_get_edge_information.argtypes = [vp, vp, C.c_int64]
 
 
 def _declare_testing(L):

@@ -262,6 +262,7 @@
         if (int rc = carry_out()) return rc;
         release();
         drop_report_maps();      // the slot -> input-edge maps of tsgo_edge_report lived in the slabs just released and described the old tables
+        drop_edit_maps();        // ... and so did the edge -> slot map of tsgo_set_edge_information
         BuildOptions bo; bo.rank = cfg.rank; bo.world = cfg.world; bo.lanes_per_pose = cfg.lanes_per_pose; bo.lanes_per_lm = cfg.lanes_per_lm;
         bo.fill_planes = false;
         const std::string err = build_problem(g, bo, pr);

@@ -1,0 +1,82 @@
+// tsgo_edit_kernels.h — tsgo_set_edge_information / tsgo_get_edge_information on the device (engine/engine_edit.inc):
+// the information diagonal of listed edges written into, or read back from, every place the handle keeps it.
+//
+// A weight on the device is a plain copy of tsgo_graph.e_inf in the handle's scalar type (engine_graph.inc: stage_values, stage_priors),
+// so an edit is a scatter of (T)value and nothing else.  Where an input edge lives is the edge -> slot map: two 32-bit words per edge,
+//   LM                        its slot in by_pose, its slot in by_lm          (the (w0, w1) pair of the pair-plane-major static planes)
+//   ODOM, virtual landmark    its slot at id1, its slot at id2 (kDirBit)      (planes OD_W0 .. of the pose-pose table; two distinct slots of one pose for a self-loop)
+//   pose / landmark prior     its record, kNoEdge                             (PRI_W0 .. / PRL_W0 .. of the record)
+// and the edge's class as one byte per edge (tsgo_graph.e_type).  The host builds and checks the map once per structure: every edge has
+// exactly these locations, every location is inside its table, and no location belongs to two edges.  With the host's duplicate check
+// on the list every address below has ONE writer: plain stores, no atomics, no read-modify-write.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "tsgo_kernels.h"
+
+namespace tsgo {
+
+template <typename T> struct EditTables {      // the writable static planes of the three tables and the prior records (null without priors)
+    T* st_p; size_t slots_p;
+    T* st_l; size_t slots_l;
+    T* st_o; size_t slots_o;
+    T* pri_p; T* pri_l;
+};
+
+// One thread per LISTED edge: edge list[i] (i when list is null) takes inf[3 i ..].
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_set_edge_inf(int n, const int64_t* __restrict__ list, const double* __restrict__ inf, const uint32_t* __restrict__ map,
+                                                         const uint8_t* __restrict__ cls, EditTables<T> t) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const size_t e = list ? (size_t)list[i] : (size_t)i;
+    const uint2 at = *reinterpret_cast<const uint2*>(map + 2 * e);
+    const T w0 = (T)inf[3 * (size_t)i], w1 = (T)inf[3 * (size_t)i + 1], w2 = (T)inf[3 * (size_t)i + 2];
+    switch (cls[e]) {
+    case kClassLm:
+        st2<T>(t.st_p + 2 * (t.slots_p + at.x), w0, w1);
+        st2<T>(t.st_l + 2 * (t.slots_l + at.y), w0, w1);
+        break;
+    case kClassOdom:
+        t.st_o[(size_t)OD_W0 * t.slots_o + at.x] = w0; t.st_o[(size_t)(OD_W0 + 1) * t.slots_o + at.x] = w1; t.st_o[(size_t)(OD_W0 + 2) * t.slots_o + at.x] = w2;
+        t.st_o[(size_t)OD_W0 * t.slots_o + at.y] = w0; t.st_o[(size_t)(OD_W0 + 1) * t.slots_o + at.y] = w1; t.st_o[(size_t)(OD_W0 + 2) * t.slots_o + at.y] = w2;
+        break;
+    case kClassVlm:
+        t.st_o[(size_t)OD_W0 * t.slots_o + at.x] = w0; t.st_o[(size_t)(OD_W0 + 1) * t.slots_o + at.x] = w1;
+        t.st_o[(size_t)OD_W0 * t.slots_o + at.y] = w0; t.st_o[(size_t)(OD_W0 + 1) * t.slots_o + at.y] = w1;
+        break;
+    case kClassPosePrior: {
+        T* q = t.pri_p + (size_t)at.x * PRI_POSE_REC;
+        q[PRI_W0] = w0; q[PRI_W1] = w1; q[PRI_W2] = w2;
+        break;
+    }
+    case kClassLmPrior: {
+        T* q = t.pri_l + (size_t)at.x * PRI_LM_REC;
+        q[PRL_W0] = w0; q[PRL_W1] = w1;
+        break;
+    }
+    default: break;
+    }
+}
+
+// One thread per edge of the graph: what its FIRST location holds, widened; entries the class does not use are 0.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_get_edge_inf(int n_edges, const uint32_t* __restrict__ map, const uint8_t* __restrict__ cls, EditTables<T> t,
+                                                         double* __restrict__ out) {
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= n_edges) return;
+    const size_t at = map[2 * (size_t)e];
+    double w0 = 0, w1 = 0, w2 = 0;
+    switch (cls[e]) {
+    case kClassLm: { const auto w = ld2<T>(t.st_p + 2 * (t.slots_p + at)); w0 = (double)w.x; w1 = (double)w.y; break; }
+    case kClassOdom: w2 = (double)t.st_o[(size_t)(OD_W0 + 2) * t.slots_o + at]; [[fallthrough]];
+    case kClassVlm: w0 = (double)t.st_o[(size_t)OD_W0 * t.slots_o + at]; w1 = (double)t.st_o[(size_t)(OD_W0 + 1) * t.slots_o + at]; break;
+    case kClassPosePrior: { const T* q = t.pri_p + at * PRI_POSE_REC; w0 = (double)q[PRI_W0]; w1 = (double)q[PRI_W1]; w2 = (double)q[PRI_W2]; break; }
+    case kClassLmPrior: { const T* q = t.pri_l + at * PRI_LM_REC; w0 = (double)q[PRL_W0]; w1 = (double)q[PRL_W1]; break; }
+    default: break;
+    }
+    out[3 * (size_t)e] = w0; out[3 * (size_t)e + 1] = w1; out[3 * (size_t)e + 2] = w2;
+}
+
+}  // namespace tsgo

@@ -1,6 +1,6 @@
 // tsgo_hip.hip — device side of the C ABI in include/tsgo.h: buffers, launches, the Gauss-Newton
 // loop with the reference's stop rules (remote/optimizer/OptimizerCpu.h:80-180), hipGraph replay of
-// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_init_kernels.h.
+// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h.
 //
 // One translation unit; the engine class is laid out over this file and engine/*.inc (each included inside the class body):
 //   this file                      members (what the solver learns grouped by lifetime: SolverMemory), configuration / environment (host/knobs.h), device slabs and upload helpers; the C ABI at the end
@@ -14,6 +14,7 @@
 //   engine/engine_report.inc       tsgo_edge_report: per-edge residual records and the per-class summary
 //   engine/engine_gate.inc         tsgo_gate_edges: candidate edges against the joint marginal of their vertices (Mahalanobis gate)
 //   engine/engine_init.inc         tsgo_init_estimates: estimates from an odometry spanning tree (pointer jumping), landmarks from their observations
+//   engine/engine_edit.inc         tsgo_set_edge_information / tsgo_get_edge_information: the information diagonal of listed edges, in place
 //   engine/engine_testing.inc      tsgo_testing_apply (TSGO_TESTING builds only): the operators PCG applies, read out column by column
 //
 // There is NO CPU fallback in this file: every entry point that computes needs a gfx950 device and
@@ -48,6 +49,7 @@
 #include "host/parallel.h"
 #include "host/problem.h"
 #include "tsgo_amg_kernels.h"
+#include "tsgo_edit_kernels.h"
 #include "tsgo_gate_kernels.h"
 #include "tsgo_init_kernels.h"
 #include "tsgo_kernels.h"
@@ -157,6 +159,8 @@ struct IEngine {
     virtual int gate_edges(int n, const uint32_t* e_type, const uint32_t* e_ids, const double* e_meas, const double* e_inf, double rel_tol, double* rec_out,
                            double* innov_out, tsgo_gate_stats* st) = 0;
     virtual int init_estimates(int what, const uint8_t* mask, int64_t n_mask, tsgo_init_stats* st) = 0;
+    virtual int set_edge_information(int64_t n, const int64_t* edge_idx, const double* e_inf, tsgo_edge_info_stats* st) = 0;
+    virtual int get_edge_information(double* e_inf_out, int64_t cap_edges) = 0;
 #ifdef TSGO_TESTING
     virtual int testing_apply(int which, const double* in, double* out, int n_cols) = 0;
 #endif
@@ -290,7 +294,7 @@ template <typename T> struct Engine : IEngine {
         double hier_shift = 0;             // ... relative raise of the diagonal of the hierarchy's level-0 matrix: hier_shift_cfg until a breakdown
     } mem;
     SolverMemory fresh_memory() const { SolverMemory m; m.cy16 = cfg.cycle_storage != 32; m.hier_shift = hier_shift_cfg; return m; }
-    // 2. Belongs to the TABLES: reset where set_graph builds a new structure, kept by a refill.  (With the report maps, engine_report.inc.)
+    // 2. Belongs to the TABLES: reset where set_graph builds a new structure, kept by a refill.  (With the report maps, engine_report.inc, and the edge -> slot map, engine_edit.inc.)
     int optimize_calls_on_tables = 0;  // tsgo_optimize calls since the tables were built (lazy hipGraph capture, see set_graph)
     hipGraphExec_t cg_graph = nullptr; // (also dropped when the cycle leaves or re-enters the packed format: it holds those kernels)
     double od_live = -1;               // live ODOM slots of this shard (the byte models'), counted once per structure (od_slots_live)
@@ -460,6 +464,7 @@ template <typename T> struct Engine : IEngine {
 #include "engine/engine_gate.inc"
 #include "engine/engine_report.inc"
 #include "engine/engine_init.inc"
+#include "engine/engine_edit.inc"
 #ifdef TSGO_TESTING
 #include "engine/engine_testing.inc"
 #endif
@@ -581,6 +586,14 @@ int tsgo_gate_edges(tsgo_optimizer* o, int32_t n, const uint32_t* e_type, const 
 int tsgo_init_estimates(tsgo_optimizer* o, int32_t what, const uint8_t* odom_mask, int64_t n_mask, tsgo_init_stats* stats) {
     if (!o) return tsgo::set_error(-1, "tsgo_init_estimates: null handle");
     return o->eng->init_estimates(what, odom_mask, n_mask, stats);
+}
+int tsgo_set_edge_information(tsgo_optimizer* o, int64_t n, const int64_t* edge_idx, const double* e_inf, tsgo_edge_info_stats* stats) {
+    if (!o) return tsgo::set_error(-1, "tsgo_set_edge_information: null handle");
+    return o->eng->set_edge_information(n, edge_idx, e_inf, stats);
+}
+int tsgo_get_edge_information(tsgo_optimizer* o, double* e_inf_out, int64_t cap_edges) {
+    if (!o) return tsgo::set_error(-1, "tsgo_get_edge_information: null handle");
+    return o->eng->get_edge_information(e_inf_out, cap_edges);
 }
 void tsgo_reset_history(tsgo_optimizer* o) {
     if (o && o->eng) o->eng->reset_history();

@@ -232,6 +232,37 @@ class HipOptimizer:
                    "tsgo_init_estimates")
         return {f: getattr(st, f) for f, _t in st._fields_}
 
+    def set_edge_information(self, e_inf, edges=None):
+        """Replace the information diagonal of edges of the graph the handle holds, in place on the device (tsgo_set_edge_information).
+        edges: integer positions in the edge arrays of the graph given to set_graph (the numbering of edge_report), e_inf (n, 3) in the
+        same order; edges=None: e_inf is (n_edges, 3), every edge in order.  The estimates, the robust setting and the solver's history
+        stay; the next set_graph replaces every weight with what it carries.  Returns tsgo_edge_info_stats as a dict."""
+        e_inf = np.ascontiguousarray(np.asarray(e_inf, dtype=np.float64).reshape(-1, 3))
+        n = len(e_inf)
+        idx = None
+        if edges is not None:
+            idx = np.ascontiguousarray(np.asarray(edges).reshape(-1).astype(np.int64))
+            if len(idx) != n:
+                raise ValueError("set_edge_information: %d edges listed but e_inf has %d rows" % (len(idx), n))
+        st = _lib.tsgo_edge_info_stats()
+        _lib.check(self.lib, self.lib.tsgo_set_edge_information(self.h, n, idx.ctypes.data if idx is not None and n else None,
+                                                                 e_inf.ctypes.data if n else None, C.byref(st)), "tsgo_set_edge_information")
+        out = {f: getattr(st, f) for f, _t in st._fields_ if f != "reserved"}
+        out["edges_by_class"] = {c: st.edges_by_class[k] for k, c in enumerate(_lib.ROBUST_CLASSES)}
+        return out
+
+    def disable_edges(self, edges):
+        """Switch edges off: information 0, where an edge contributes exactly nothing (set_edge_information with zeros)."""
+        idx = np.asarray(edges).reshape(-1)
+        return self.set_edge_information(np.zeros((len(idx), 3)), idx)
+
+    def edge_information(self):
+        """The information diagonals the handle holds now (tsgo_get_edge_information): (n_edges, 3) in input edge order, widened from the
+        handle's precision; an entry the edge's type does not use is 0."""
+        out = np.zeros((self.n_edges, 3))
+        _lib.check(self.lib, self.lib.tsgo_get_edge_information(self.h, out.ctypes.data if self.n_edges else None, self.n_edges), "tsgo_get_edge_information")
+        return out
+
     def time_kernel(self, which, reps=50):
         us = C.c_double(); nbytes = C.c_double()
         _lib.check(self.lib, self.lib.tsgo_time_kernel(self.h, which, reps, C.byref(us), C.byref(nbytes)),
