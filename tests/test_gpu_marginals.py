@@ -147,6 +147,29 @@ def test_properties_symmetry_determinism_and_query_forms():
     assert rel(one, cov[:6]) <= 1e-9
 
 
+def test_marginal_width_one_agrees_with_width_sixteen(monkeypatch):
+    """The narrow path (one column per batch, a query's solves gathered before the read-out) against the whole-query packing."""
+    g = util.c1_arrays()
+    ids = g.v_id[::23]
+    kinds = g.v_type[::23]
+    poses, lms = int((kinds == 0).sum()), int((kinds == 1).sum())
+    assert poses > 0 and lms > 0
+    out = {}
+    for w in ("16", "1"):
+        monkeypatch.setenv("TSGO_MARGINAL_WIDTH", w)
+        o = HipOptimizer(pcg_rel_tol=1e-12, testing=True)
+        try:
+            o.set_graph(g)
+            o.optimize(5)
+            out[w] = o.marginals(ids, rel_tol=1e-12)
+        finally:
+            o.close()
+    (c16, s16), (c1, s1) = out["16"], out["1"]
+    assert s16["batch_width"] == 16 and s1["batch_width"] == 1
+    assert s1["batches"] == s1["columns"] == 3 * poses + 2 * lms
+    assert np.abs(c1 - c16).max() <= 1e-9 * np.abs(c16).max()
+
+
 def _chain(n=60):
     v_id = np.arange(n, dtype=np.uint32); v_type = np.zeros(n, np.uint32)
     v_pos = np.zeros((n, 3)); v_pos[:, 0] = np.arange(n)

@@ -52,15 +52,14 @@
 #endif
         if (ranks_out) *ranks_out = n;
         if (!collective()) return 0;
-        T* d = nullptr;
-        HIP_OK(hipMalloc((void**)&d, sizeof(T)));
+        CallScratch one; T* d = nullptr;
+        one.want(&d, sizeof(T));
+        if (int rc = one.commit()) return rc;
         T v = (T)(cfg.rank + 1);
-        int rc = 0;
-        if (hipMemcpyAsync(d, &v, sizeof(T), hipMemcpyHostToDevice, stream) != hipSuccess) rc = set_error(-10, "tsgo_comm_selftest: copy to the device failed");
-        if (!rc) rc = allreduce(d, 1);
-        if (!rc && (hipMemcpyAsync(&v, d, sizeof(T), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)) rc = set_error(-10, "tsgo_comm_selftest: the all-reduce did not complete");
-        (void)hipFree(d);
-        if (rc) return rc;
+        HIP_OK(hipMemcpyAsync(d, &v, sizeof(T), hipMemcpyHostToDevice, stream));
+        if (int rc = allreduce(d, 1)) return rc;
+        HIP_OK(hipMemcpyAsync(&v, d, sizeof(T), hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
         const double want = 0.5 * n * (n + 1.0);
         if (n != std::max(1, cfg.world) || std::fabs((double)v - want) > 1e-6) return set_error(-12, "tsgo_comm_selftest: " + std::to_string(n) + " ranks in the communicator, world " + std::to_string(cfg.world) + ", sum " + std::to_string((double)v) + " instead of " + std::to_string(want));
         return 0;
@@ -71,18 +70,17 @@
         HIP_OK(hipSetDevice(cfg.device));
         *us = 0;
         if (!collective()) return 0;
-        T* d = nullptr;
-        HIP_OK(hipMalloc((void**)&d, sizeof(T) * (size_t)n));
-        int rc = 0;
-        if (hipMemsetAsync(d, 0, sizeof(T) * (size_t)n, stream) != hipSuccess) rc = set_error(-10, "tsgo_comm_time_allreduce: memset failed");
-        for (int k = 0; k < 2 && !rc; ++k) rc = allreduce(d, (size_t)n);       // the first call of a size sets its channels up
-        if (!rc && hipEventRecord(ev[0], stream) != hipSuccess) rc = set_error(-10, "tsgo_comm_time_allreduce: event");
-        for (int k = 0; k < reps && !rc; ++k) rc = allreduce(d, (size_t)n);
+        CallScratch zeros; T* d = nullptr;
+        zeros.want(&d, sizeof(T) * (size_t)n);
+        if (int rc = zeros.commit()) return rc;
+        HIP_OK(hipMemsetAsync(d, 0, sizeof(T) * (size_t)n, stream));
+        for (int k = 0; k < 2; ++k) if (int rc = allreduce(d, (size_t)n)) return rc;       // the first call of a size sets its channels up
+        HIP_OK(hipEventRecord(ev[0], stream));
+        for (int k = 0; k < reps; ++k) if (int rc = allreduce(d, (size_t)n)) return rc;
         float ms = 0;
-        if (!rc && (hipEventRecord(ev[1], stream) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess || hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess))
-            rc = set_error(-10, "tsgo_comm_time_allreduce: the all-reduces did not complete");
-        (void)hipStreamSynchronize(stream);
-        (void)hipFree(d);
-        if (!rc) *us = 1e3 * ms / reps;
-        return rc;
+        HIP_OK(hipEventRecord(ev[1], stream));
+        HIP_OK(hipEventSynchronize(ev[1]));
+        HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        *us = 1e3 * ms / reps;
+        return 0;
     }

@@ -58,26 +58,16 @@
             s.ms_tree = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
             // ---- device memory of the call ----
             HIP_OK(hipSetDevice(cfg.device));
-            char* base = nullptr;
-            struct Free { char*& b; ~Free() { if (b) (void)hipFree(b); } } fr{base};
-            hipEvent_t te[2] = {nullptr, nullptr};
-            struct FreeEv { hipEvent_t* e; ~FreeEv() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } fe{te};
+            CallScratch scratch; EventPair te;
             int *parent_d = nullptr, *par_d[2] = {nullptr, nullptr}, *counts_d = nullptr; uint32_t* slot_d = nullptr; InitRec* rec_d[2] = {nullptr, nullptr};
-            {
-                std::vector<std::pair<void**, size_t>> want;
-                if (poses) {
-                    want.push_back({(void**)&rec_d[0], (size_t)P * sizeof(InitRec)}); want.push_back({(void**)&rec_d[1], (size_t)P * sizeof(InitRec)});
-                    want.push_back({(void**)&par_d[0], (size_t)P * sizeof(int)}); want.push_back({(void**)&par_d[1], (size_t)P * sizeof(int)});
-                    want.push_back({(void**)&parent_d, (size_t)P * sizeof(int)}); want.push_back({(void**)&slot_d, (size_t)P * sizeof(uint32_t)});
-                }
-                if (lms) want.push_back({(void**)&counts_d, (size_t)nbL * 2 * sizeof(int)});
-                size_t total = 0;
-                for (auto& w : want) total += (w.second + 255) & ~size_t(255);
-                if (total) HIP_OK(hipMalloc((void**)&base, total));
-                size_t off = 0;
-                for (auto& w : want) { *w.first = base + off; off += (w.second + 255) & ~size_t(255); }
+            if (poses) {
+                scratch.want(&rec_d[0], (size_t)P * sizeof(InitRec)); scratch.want(&rec_d[1], (size_t)P * sizeof(InitRec));
+                scratch.want(&par_d[0], (size_t)P * sizeof(int)); scratch.want(&par_d[1], (size_t)P * sizeof(int));
+                scratch.want(&parent_d, (size_t)P * sizeof(int)); scratch.want(&slot_d, (size_t)P * sizeof(uint32_t));
             }
-            HIP_OK(hipEventCreate(&te[0])); HIP_OK(hipEventCreate(&te[1]));
+            if (lms) scratch.want(&counts_d, (size_t)nbL * 2 * sizeof(int));
+            if (int rc = scratch.commit()) return rc;
+            if (int rc = te.create()) return rc;
             if (poses) {
                 HIP_OK(hipMemcpyAsync(parent_d, h_parent.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, stream));
                 HIP_OK(hipMemcpyAsync(slot_d, h_slot.data(), (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, stream));

@@ -22,6 +22,10 @@
     template <typename... P, typename... A> void launch(void (*kernel)(P...), int grid, A&&... args) {
         kernel<<<dim3(grid), dim3(kBlock), 0, stream>>>(std::forward<A>(args)...);
     }
+    // ... one wavefront (64 threads) per workgroup: the right-hand-side and read-out kernels of the batched solve (__launch_bounds__(64))
+    template <typename... P, typename... A> void launch_wave(void (*kernel)(P...), int grid, A&&... args) {
+        kernel<<<dim3(grid), dim3(64), 0, stream>>>(std::forward<A>(args)...);
+    }
     // A table kernel with an argument head (tsgo_kernels.h, "Argument heads"): the walked table's row offsets, slice and vertex counts and
     // the grid's eighth under the XCD map go first, as plain arguments; `args` continue the head and then list everything else
     template <typename... P, typename... A> void launch_table(void (*kernel)(P...), int grid, const Table<T>& tb, A&&... args) {

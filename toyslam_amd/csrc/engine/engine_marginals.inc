@@ -17,6 +17,7 @@
     static constexpr int kMbChunkMg = 4, kMbChunkBj = 32;      // iterations enqueued between two looks at the batch's state
 
     struct MbBuf {
+        CallScratch mem;      // everything below lies in it (mb_alloc) and goes with it
         T *x = nullptr, *r = nullptr, *z = nullptr, *p = nullptr, *q = nullptr, *s0 = nullptr, *t = nullptr;
         T *dpart = nullptr, *gpart = nullptr, *fd = nullptr, *fg = nullptr;
         MbState<T>* st[2] = {nullptr, nullptr};
@@ -42,7 +43,7 @@
         }); });
     }
     template <int NV, int MODE> void mb_bsr(int n, const int* ptr, const int* col, const H* M, const T* x, const T* b, const H* dinv, const T* omega, T* out, const int* stop) {
-        hipLaunchKernelGGL((k_mb_bsr<T, NV, MODE>), dim3(grid_for(n * NV)), dim3(kBlock), 0, stream, n, ptr, col, M, x, b, dinv, omega, out, stop);
+        launch(k_mb_bsr<T, NV, MODE>, grid_for(n * NV), n, ptr, col, M, x, b, dinv, omega, out, stop);
     }
     // z = V-cycle(r) on the handle's hierarchy, NV columns: level 0 with the implicit Schur passes and Minv (one sweep per side), the levels
     // below with their block-indexed matrices (nu_at(l) block-Jacobi sweeps per side), the coarsest one through its dense inverse.  Same
@@ -51,7 +52,7 @@
         const int P = pr.P;
         const size_t nl = lv.size();
         const int gv = grid_for(P * NV);
-        hipLaunchKernelGGL((k_mb_smooth0<T, NV, 0>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)minv, (const T*)omega_dev, r, (const T*)nullptr, z, stop);
+        launch(k_mb_smooth0<T, NV, 0>, gv, P, (const T*)minv, (const T*)omega_dev, r, (const T*)nullptr, z, stop);
         mb_product<NV, 1>(B, z, B.s0, r, stop);
         mb_bsr<NV, 2>(lv[0].n_agg, lv[0].R_ptr, lv[0].R_col, (const H*)lv[0].Rv, B.s0, nullptr, nullptr, nullptr, nl > 1 ? B.lb[1] : B.b_last, stop);
         for (size_t l = 1; l < nl; ++l) {
@@ -64,7 +65,7 @@
             mb_bsr<NV, 2>(L.n_agg, L.R_ptr, L.R_col, (const H*)L.Rv, B.lres[l], nullptr, nullptr, nullptr, l + 1 < nl ? B.lb[l + 1] : B.b_last, stop);
             B.lfinal[l] = cur;
         }
-        hipLaunchKernelGGL((k_mb_dense<T, NV>), dim3(grid_for(nb_last * NV)), dim3(kBlock), 0, stream, nb_last, (const T*)inv_last, (const T*)B.b_last, B.z_last, stop);
+        launch(k_mb_dense<T, NV>, grid_for(nb_last * NV), nb_last, (const T*)inv_last, (const T*)B.b_last, B.z_last, stop);
         for (size_t l = nl - 1; l >= 1; --l) {
             DevLevel<T>& L = lv[l];
             const int nu = nu_at(l);
@@ -75,124 +76,107 @@
         }
         mb_bsr<NV, 3>(lv[0].n, lv[0].P_ptr, lv[0].P_col, (const H*)lv[0].P, nl > 1 ? B.lfinal[1] : B.z_last, nullptr, nullptr, nullptr, z, stop);
         mb_product<NV, 2>(B, z, B.s0, nullptr, stop);
-        hipLaunchKernelGGL((k_mb_smooth0<T, NV, 1>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)minv, (const T*)omega_dev, r, (const T*)B.s0, z, stop);
+        launch(k_mb_smooth0<T, NV, 1>, gv, P, (const T*)minv, (const T*)omega_dev, r, (const T*)B.s0, z, stop);
     }
 
-    // PCG on one batch (columns already in B.cols): X = S^-1 B, column by column.  out: the largest / summed iterations, and whether
-    // any column broke down (1) or ran out of iterations (2).
-    template <int NV> int mb_solve(MbBuf& B, bool mg, double tol, int* it_max, int64_t* it_sum, int* fail_out) {
+    // PCG on one batch (columns already in B.cols): X = S^-1 B, column by column.  out: the batch and its largest / summed iterations
+    // counted in s, and whether any column broke down (1) or ran out of iterations (2).
+    template <int NV> int mb_solve(MbBuf& B, bool mg, double tol, tsgo_marginal_stats& s, int* fail_out) {
         const int P = pr.P;
         const size_t vb = (size_t)P * NV * 3 * sizeof(T);
         HIP_OK(hipMemsetAsync(B.x, 0, vb, stream));
         HIP_OK(hipMemsetAsync(B.r, 0, vb, stream));
-        hipLaunchKernelGGL((k_mb_rhs<T, NV>), dim3(1), dim3(64), 0, stream, tl, pr.by_lm.G, (const T*)ps, (const T*)lmrec, (const MbColumn*)B.cols, B.r);
+        launch_wave(k_mb_rhs<T, NV>, 1, tl, pr.by_lm.G, (const T*)ps, (const T*)lmrec, (const MbColumn*)B.cols, B.r);
         const int gv = grid_for(P * NV);
-        if (mg) {
-            mb_cycle<NV>(B, B.r, B.z, B.zero);
-            hipLaunchKernelGGL((k_mb_dots<T, NV, 0>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.r, B.z, (const T*)minv, B.gpart, (const int*)B.zero);
-        } else hipLaunchKernelGGL((k_mb_dots<T, NV, 1>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.r, B.z, (const T*)minv, B.gpart, (const int*)B.zero);
-        hipLaunchKernelGGL((k_mb_fold<T>), dim3(1), dim3(kBlock), 0, stream, gv, 2 * NV, (const T*)B.gpart, B.fg, (const int*)B.zero);
-        hipLaunchKernelGGL((k_mb_start<T, NV>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.fg, (const T*)B.z, B.p, B.st[0]);
+        // z = M^-1 r (the cycle, or Minv inside k_mb_dots) and the partials of r^T z, folded
+        auto precondition = [&](const int* stop) {
+            if (mg) {
+                mb_cycle<NV>(B, B.r, B.z, stop);
+                launch(k_mb_dots<T, NV, 0>, gv, P, (const T*)B.r, B.z, (const T*)minv, B.gpart, stop);
+            } else launch(k_mb_dots<T, NV, 1>, gv, P, (const T*)B.r, B.z, (const T*)minv, B.gpart, stop);
+            launch(k_mb_fold<T>, 1, gv, 2 * NV, (const T*)B.gpart, B.fg, stop);
+        };
+        precondition(B.zero);
+        launch(k_mb_start<T, NV>, gv, P, (const T*)B.fg, (const T*)B.z, B.p, B.st[0]);
         const T tol2 = (T)(tol * tol);
         const int chunk = mg ? kMbChunkMg : kMbChunkBj;
         MbState<T> hs;
         int launched = 0;
         for (;;) {
             for (int j = 0; j < chunk; ++j, ++launched) {
-                const int s = launched & 1;
-                const int* stop = reinterpret_cast<const int*>(B.st[s]);      // MbState::all_done
+                const int k = launched & 1;
+                const int* stop = reinterpret_cast<const int*>(B.st[k]);      // MbState::all_done
                 mb_product<NV, 0>(B, B.p, B.q, nullptr, stop);
-                hipLaunchKernelGGL((k_mb_fold<T>), dim3(1), dim3(kBlock), 0, stream, nbP, NV, (const T*)B.dpart, B.fd, stop);
-                hipLaunchKernelGGL((k_mb_alpha<T, NV>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.fd, (const MbState<T>*)B.st[s], (const T*)B.p, (const T*)B.q, B.x, B.r);
-                if (mg) {
-                    mb_cycle<NV>(B, B.r, B.z, stop);
-                    hipLaunchKernelGGL((k_mb_dots<T, NV, 0>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.r, B.z, (const T*)minv, B.gpart, stop);
-                } else hipLaunchKernelGGL((k_mb_dots<T, NV, 1>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.r, B.z, (const T*)minv, B.gpart, stop);
-                hipLaunchKernelGGL((k_mb_fold<T>), dim3(1), dim3(kBlock), 0, stream, gv, 2 * NV, (const T*)B.gpart, B.fg, stop);
-                hipLaunchKernelGGL((k_mb_beta<T, NV>), dim3(gv), dim3(kBlock), 0, stream, P, (const T*)B.fd, (const T*)B.fg, (const MbState<T>*)B.st[s], B.st[s ^ 1],
-                                   (const T*)B.z, B.p, tol2, cfg.pcg_max_iters);
+                launch(k_mb_fold<T>, 1, nbP, NV, (const T*)B.dpart, B.fd, stop);
+                launch(k_mb_alpha<T, NV>, gv, P, (const T*)B.fd, (const MbState<T>*)B.st[k], (const T*)B.p, (const T*)B.q, B.x, B.r);
+                precondition(stop);
+                launch(k_mb_beta<T, NV>, gv, P, (const T*)B.fd, (const T*)B.fg, (const MbState<T>*)B.st[k], B.st[k ^ 1], (const T*)B.z, B.p, tol2, cfg.pcg_max_iters);
             }
             HIP_OK(hipMemcpyAsync(&hs, B.st[launched & 1], sizeof(hs), hipMemcpyDeviceToHost, stream));
             HIP_OK(hipStreamSynchronize(stream));
             if (hs.all_done) break;
             if (launched > cfg.pcg_max_iters + 2 * chunk) return set_error(-20, "tsgo_marginals: PCG did not terminate");
         }
-        int imax = 0, fail = 0; int64_t isum = 0;
-        for (int c = 0; c < NV; ++c) { imax = std::max(imax, hs.col[c].iters); isum += hs.col[c].iters; fail = std::max(fail, hs.col[c].fail); }
-        *it_max = imax; *it_sum = isum; *fail_out = fail;
+        ++s.batches; *fail_out = 0;
+        for (int c = 0; c < NV; ++c) { s.pcg_iters_max = std::max(s.pcg_iters_max, hs.col[c].iters); s.pcg_iters_total += hs.col[c].iters; *fail_out = std::max(*fail_out, hs.col[c].fail); }
         return 0;
     }
 
-    int mb_alloc(MbBuf& B, int NV, char** base) {
-        const int P = pr.P;
-        B.nbV = grid_for(P * NV);
-        std::vector<std::pair<void**, size_t>> want;
-        const size_t pv = (size_t)P * NV * 3 * sizeof(T);
-        for (T** v : {&B.x, &B.r, &B.z, &B.p, &B.q, &B.s0}) want.push_back({(void**)v, pv});
-        want.push_back({(void**)&B.t, (size_t)std::max(pr.L, 1) * NV * 2 * sizeof(T)});
-        want.push_back({(void**)&B.dpart, (size_t)nbP * NV * sizeof(T)});
-        want.push_back({(void**)&B.gpart, (size_t)B.nbV * 2 * NV * sizeof(T)});
-        want.push_back({(void**)&B.fd, (size_t)NV * sizeof(T)});
-        want.push_back({(void**)&B.fg, (size_t)2 * NV * sizeof(T)});
-        want.push_back({(void**)&B.st[0], sizeof(MbState<T>)});
-        want.push_back({(void**)&B.st[1], sizeof(MbState<T>)});
-        want.push_back({(void**)&B.cols, (size_t)kMbMaxWidth * sizeof(MbColumn)});
-        want.push_back({(void**)&B.items, (size_t)kMbMaxWidth * sizeof(MbColumn)});
-        want.push_back({(void**)&B.out, (size_t)kMbMaxWidth * 9 * sizeof(double)});
-        want.push_back({(void**)&B.zero, 4 * sizeof(int)});
+    int mb_alloc(MbBuf& B, int NV) {
+        B.nbV = grid_for(pr.P * NV);
+        CallScratch& m = B.mem;
+        const size_t pv = (size_t)pr.P * NV * 3 * sizeof(T);
+        for (T** v : {&B.x, &B.r, &B.z, &B.p, &B.q, &B.s0}) m.want(v, pv);
+        m.want(&B.t, (size_t)std::max(pr.L, 1) * NV * 2 * sizeof(T));
+        m.want(&B.dpart, (size_t)nbP * NV * sizeof(T));
+        m.want(&B.gpart, (size_t)B.nbV * 2 * NV * sizeof(T));
+        m.want(&B.fd, (size_t)NV * sizeof(T));
+        m.want(&B.fg, (size_t)2 * NV * sizeof(T));
+        for (MbState<T>** v : {&B.st[0], &B.st[1]}) m.want(v, sizeof(MbState<T>));
+        for (MbColumn** v : {&B.cols, &B.items}) m.want(v, (size_t)kMbMaxWidth * sizeof(MbColumn));
+        m.want(&B.out, (size_t)kMbMaxWidth * 9 * sizeof(double));
+        m.want(&B.zero, 4 * sizeof(int));
         const size_t nl = amg_on ? lv.size() : 0;
         B.lb.assign(nl, nullptr); B.lz.assign(nl, nullptr); B.lz2.assign(nl, nullptr); B.lres.assign(nl, nullptr); B.lfinal.assign(nl, nullptr);
-        for (size_t l = 1; l < nl; ++l) {
-            const size_t lvb = (size_t)lv[l].n * NV * 3 * sizeof(T);
-            for (T** v : {&B.lb[l], &B.lz[l], &B.lz2[l], &B.lres[l]}) want.push_back({(void**)v, lvb});
-        }
-        if (amg_on) {
-            want.push_back({(void**)&B.b_last, (size_t)nb_last * NV * 3 * sizeof(T)});
-            want.push_back({(void**)&B.z_last, (size_t)nb_last * NV * 3 * sizeof(T)});
-        }
-        size_t total = 0;
-        for (auto& w : want) total += (w.second + 255) & ~size_t(255);
-        HIP_OK(hipMalloc((void**)base, total));
-        size_t off = 0;
-        for (auto& w : want) { *w.first = *base + off; off += (w.second + 255) & ~size_t(255); }
-        HIP_OK(hipMemsetAsync(*base, 0, total, stream));
+        for (size_t l = 1; l < nl; ++l)
+            for (T** v : {&B.lb[l], &B.lz[l], &B.lz2[l], &B.lres[l]}) m.want(v, (size_t)lv[l].n * NV * 3 * sizeof(T));
+        if (amg_on) for (T** v : {&B.b_last, &B.z_last}) m.want(v, (size_t)nb_last * NV * 3 * sizeof(T));
+        if (int rc = m.commit()) return rc;
+        HIP_OK(hipMemsetAsync(m.base, 0, m.total, stream));
         return 0;
     }
 
-    struct MbQuery { int kind, idx; };
     // the batches of one query list: queries are packed whole (3 columns a pose, 2 a landmark) into batches of NV columns
     template <int NV> int mb_run(const std::vector<MbQuery>& qs, double tol, double* cov, tsgo_marginal_stats& s) {
-        MbBuf B; char* base = nullptr;
-        struct Free { char*& b; ~Free() { if (b) (void)hipFree(b); } } fr{base};
-        if (int rc = mb_alloc(B, NV, &base)) return rc;
-        s.batch_width = NV;
-        s.preconditioner = amg_on ? 1 : 0;
-        float ms = 0;
-        size_t q0 = 0;
-        while (q0 < qs.size()) {
-            std::vector<MbColumn> cols(kMbMaxWidth, MbColumn{-1, 0, 0, 0}), items;
-            int nc = 0; size_t q1 = q0;
-            while (q1 < qs.size()) {
-                const int need = qs[q1].kind == 0 ? 3 : 2;
-                if (nc + need > NV && nc > 0) break;
-                if (need > NV) {      // width 1: one column per batch, a query over several batches
-                    break;
-                }
-                items.push_back(MbColumn{qs[q1].kind, qs[q1].idx, nc, 0});
-                for (int k = 0; k < need; ++k) cols[nc + k] = MbColumn{qs[q1].kind, qs[q1].idx, k, 0};
-                nc += need; ++q1;
-            }
-            if (q1 == q0) return mb_run_narrow<NV>(B, qs, q0, tol, cov, s);      // NV < 3: columns one by one
-            HIP_OK(hipMemcpyAsync(B.cols, cols.data(), cols.size() * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
-            HIP_OK(hipMemcpyAsync(B.items, items.data(), items.size() * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
-            if (int rc = mb_batch<NV>(B, tol, s, &ms)) return rc;
-            std::vector<double> o(items.size() * 9);
-            hipLaunchKernelGGL((k_mb_extract<T, NV>), dim3(1), dim3(64), 0, stream, tl, pr.by_lm.G, (int)items.size(), (const T*)ps, (const T*)lmrec, (const MbColumn*)B.items, (const T*)B.x, B.out);
+        MbBuf B;
+        if (int rc = mb_alloc(B, NV)) return rc;
+        const QueryBatches pl = whole_query_batches(qs, NV);
+        if (pl.narrow) return mb_run_narrow<NV>(B, qs, tol, cov, s);      // NV < 3: columns one by one
+        return mb_for_batches<NV>(B, pl.all, pl.ranges, tol, s, [&](int b, int, int) -> int {
+            const size_t q0 = (size_t)pl.q_off[(size_t)b], n = (size_t)pl.q_off[(size_t)b + 1] - q0;
+            HIP_OK(hipMemcpyAsync(B.items, pl.items.data() + q0, n * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
+            std::vector<double> o(n * 9);
+            launch_wave(k_mb_extract<T, NV>, 1, tl, pr.by_lm.G, (int)n, (const T*)ps, (const T*)lmrec, (const MbColumn*)B.items, (const T*)B.x, B.out);
             HIP_OK(hipMemcpyAsync(o.data(), B.out, o.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
             HIP_OK(hipStreamSynchronize(stream));
-            for (size_t k = 0; k < items.size(); ++k) mb_store(o.data() + 9 * k, cov + 9 * (q0 + k));
+            for (size_t k = 0; k < n; ++k) mb_store(o.data() + 9 * k, cov + 9 * (q0 + k));
+            return 0;
+        });
+    }
+    // Every reader of the batched solve.  For each range (j0, nc) of `all`: the columns go to B.cols (padded to kMbMaxWidth with "none"),
+    // mb_batch solves them (and ends with the one host synchronisation of a batch), after(b, j0, nc) reads X out of B.x with the copies and waits it needs.
+    template <int NV, typename After>
+    int mb_for_batches(MbBuf& B, const std::vector<MbColumn>& all, const BatchRanges& ranges, double tol, tsgo_marginal_stats& s, After&& after) {
+        s.batch_width = NV; s.preconditioner = amg_on ? 1 : 0;
+        float ms = 0;
+        for (size_t b = 0; b < ranges.size(); ++b) {
+            const int j0 = ranges[b].first, nc = ranges[b].second;
+            std::vector<MbColumn> cols(kMbMaxWidth, MbColumn{-1, 0, 0, 0});
+            std::copy(all.begin() + j0, all.begin() + j0 + nc, cols.begin());
+            HIP_OK(hipMemcpyAsync(B.cols, cols.data(), cols.size() * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
+            if (int rc = mb_batch<NV>(B, tol, s, &ms)) return rc;
+            if (int rc = after((int)b, j0, nc)) return rc;
             s.columns += nc;
-            q0 = q1;
         }
         s.ms_solve = ms;
         return 0;
@@ -204,15 +188,11 @@
     // one batch: the handle's preconditioner, repeated with block-Jacobi after a breakdown of the cycle
     template <int NV> int mb_batch(MbBuf& B, double tol, tsgo_marginal_stats& s, float* ms_acc) {
         HIP_OK(hipEventRecord(ev[0], stream));
-        int imax = 0, fail = 0; int64_t isum = 0;
-        if (int rc = mb_solve<NV>(B, amg_on, tol, &imax, &isum, &fail)) return rc;
-        ++s.batches;
-        s.pcg_iters_max = std::max(s.pcg_iters_max, imax); s.pcg_iters_total += isum;
+        int fail = 0;
+        if (int rc = mb_solve<NV>(B, amg_on, tol, s, &fail)) return rc;
         if (fail == 1 && amg_on) {
             ++s.fallbacks; s.preconditioner = 0;
-            if (int rc = mb_solve<NV>(B, false, tol, &imax, &isum, &fail)) return rc;
-            ++s.batches;
-            s.pcg_iters_max = std::max(s.pcg_iters_max, imax); s.pcg_iters_total += isum;
+            if (int rc = mb_solve<NV>(B, false, tol, s, &fail)) return rc;
         }
         HIP_OK(hipEventRecord(ev[1], stream));
         HIP_OK(hipEventSynchronize(ev[1]));
@@ -223,41 +203,35 @@
         if (fail != 0) return set_error(-22, "tsgo_marginals: PCG did not converge within pcg_max_iters");
         return 0;
     }
-    // width 1 (the research baseline): a query's columns in batches of their own; the read-out gathers them from three / two solves
-    template <int NV> int mb_run_narrow(MbBuf& B, const std::vector<MbQuery>& qs, size_t q0, double tol, double* cov, tsgo_marginal_stats& s) {
-        float ms = 0;
+    // width 1 (the research baseline): every column a batch of its own.  A query's three / two solves are gathered on the host into a
+    // [P][need][3] block; after the last of them the block goes back and is read out with the same kernel
+    template <int NV> int mb_run_narrow(MbBuf& B, const std::vector<MbQuery>& qs, double tol, double* cov, tsgo_marginal_stats& s) {
         const int P = pr.P;
-        std::vector<T> xall;
-        for (size_t q = q0; q < qs.size(); ++q) {
-            const int need = qs[q].kind == 0 ? 3 : 2;
-            // X columns of this query, gathered on the host into a [P][need][3] block, then read out with the same kernel
-            xall.assign((size_t)P * need * 3, T(0));
-            std::vector<T> col((size_t)P * NV * 3);
-            for (int k = 0; k < need; ++k) {
-                std::vector<MbColumn> cols(kMbMaxWidth, MbColumn{-1, 0, 0, 0});
-                cols[0] = MbColumn{qs[q].kind, qs[q].idx, k, 0};
-                HIP_OK(hipMemcpyAsync(B.cols, cols.data(), cols.size() * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
-                if (int rc = mb_batch<NV>(B, tol, s, &ms)) return rc;
-                HIP_OK(hipMemcpyAsync(col.data(), B.x, col.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
-                HIP_OK(hipStreamSynchronize(stream));
-                for (int i = 0; i < P; ++i) for (int m = 0; m < 3; ++m) xall[((size_t)i * need + k) * 3 + m] = col[(size_t)i * NV * 3 + m];
-                s.columns += 1;
-            }
-            T* xd = nullptr;
-            HIP_OK(hipMalloc((void**)&xd, xall.size() * sizeof(T)));
-            struct FreeX { T* p; ~FreeX() { (void)hipFree(p); } } fx{xd};
+        std::vector<MbColumn> all; std::vector<size_t> query_of;
+        for (size_t q = 0; q < qs.size(); ++q)
+            for (int k = 0; k < mb_columns_of(qs[q].kind); ++k) { all.push_back(MbColumn{qs[q].kind, qs[q].idx, k, 0}); query_of.push_back(q); }
+        std::vector<T> xall, col((size_t)P * NV * 3);
+        return mb_for_batches<NV>(B, all, full_batches((int)all.size(), 1), tol, s, [&](int, int j, int) -> int {
+            const size_t q = query_of[(size_t)j];
+            const int need = mb_columns_of(qs[q].kind), k = all[(size_t)j].comp;
+            if (k == 0) xall.assign((size_t)P * need * 3, T(0));
+            HIP_OK(hipMemcpyAsync(col.data(), B.x, col.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            for (int i = 0; i < P; ++i) for (int m = 0; m < 3; ++m) xall[((size_t)i * need + k) * 3 + m] = col[(size_t)i * NV * 3 + m];
+            if (k + 1 < need) return 0;
+            CallScratch xs; T* xd = nullptr;
+            xs.want(&xd, xall.size() * sizeof(T));
+            if (int rc = xs.commit()) return rc;
             HIP_OK(hipMemcpyAsync(xd, xall.data(), xall.size() * sizeof(T), hipMemcpyHostToDevice, stream));
             MbColumn it{qs[q].kind, qs[q].idx, 0, 0};
             HIP_OK(hipMemcpyAsync(B.items, &it, sizeof(it), hipMemcpyHostToDevice, stream));
             double o[9];
-            if (need == 3) hipLaunchKernelGGL((k_mb_extract<T, 3>), dim3(1), dim3(64), 0, stream, tl, pr.by_lm.G, 1, (const T*)ps, (const T*)lmrec, (const MbColumn*)B.items, (const T*)xd, B.out);
-            else hipLaunchKernelGGL((k_mb_extract<T, 2>), dim3(1), dim3(64), 0, stream, tl, pr.by_lm.G, 1, (const T*)ps, (const T*)lmrec, (const MbColumn*)B.items, (const T*)xd, B.out);
+            pick<3, 2>(need, [&](auto w) { launch_wave(k_mb_extract<T, w>, 1, tl, pr.by_lm.G, 1, (const T*)ps, (const T*)lmrec, (const MbColumn*)B.items, (const T*)xd, B.out); });
             HIP_OK(hipMemcpyAsync(o, B.out, sizeof(o), hipMemcpyDeviceToHost, stream));
             HIP_OK(hipStreamSynchronize(stream));
             mb_store(o, cov + 9 * q);
-        }
-        s.ms_solve += ms;
-        return 0;
+            return 0;
+        });
     }
 
     // ONE linearisation at the current estimates, without damping, and a hierarchy built for it (both entry points)
@@ -273,10 +247,9 @@
         return 0;
     }
 
-    // the whole call between the snapshot and the restore
-    int mb_compute(const std::vector<MbQuery>& qs, double tol, double* cov, tsgo_marginal_stats& s) {
-        if (int rc = mb_prepare()) return rc;
-        return pick<1, 16, 8>(marginal_width(), [&](auto nv) { return mb_run<nv>(qs, tol, cov, s); });
+    // the whole call between the snapshot and the restore (mb_guarded): the linearisation, then run(the batch width, as a constant)
+    template <typename F> int mb_compute(F&& run) {
+        return mb_guarded([&]() -> int { if (int rc = mb_prepare()) return rc; return pick<1, 16, 8>(marginal_width(), run); });
     }
 
     // The shell both entry points share.  mb_queries: the handle's checks and the id -> (pose | landmark, index) map (`name` prefixes
@@ -314,23 +287,22 @@
         HIP_OK(hipSetDevice(cfg.device));
         size_t total = 0;
         for (const Slab& sl : slabs) total += sl.used;
-        char* snap = nullptr;
-        HIP_OK(hipMalloc((void**)&snap, std::max<size_t>(total, 1)));
-        {
+        CallScratch aside; char* snap = nullptr;
+        aside.want(&snap, std::max<size_t>(total, 1));
+        if (int rc = aside.commit()) return rc;
+        auto copy_slabs = [&](bool back) -> int {      // aside, or back
             size_t off = 0;
-            for (const Slab& sl : slabs) { if (sl.used) { const hipError_t e = hipMemcpyAsync(snap + off, sl.base, sl.used, hipMemcpyDeviceToDevice, stream); if (e != hipSuccess) { (void)hipFree(snap); HIP_OK(e); } } off += sl.used; }
-        }
+            for (const Slab& sl : slabs) { if (sl.used) { const hipError_t e = hipMemcpyAsync(back ? sl.base : snap + off, back ? snap + off : sl.base, sl.used, hipMemcpyDeviceToDevice, stream); HIP_OK(e); } off += sl.used; }
+            return 0;
+        };
+        if (int rc = copy_slabs(false)) return rc;
         const double lambda0 = lambda;
         const std::vector<double> omega0 = omega_host;
         const int rc = run();
         lambda = lambda0; omega_host = omega0;
         const std::string err = rc ? std::string(tsgo_last_error()) : std::string();
-        {
-            size_t off = 0;
-            for (const Slab& sl : slabs) { if (sl.used) { const hipError_t e = hipMemcpyAsync(sl.base, snap + off, sl.used, hipMemcpyDeviceToDevice, stream); if (e != hipSuccess) { (void)hipFree(snap); HIP_OK(e); } } off += sl.used; }
-        }
+        if (int rc2 = copy_slabs(true)) return rc2;
         const hipError_t es = hipStreamSynchronize(stream);
-        (void)hipFree(snap);
         HIP_OK(es);
         if (rc) return set_error(rc, err);
         return 0;
@@ -343,7 +315,7 @@
         if (int rc = mb_queries("tsgo_marginals", ids, n_ids, !cov, qs)) return rc;
         if (n_ids == 0) { if (st_out) *st_out = s; return 0; }
         const double tol = rel_tol > 0 ? rel_tol : cfg.pcg_rel_tol;
-        if (int rc = mb_guarded([&] { return mb_compute(qs, tol, cov, s); })) return rc;
+        if (int rc = mb_compute([&](auto nv) { return mb_run<nv>(qs, tol, cov, s); })) return rc;
         s.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
         if (st_out) *st_out = s;
         return 0;
@@ -355,47 +327,35 @@
     // last is full, and a query's columns may straddle two batches.  After each batch k_mb_joint writes the [D][NV] slice of the result
     // (one host synchronisation), which lands in columns j0 .. j0 + nc of cov.  At the end cov = (C + C^T) / 2.
     template <int NV> int mb_run_joint(const std::vector<MbQuery>& qs, int D, double tol, double* cov, tsgo_marginal_stats& s) {
-        MbBuf B; char* base = nullptr; char* jbase = nullptr;
-        struct Free { char*& b; ~Free() { if (b) (void)hipFree(b); } } fr{base}, fj{jbase};
-        if (int rc = mb_alloc(B, NV, &base)) return rc;
+        MbBuf B;
+        if (int rc = mb_alloc(B, NV)) return rc;
         const size_t nq = qs.size();
         std::vector<MbColumn> items(nq), all;
         all.reserve((size_t)D);
         for (size_t q = 0; q < nq; ++q) {
             items[q] = MbColumn{qs[q].kind, qs[q].idx, (int)all.size(), 0};
-            const int need = qs[q].kind == 0 ? 3 : 2;
-            for (int k = 0; k < need; ++k) all.push_back(MbColumn{qs[q].kind, qs[q].idx, k, 0});
+            for (int k = 0; k < mb_columns_of(qs[q].kind); ++k) all.push_back(MbColumn{qs[q].kind, qs[q].idx, k, 0});
         }
-        const size_t items_b = (nq * sizeof(MbColumn) + 255) & ~size_t(255);
-        HIP_OK(hipMalloc((void**)&jbase, items_b + (size_t)D * NV * sizeof(double)));
-        MbColumn* items_d = reinterpret_cast<MbColumn*>(jbase);
-        double* out_d = reinterpret_cast<double*>(jbase + items_b);
+        CallScratch joint; MbColumn* items_d = nullptr; double* out_d = nullptr;
+        joint.want(&items_d, nq * sizeof(MbColumn));
+        joint.want(&out_d, (size_t)D * NV * sizeof(double));
+        if (int rc = joint.commit()) return rc;
         HIP_OK(hipMemcpyAsync(items_d, items.data(), nq * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
-        s.batch_width = NV;
-        s.preconditioner = amg_on ? 1 : 0;
-        float ms = 0;
         std::vector<double> o((size_t)D * NV);
-        for (int j0 = 0; j0 < D; j0 += NV) {
-            const int nc = std::min(NV, D - j0);
-            std::vector<MbColumn> cols(kMbMaxWidth, MbColumn{-1, 0, 0, 0});
-            std::copy(all.begin() + j0, all.begin() + j0 + nc, cols.begin());
-            HIP_OK(hipMemcpyAsync(B.cols, cols.data(), cols.size() * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
-            if (int rc = mb_batch<NV>(B, tol, s, &ms)) return rc;
-            hipLaunchKernelGGL((k_mb_joint<T, NV>), dim3((unsigned)nq), dim3(64), 0, stream, tl, pr.by_lm.G, (const T*)ps, (const T*)lmrec,
-                               (const MbColumn*)items_d, (const MbColumn*)B.cols, (const T*)B.x, out_d);
+        if (int rc = mb_for_batches<NV>(B, all, full_batches(D, NV), tol, s, [&](int, int j0, int nc) -> int {
+            launch_wave(k_mb_joint<T, NV>, (int)nq, tl, pr.by_lm.G, (const T*)ps, (const T*)lmrec, (const MbColumn*)items_d, (const MbColumn*)B.cols, (const T*)B.x, out_d);
             HIP_OK(hipGetLastError());
             HIP_OK(hipMemcpyAsync(o.data(), out_d, o.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
             HIP_OK(hipStreamSynchronize(stream));
             for (int r = 0; r < D; ++r)
                 for (int c = 0; c < nc; ++c) cov[(size_t)r * D + j0 + c] = o[(size_t)r * NV + c];
-            s.columns += nc;
-        }
+            return 0;
+        })) return rc;
         for (int r = 0; r < D; ++r)
             for (int c = 0; c < r; ++c) {
                 const double v = 0.5 * (cov[(size_t)r * D + c] + cov[(size_t)c * D + r]);
                 cov[(size_t)r * D + c] = v; cov[(size_t)c * D + r] = v;
             }
-        s.ms_solve = ms;
         return 0;
     }
 
@@ -417,11 +377,7 @@
         if (D == 0) { if (st_out) *st_out = s; return 0; }
         const double tol = rel_tol > 0 ? rel_tol : cfg.pcg_rel_tol;
         const int Di = (int)D;
-        const int rc = mb_guarded([&]() -> int {
-            if (int r = mb_prepare()) return r;
-            return pick<1, 16, 8>(marginal_width(), [&](auto nv) { return mb_run_joint<nv>(qs, Di, tol, cov, s); });
-        });
-        if (rc) return rc;
+        if (int rc = mb_compute([&](auto nv) { return mb_run_joint<nv>(qs, Di, tol, cov, s); })) return rc;
         s.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
         if (st_out) *st_out = s;
         return 0;

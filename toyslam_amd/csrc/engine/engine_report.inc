@@ -64,9 +64,9 @@
         if (rec_out && cap_edges < (int64_t)E) return set_error(-1, "tsgo_edge_report: cap_edges " + std::to_string(cap_edges) + " is below n_edges = " + std::to_string(E));
         HIP_OK(hipSetDevice(cfg.device));
         if (int rc = report_prepare()) return rc;
-        T* rec_dev = nullptr;
-        struct Free { T*& p; ~Free() { if (p) (void)hipFree(p); } } fr{rec_dev};
-        if (rec_out && E > 0) HIP_OK(hipMalloc((void**)&rec_dev, 6 * E * sizeof(T)));
+        CallScratch records; T* rec_dev = nullptr;
+        if (rec_out && E > 0) records.want(&rec_dev, 6 * E * sizeof(T));
+        if (int rc = records.commit()) return rc;
         launch_report(rec_dev);
         HIP_OK(hipGetLastError());
         const size_t n_main = (size_t)nbP * kEdgeClasses, n_lp = report_lm_priors() ? (size_t)nbL : 0;

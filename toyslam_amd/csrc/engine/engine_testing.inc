@@ -21,9 +21,8 @@
     }
     template <int NV> int ta_batched(const std::vector<int>& of_graph, const double* in, double* out, int n_cols) {
         const int P = pr.P;
-        MbBuf B; char* base = nullptr;
-        struct Free { char*& b; ~Free() { if (b) (void)hipFree(b); } } fr{base};
-        if (int rc = mb_alloc(B, NV, &base)) return rc;
+        MbBuf B;
+        if (int rc = mb_alloc(B, NV)) return rc;
         std::vector<T> h((size_t)P * NV * 3, T(0));
         for (int c = 0; c < n_cols; ++c)
             for (int i = 0; i < P; ++i) for (int k = 0; k < 3; ++k) h[((size_t)i * NV + c) * 3 + k] = (T)in[(size_t)c * 3 * P + 3 * (size_t)of_graph[i] + k];
@@ -60,8 +59,7 @@
                 // zc (and zc32) = omega_0 Minv r as k_cg_step / k_pose_finalize leave them: k_warm_residual with S x0 = 0 is that arithmetic
                 if (int rc = ta_load_r(of_graph, x_in, h3)) return rc;
                 HIP_OK(hipMemsetAsync(sbuf, 0, sizeof(T) * (size_t)P * 3, stream));
-                hipLaunchKernelGGL((k_warm_residual<T>), dim3(nbC), dim3(kBlock), 0, stream, P, (const T*)sbuf, (const T*)minv, r, zc, (const T*)(amg_on ? omega_dev : one_dev), npart,
-                                   amg_on && low_cycle ? zc32 : (float*)nullptr);
+                launch(k_warm_residual<T>, nbC, P, (const T*)sbuf, (const T*)minv, r, zc, (const T*)(amg_on ? omega_dev : one_dev), npart, amg_on && low_cycle ? zc32 : (float*)nullptr);
                 if (amg_on) { if (int rc = launch_vcycle(0)) return rc; }
             }
             if (from_sbuf) {

@@ -18,8 +18,7 @@ namespace tsgo {
 // (LM), (p1x, p1y, p2x, p2y) (virtual landmark), (mx, my, cos, sin) (pose prior), (mx, my) (landmark prior); w = the raw information diagonal.
 // i0, i1: internal pose / landmark numbers (i1 = i0 for a unary type).
 template <typename T> struct GateCand { int type, i0, i1, pad; T m[6]; T w[3]; T pad2; };
-// One candidate's visit in one batch: the first rows of its two vertices in that batch's k_mb_joint slice (r1 unused for a unary type)
-struct GateJob { int cand, r0, r1, pad; };
+// (GateJob, one candidate's visit in one batch: host/batch_plan.h)
 
 constexpr int kGateSig = 36;      // doubles per candidate: the 6 x 6 pair block
 constexpr int kGateRec = 8;       // (e0, e1, e2, s, d2, dof, logdet, status)

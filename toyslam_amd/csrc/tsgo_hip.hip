@@ -3,14 +3,15 @@
 // the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h.
 //
 // One translation unit; the engine class is laid out over this file and engine/*.inc (each included inside the class body):
-//   this file                      members (what the solver learns grouped by lifetime: SolverMemory), configuration / environment (host/knobs.h), device slabs and upload helpers; the C ABI at the end
+//   this file                      members (what the solver learns grouped by lifetime: SolverMemory), configuration / environment (host/knobs.h), device slabs, call-scoped device scratch (CallScratch, EventPair) and upload helpers; the C ABI at the end
 //   engine/engine_hierarchy.inc    the multigrid hierarchy on the device: patterns, symbolic products, dense bottom operators
 //   engine/engine_graph.inc        tsgo_set_graph: tables, value staging, structure re-use, where SolverMemory starts afresh, solver history across requests
 //   engine/engine_launch.inc       every kernel launch of a linearisation / a hierarchy build / a PCG iteration
 //   engine/engine_collective.inc   the all-reduces of an edge-sharded run
 //   engine/engine_solve.inc        the Gauss-Newton and Levenberg-Marquardt loops, the PCG drivers and the retry ladder (do_solve), read-outs
 //   engine/engine_probes.inc       timing probes (bench.py)
-//   engine/engine_marginals.inc    tsgo_marginals, tsgo_joint_marginals: batched PCG for blocks of H^-1
+//   engine/engine_marginals.inc    tsgo_marginals, tsgo_joint_marginals: batched PCG for blocks of H^-1, one column-batch driver for every reader (mb_for_batches)
+//   host/batch_plan.h              (host only, no HIP) how the readers cut their columns into batches; the gate's per-batch lists
 //   engine/engine_report.inc       tsgo_edge_report: per-edge residual records and the per-class summary
 //   engine/engine_gate.inc         tsgo_gate_edges: candidate edges against the joint marginal of their vertices (Mahalanobis gate)
 //   engine/engine_init.inc         tsgo_init_estimates: estimates from an odometry spanning tree (pointer jumping), landmarks from their observations
@@ -434,6 +435,27 @@ template <typename T> struct Engine : IEngine {
         *out = (U*)ptr;
         return 0;
     }
+    // Device memory that lives for ONE call (what dalloc is for a graph): want() lists the buffers, commit() makes one hipMalloc of their sizes,
+    // each rounded up to 256 B, and hands the pointers out in the order asked (no allocation when the sum is 0); freed with the object.
+    struct CallScratch {
+        char* base = nullptr; size_t total = 0; std::vector<std::pair<void**, size_t>> wants;
+        CallScratch() = default; CallScratch(const CallScratch&) = delete; void operator=(const CallScratch&) = delete;
+        ~CallScratch() { if (base) (void)hipFree(base); }
+        template <typename U> void want(U** out, size_t bytes) { wants.push_back({(void**)out, (bytes + 255) & ~size_t(255)}); total += wants.back().second; }
+        int commit() {
+            if (total) HIP_OK(hipMalloc((void**)&base, total));
+            size_t off = 0;
+            for (auto& w : wants) { *w.first = base + off; off += w.second; }
+            return 0;
+        }
+    };
+    // ... and a pair of events that lives for one call
+    struct EventPair {
+        hipEvent_t e[2] = {nullptr, nullptr}; EventPair() = default; EventPair(const EventPair&) = delete; void operator=(const EventPair&) = delete;
+        ~EventPair() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+        int create() { HIP_OK(hipEventCreate(&e[0])); HIP_OK(hipEventCreate(&e[1])); return 0; }
+        hipEvent_t operator[](int k) const { return e[k]; }
+    };
     int upload_T(T** out, const double* src, size_t n) {
         if (int rc = dalloc(out, n)) return rc;
         if (n == 0) return 0;

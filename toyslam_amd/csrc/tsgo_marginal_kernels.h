@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "host/batch_plan.h"
 #include "tsgo_amg_kernels.h"
 #include "tsgo_kernels.h"
 
@@ -361,8 +362,7 @@ __global__ __launch_bounds__(kBlock) void k_mb_dense(int nb, const T* __restrict
 }
 
 // ---- right-hand sides and read-out -------------------------------------------------------------------------------------------
-// One query column: a unit column of pose `idx` (comp = 0, 1, 2), or column `comp` of Y_l = W_{:,l} Dl^-1 for landmark `idx`.
-struct MbColumn { int kind, idx, comp, pad; };      // kind 0 pose, 1 landmark, -1 none
+// (one query column, MbColumn: host/batch_plan.h)
 
 // One slot k of a landmark in the landmark-major table: its pose and Y_il = W_il Dl^-1 (3 x 2).  Padding slots have zero weights and
 // give Y = 0.
