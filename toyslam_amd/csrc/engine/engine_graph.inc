@@ -181,19 +181,12 @@
     int carry_in(const tsgo_graph& g) {
         if (carry.n <= 0) return 0;
         const int n_old = carry.n; carry.n = 0;
-        uint32_t max_id = 0;
-        for (uint32_t id : carry.pose_id) max_id = std::max(max_id, id);
-        const bool flat = (uint64_t)max_id < 8ull * (uint64_t)carry.P + 1024;
-        std::vector<int> table(flat ? (size_t)max_id + 1 : 0, -1);
-        std::unordered_map<uint32_t, int> by_id;
-        if (flat) for (int i = 0; i < carry.P; ++i) table[carry.pose_id[(size_t)i]] = i;
-        else { by_id.reserve((size_t)carry.P * 2); for (int i = 0; i < carry.P; ++i) by_id.emplace(carry.pose_id[(size_t)i], i); }
+        IdMap old;      // the previous graph's pose ids (distinct: they passed build_problem), a few of many vertex ids: a wider flat table
+        old.build(carry.pose_id.data(), carry.P, 8);
         std::vector<int> src((size_t)pr.P);
         int found = 0;
         for (int i = 0; i < pr.P; ++i) {
-            const uint32_t id = g.v_id[(size_t)pr.pose_vertex[(size_t)i]];
-            int j = -1;
-            if (flat) { if (id <= max_id) j = table[id]; } else { auto it = by_id.find(id); if (it != by_id.end()) j = it->second; }
+            const int j = old.find(g.v_id[(size_t)pr.pose_vertex[(size_t)i]]);
             src[(size_t)i] = j; found += j >= 0;
         }
         if (2 * (int64_t)found < (int64_t)std::max(pr.P, carry.P)) return 0;      // another graph altogether (or one grown beyond recognition): nothing to continue
@@ -261,8 +254,7 @@
         if (last_set_reused) return refill(g);
         if (int rc = carry_out()) return rc;
         release();
-        drop_report_maps();      // the slot -> input-edge maps of tsgo_edge_report lived in the slabs just released and described the old tables
-        drop_edit_maps();        // ... and so did the edge -> slot map of tsgo_set_edge_information
+        drop_structure_maps();      // the index described the old tables, and its device maps lived in the slabs just released
         BuildOptions bo; bo.rank = cfg.rank; bo.world = cfg.world; bo.lanes_per_pose = cfg.lanes_per_pose; bo.lanes_per_lm = cfg.lanes_per_lm;
         bo.fill_planes = false;
         const std::string err = build_problem(g, bo, pr);

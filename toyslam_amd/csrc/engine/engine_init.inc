@@ -24,10 +24,11 @@
             const bool poses = (what & TSGO_INIT_POSES) != 0, lms = (what & TSGO_INIT_LANDMARKS) != 0 && L > 0 && tl.n_slices > 0;
             // ---- the tree, then its two words per pose in the internal numbering ----
             InitTree tree;
+            const VertexIndex& vi = vertices();
             {
                 const tsgo_graph view{(int32_t)structure.v_id.size(), structure.v_id.data(), structure.v_type.data(), nullptr, (int32_t)E, structure.e_type.data(),
                                       structure.e_ids.data(), nullptr, nullptr, (int32_t)structure.fixed.size(), structure.fixed.data()};
-                const std::string err = build_init_tree(view, mask, n_mask, tree);
+                const std::string err = build_init_tree(view, mask, n_mask, tree, &vi.ids);
                 if (!err.empty()) return set_error(-2, "tsgo_init_estimates: " + err);
             }
             s.roots_fixed = tree.roots_fixed; s.roots_free = tree.roots_free; s.edges_usable = tree.edges_usable; s.tree_edges = tree.tree_edges;
@@ -35,24 +36,21 @@
             const int rounds = poses ? tree.rounds() : 0;
             std::vector<int> h_parent; std::vector<uint32_t> h_slot;
             if (poses) {
-                std::vector<int> pose_of((size_t)pr.n_vertices, -1);
-                for (int i = 0; i < P; ++i) pose_of[(size_t)pr.pose_vertex[(size_t)i]] = i;
-                std::vector<uint32_t> slot_of(E, kNoEdge);      // an ODOM edge -> the first slot that holds it
+                const EdgeSlots* es = edges("tsgo_init_estimates");
+                if (!es) return -30;
                 const size_t So = pr.odom.slots();
-                for (size_t k = 0; k < So; ++k) {
-                    const uint32_t e = pr.odom.edge[k];
-                    if (e != kNoEdge && e < E && !(pr.odom.idx[k] & kVlmBit) && slot_of[e] == kNoEdge) slot_of[e] = (uint32_t)k;
-                }
                 h_parent.assign((size_t)P, -1); h_slot.assign((size_t)P, 0u);
                 for (int i = 0; i < P; ++i) {
                     const int v = pr.pose_vertex[(size_t)i], pv = tree.parent[(size_t)v];
                     if (pv < 0) continue;
                     const int e = tree.edge[(size_t)v];
+                    // the first slot that holds the tree edge (an ODOM edge: either endpoint's slot keeps the same planes)
+                    const uint32_t at = e < 0 || (size_t)e >= E || structure.e_type[(size_t)e] != kClassOdom ? kNoEdge : es->first_odom_slot((size_t)e);
                     // what the kernels rely on: the parent is a pose of this table, the edge sits in a slot of it
-                    if (pose_of[(size_t)pv] < 0 || e < 0 || (size_t)e >= E || slot_of[(size_t)e] == kNoEdge || (size_t)slot_of[(size_t)e] >= So || So >= (size_t)kInitInverse)
+                    if (vi.pose_of(pv) < 0 || at == kNoEdge || (size_t)at >= So || So >= (size_t)kInitInverse)
                         return set_error(-30, "tsgo_init_estimates: the pose-pose table does not hold tree edge " + std::to_string(e));
-                    h_parent[(size_t)i] = pose_of[(size_t)pv];
-                    h_slot[(size_t)i] = slot_of[(size_t)e] | (structure.e_ids[2 * (size_t)e] == structure.v_id[(size_t)v] ? kInitInverse : 0u);
+                    h_parent[(size_t)i] = vi.pose_of(pv);
+                    h_slot[(size_t)i] = at | (structure.e_ids[2 * (size_t)e] == structure.v_id[(size_t)v] ? kInitInverse : 0u);
                 }
             }
             s.ms_tree = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();

@@ -269,15 +269,11 @@
         fixed |= has_full_pose_prior();      // a pose prior on every axis anchors H to the world frame
         if (!fixed) return set_error(-1, nm + ": marginals need a fixed vertex (without one H is singular)");
         qs.resize((size_t)n_ids);
-        std::unordered_map<uint32_t, int> pos; pos.reserve(structure.v_id.size() * 2);
-        for (size_t v = 0; v < structure.v_id.size(); ++v) pos.emplace(structure.v_id[v], (int)v);
-        std::vector<MbQuery> of_vertex((size_t)pr.n_vertices, MbQuery{-1, 0});
-        for (int i = 0; i < pr.P; ++i) of_vertex[(size_t)pr.pose_vertex[i]] = MbQuery{0, i};
-        for (int l = 0; l < pr.L; ++l) of_vertex[(size_t)pr.lm_vertex[l]] = MbQuery{1, l};
+        const VertexIndex& vi = vertices();
         for (int k = 0; k < n_ids; ++k) {
-            auto it = pos.find(ids[k]);
-            if (it == pos.end() || of_vertex[(size_t)it->second].kind < 0) { qs.clear(); return set_error(-1, nm + ": unknown vertex id " + std::to_string(ids[k])); }
-            qs[(size_t)k] = of_vertex[(size_t)it->second];
+            const int v = vi.ids.find(ids[k]);
+            if (v < 0 || vi.of[(size_t)v].kind < 0) { qs.clear(); return set_error(-1, nm + ": unknown vertex id " + std::to_string(ids[k])); }
+            qs[(size_t)k] = vi.of[(size_t)v];
         }
         return 0;
     }

@@ -7,45 +7,30 @@
 // the call — so the estimates, the solver history and everything the next tsgo_optimize or tsgo_linearize reads stay bit for bit.
 //
 // The maps (SellTable::edge of by_pose and odom, Problem::prior_p_edge / prior_l_edge) exist on the host for every graph and go to the
-// device at the first report on a structure: a handle that never asks pays nothing.  They belong to the STRUCTURE: a tsgo_set_graph that
-// reuses it keeps them, one that rebuilds drops them (drop_report_maps, called where set_graph releases the slabs).
-    uint32_t *rep_lm_edge = nullptr, *rep_od_edge = nullptr, *rep_pp_edge = nullptr, *rep_pl_edge = nullptr;
-    ReportPartial<T>* rep_part = nullptr;      // [nbP][kEdgeClasses] of k_edge_report, then [nbL] of k_edge_report_lm_prior
-    bool rep_ready = false;
-    int rep_uploads = 0;                       // map uploads of this handle (diagnostics)
-    void drop_report_maps() { rep_lm_edge = rep_od_edge = rep_pp_edge = rep_pl_edge = nullptr; rep_part = nullptr; rep_ready = false; }
-
+// device at the first report on a structure: a handle that never asks pays nothing.  They belong to the STRUCTURE (StructureMaps,
+// tsgo_hip.hip): a tsgo_set_graph that reuses it keeps them, one that rebuilds drops them where it releases the slabs.
     bool report_lm_priors() const { return pr.has_priors && tl.n_slices > 0; }
     int report_prepare() {
-        if (rep_ready) return 0;
-        // what the kernels rely on, checked once per structure: every map entry is an input edge, and every input edge sits in exactly one
-        // slot the pass evaluates (a record is written once, inside the result buffer)
-        const size_t E = structure.e_type.size();
-        std::vector<unsigned char> seen(E, 0);
-        bool ok = true;
-        auto take = [&](uint32_t e) { if (e >= E || seen[e]) ok = false; else seen[e] = 1; };
-        for (uint32_t e : pr.by_pose.edge) if (e != kNoEdge) take(e);
-        for (size_t k = 0; k < pr.odom.edge.size(); ++k) if (pr.odom.edge[k] != kNoEdge && !(pr.odom.idx[k] & kDirBit)) take(pr.odom.edge[k]);
-        for (uint32_t e : pr.prior_p_edge) take(e);
-        for (uint32_t e : pr.prior_l_edge) take(e);
-        for (unsigned char s : seen) ok = ok && s;
-        if (!ok) return set_error(-30, "tsgo_edge_report: the slot tables do not list every input edge exactly once");
-        if (int rc = upload_u32m(&rep_lm_edge, pr.by_pose.edge)) return rc;
-        if (int rc = upload_u32m(&rep_od_edge, pr.odom.edge)) return rc;
-        if (int rc = upload_u32m(&rep_pp_edge, pr.prior_p_edge)) return rc;
-        if (int rc = upload_u32m(&rep_pl_edge, pr.prior_l_edge)) return rc;
-        if (int rc = dalloc(&rep_part, (size_t)nbP * kEdgeClasses + (size_t)std::max(nbL, 1))) return rc;
-        rep_ready = true; ++rep_uploads;
+        if (maps.rep_ready) return 0;
+        // what the kernels rely on — every map entry is an input edge, and every input edge sits in exactly one slot the pass evaluates (a
+        // record is written once, inside the result buffer) — follows from the structure index's check (host/structure_index.h)
+        if (!edges("tsgo_edge_report")) return -30;
+        if (int rc = upload_u32m(&maps.rep_lm_edge, pr.by_pose.edge)) return rc;
+        if (int rc = upload_u32m(&maps.rep_od_edge, pr.odom.edge)) return rc;
+        if (int rc = upload_u32m(&maps.rep_pp_edge, pr.prior_p_edge)) return rc;
+        if (int rc = upload_u32m(&maps.rep_pl_edge, pr.prior_l_edge)) return rc;
+        if (int rc = dalloc(&maps.rep_part, (size_t)nbP * kEdgeClasses + (size_t)std::max(nbL, 1))) return rc;
+        maps.rep_ready = true;
         return 0;
     }
     // the pass (tsgo_time_kernel 8 too).  rec = nullptr: summary only
     void launch_report(T* rec) {
         if (report_lm_priors()) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(rk(), [&](auto rk) {
-            launch(k_edge_report_lm_prior<T, g, rk>, nbL, tl, (const T*)lmrec, (const uint32_t*)rep_pl_edge, rec, rep_part + (size_t)nbP * kEdgeClasses, lm_prior_args(), robust_args());
+            launch(k_edge_report_lm_prior<T, g, rk>, nbL, tl, (const T*)lmrec, (const uint32_t*)maps.rep_pl_edge, rec, maps.rep_part + (size_t)nbP * kEdgeClasses, lm_prior_args(), robust_args());
         }); });
         pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick<0, 1>(rk(), [&](auto rk) {
-            launch(k_edge_report<T, g, general, pri, rk>, nbP, tp, to, (const T*)ps, (const T*)lmrec, (const uint32_t*)rep_lm_edge, (const uint32_t*)rep_od_edge,
-                   (const uint32_t*)rep_pp_edge, rec, rep_part, pri ? pose_prior_args() : no_priors(), robust_args());
+            launch(k_edge_report<T, g, general, pri, rk>, nbP, tp, to, (const T*)ps, (const T*)lmrec, (const uint32_t*)maps.rep_lm_edge, (const uint32_t*)maps.rep_od_edge,
+                   (const uint32_t*)maps.rep_pp_edge, rec, maps.rep_part, pri ? pose_prior_args() : no_priors(), robust_args());
         }); }); }); });
     }
     // what k_chi2 reads, 4 B of map per evaluated slot, the partials; with records 6 numbers per edge more
@@ -71,7 +56,7 @@
         HIP_OK(hipGetLastError());
         const size_t n_main = (size_t)nbP * kEdgeClasses, n_lp = report_lm_priors() ? (size_t)nbL : 0;
         std::vector<ReportPartial<T>> hp(n_main + n_lp);
-        HIP_OK(hipMemcpyAsync(hp.data(), rep_part, hp.size() * sizeof(ReportPartial<T>), hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipMemcpyAsync(hp.data(), maps.rep_part, hp.size() * sizeof(ReportPartial<T>), hipMemcpyDeviceToHost, stream));
         if (rec_dev) {
             if constexpr (sizeof(T) == sizeof(double)) HIP_OK(hipMemcpyAsync(rec_out, rec_dev, 6 * E * sizeof(T), hipMemcpyDeviceToHost, stream));
             else {      // f32 records widened on the host

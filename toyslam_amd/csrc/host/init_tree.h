@@ -10,10 +10,10 @@
 #pragma once
 #include <cstdint>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../../include/tsgo.h"
+#include "structure_index.h"
 
 namespace tsgo {
 
@@ -25,26 +25,20 @@ struct InitTree {
 };
 
 // Returns the empty string on success, otherwise the error text.  Reads v_id, v_type, e_type, e_ids and fixed of g; nothing else.
-inline std::string build_init_tree(const tsgo_graph& g, const uint8_t* mask, int64_t n_mask, InitTree& t) {
+// ids: the map of g.v_id when the caller holds one (the engine: the ids are then known to be distinct), else one is built here.
+inline std::string build_init_tree(const tsgo_graph& g, const uint8_t* mask, int64_t n_mask, InitTree& t, const IdMap* ids = nullptr) {
     if (g.n_vertices < 0 || g.n_edges < 0 || g.n_fixed < 0) return "negative count";
     if (mask && n_mask != (int64_t)g.n_edges) return "n_mask = " + std::to_string(n_mask) + " but the graph has " + std::to_string(g.n_edges) + " edges (one byte per edge)";
     const int nV = g.n_vertices, nE = g.n_edges;
-    uint32_t max_id = 0;
-    for (int i = 0; i < nV; ++i) max_id = g.v_id[i] > max_id ? g.v_id[i] : max_id;
-    const bool flat = nV > 0 && (uint64_t)max_id < 4ull * (uint64_t)nV + 1024;
-    std::vector<int> table(flat ? (size_t)max_id + 1 : 0, -1);
-    std::unordered_map<uint32_t, int> by_id;
-    if (!flat) by_id.reserve((size_t)nV * 2);
-    for (int i = 0; i < nV; ++i) {
-        if (g.v_type[i] > 1) return "unknown vertex type " + std::to_string(g.v_type[i]);
-        if (flat) { if (table[g.v_id[i]] >= 0) return "duplicate vertex id " + std::to_string(g.v_id[i]); table[g.v_id[i]] = i; }
-        else if (!by_id.emplace(g.v_id[i], i).second) return "duplicate vertex id " + std::to_string(g.v_id[i]);
+    int typed = 0;      // vertices before the first of unknown type: vertex by vertex the type is checked before the id (as build_problem does)
+    while (typed < nV && g.v_type[typed] <= 1) ++typed;
+    IdMap own;
+    if (!ids) {
+        uint32_t dup = 0;
+        if (!own.build(g.v_id, typed, kVertexIdSlack, &dup)) return "duplicate vertex id " + std::to_string(dup);
+        ids = &own;
     }
-    auto lookup = [&](uint32_t id) -> int {
-        if (flat) return id <= max_id ? table[id] : -1;
-        auto it = by_id.find(id);
-        return it == by_id.end() ? -1 : it->second;
-    };
+    if (typed < nV) return "unknown vertex type " + std::to_string(g.v_type[typed]);
     t = InitTree();
     t.parent.assign((size_t)nV, -1); t.edge.assign((size_t)nV, -1); t.depth.assign((size_t)nV, -1);
     // usable edges by endpoint (CSR over vertex positions; filled in edge order, so every list is in increasing edge index)
@@ -53,7 +47,7 @@ inline std::string build_init_tree(const tsgo_graph& g, const uint8_t* mask, int
     for (int e = 0; e < nE; ++e) {
         if (g.e_type[e] != 0) continue;
         const uint32_t id1 = g.e_ids[2 * (size_t)e], id2 = g.e_ids[2 * (size_t)e + 1];
-        const int a = lookup(id1), b = lookup(id2);
+        const int a = ids->find(id1), b = ids->find(id2);
         if (a < 0 || b < 0) return "edge " + std::to_string(e) + " refers to an unknown vertex id";
         if (g.v_type[a] != 0 || g.v_type[b] != 0) return "ODOM edge " + std::to_string(e) + " must join two Se2 vertices";
         if (id1 == id2 || (mask && mask[e] == 0)) continue;
@@ -70,7 +64,7 @@ inline std::string build_init_tree(const tsgo_graph& g, const uint8_t* mask, int
     std::vector<int> queue; queue.reserve((size_t)nV);
     size_t head = 0;
     for (int i = 0; i < g.n_fixed; ++i) {
-        const int v = lookup(g.fixed[i]);
+        const int v = ids->find(g.fixed[i]);
         if (v < 0) return "fixed vertex id " + std::to_string(g.fixed[i]) + " is unknown";
         if (g.v_type[v] != 0 || t.depth[(size_t)v] >= 0) continue;      // a landmark, or a pose listed before
         t.depth[(size_t)v] = 0; queue.push_back(v); ++t.roots_fixed;

@@ -1,6 +1,6 @@
 // problem.h — host-side layout of one optimisation problem, built once per request.
 //
-// The reference keeps an unordered_map of heap vertices and a vector of heap edges
+// The reference keeps a hash map of heap vertices and a vector of heap edges
 // (remote/graph/GraphCpu.h:55-57) and, on its CUDA path, a byte-packed arena plus AoS edge arrays
 // (remote/cuda/graph/GraphGpu.h:80-187).  Here the graph becomes:
 //   * dense internal vertex numbers per class (pose p, landmark l), degree-sorted inside windows;

@@ -3,7 +3,8 @@
 // the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h.
 //
 // One translation unit; the engine class is laid out over this file and engine/*.inc (each included inside the class body):
-//   this file                      members (what the solver learns grouped by lifetime: SolverMemory), configuration / environment (host/knobs.h), device slabs, call-scoped device scratch (CallScratch, EventPair) and upload helpers; the C ABI at the end
+//   this file                      members (what the solver learns grouped by lifetime: SolverMemory; the structure index and its device maps), configuration / environment (host/knobs.h), device slabs, call-scoped device scratch (CallScratch, EventPair) and upload helpers; the C ABI at the end
+//   host/structure_index.h         (host only, no HIP) vertex id -> position -> internal number, input edge -> slots: the one index every reader of the tables uses
 //   engine/engine_hierarchy.inc    the multigrid hierarchy on the device: patterns, symbolic products, dense bottom operators
 //   engine/engine_graph.inc        tsgo_set_graph: tables, value staging, structure re-use, where SolverMemory starts afresh, solver history across requests
 //   engine/engine_launch.inc       every kernel launch of a linearisation / a hierarchy build / a PCG iteration
@@ -35,7 +36,6 @@
 #include <string>
 #include <thread>
 #include <type_traits>
-#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -49,6 +49,7 @@
 #include "host/knobs.h"
 #include "host/parallel.h"
 #include "host/problem.h"
+#include "host/structure_index.h"
 #include "tsgo_amg_kernels.h"
 #include "tsgo_edit_kernels.h"
 #include "tsgo_gate_kernels.h"
@@ -295,11 +296,36 @@ template <typename T> struct Engine : IEngine {
         double hier_shift = 0;             // ... relative raise of the diagonal of the hierarchy's level-0 matrix: hier_shift_cfg until a breakdown
     } mem;
     SolverMemory fresh_memory() const { SolverMemory m; m.cy16 = cfg.cycle_storage != 32; m.hier_shift = hier_shift_cfg; return m; }
-    // 2. Belongs to the TABLES: reset where set_graph builds a new structure, kept by a refill.  (With the report maps, engine_report.inc, and the edge -> slot map, engine_edit.inc.)
+    // 2. Belongs to the TABLES: reset where set_graph builds a new structure, kept by a refill.
     int optimize_calls_on_tables = 0;  // tsgo_optimize calls since the tables were built (lazy hipGraph capture, see set_graph)
     hipGraphExec_t cg_graph = nullptr; // (also dropped when the cycle leaves or re-enters the packed format: it holds those kernels)
     double od_live = -1;               // live ODOM slots of this shard (the byte models'), counted once per structure (od_slots_live)
     bool schur_dev = false;            // level 0's pattern and contribution lists were built on the device (run_device_schur)
+    // Where the request's vertices and edges sit in the tables (host/structure_index.h), and the device maps the readers make of that.  Each
+    // part is built by the first call that needs it — a handle that never asks pays nothing at tsgo_set_graph — and bump-allocated behind
+    // what the graph owns; all of it goes in ONE place, drop_structure_maps(), where set_graph releases the slabs.  world == 1 handles only:
+    // every reader refuses an edge-sharded handle before it would build anything.
+    StructureIndex sindex;
+    struct StructureMaps {
+        // tsgo_edge_report (engine_report.inc): slot -> input edge of by_pose and odom, record -> input edge of the two prior lists
+        uint32_t *rep_lm_edge = nullptr, *rep_od_edge = nullptr, *rep_pp_edge = nullptr, *rep_pl_edge = nullptr;
+        ReportPartial<T>* rep_part = nullptr;      // [nbP][kEdgeClasses] of k_edge_report, then [nbL] of k_edge_report_lm_prior
+        bool rep_ready = false;
+        // tsgo_set / get_edge_information (engine_edit.inc): EdgeSlots::loc and cls on the device
+        uint32_t* edit_map = nullptr;              // [2 E]
+        uint8_t* edit_cls = nullptr;               // [E]
+        char* edit_buf = nullptr;                  // [32 E] bytes: (3 n doubles | n int64) of a set call; 3 E doubles of a get call
+        bool edit_ready = false;
+    } maps;
+    void drop_structure_maps() { sindex.clear(); maps = StructureMaps(); }
+    const VertexIndex& vertices() { return sindex.vertices(structure.v_id, pr); }
+    // null after set_error(-30, nm: ...) when the tables fail the check of build_edge_slots
+    const EdgeSlots* edges(const std::string& nm) {
+        std::string err;
+        const EdgeSlots* es = sindex.edges(pr, structure.e_type, err);
+        if (!es) set_error(-30, nm + ": " + err);
+        return es;
+    }
     // 3. Belongs to the HANDLE: never reset.  (With tsgo_robust robust, engine_launch.inc.)
     int n_fallbacks = 0, n_hier_retries = 0, n_hier_shifts = 0, n_cycle_f32_switches = 0, n_carried = 0, n_carry_dropped = 0, structure_reuses = 0;
     uint32_t paced_base = 0;           // sequence numbers grow ACROSS solves: a gate of an earlier solve that is still queued when a retry
