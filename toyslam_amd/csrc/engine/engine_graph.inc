@@ -327,6 +327,7 @@
         HIP_OK(hipHostMalloc((void**)&h_flag, 16 * sizeof(int), hipHostMallocCoherent));
         std::memset(h_flag, 0, 16 * sizeof(int));
         HIP_OK(hipHostMalloc((void**)&h_scratch, sizeof(T) * (size_t)(std::max(nbP, 2 * nbC) + nbL + 8)));
+        if (int rc = rep_reserve(std::max({(size_t)nbP, (size_t)nbC + nbL, lm_rules() ? lm_red_size() : (size_t)0}))) return rc;
         snap_ps = snap_theta = snap_lm = lm_red = nullptr;
         if (lm_rules()) {
             if (int rc = dalloc(&snap_ps, (size_t)P * 4)) return rc;

@@ -151,6 +151,18 @@
     void launch_save_x(const WarmTerms<T>& w, T* xsave, T* errpart) {
         hipLaunchKernelGGL((k_save_x<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, w.n_max, (const T*)x, zc, xsave, errpart, w);
     }
+    // k_save_x and k_pose_update in one launch (do_backsub_update under step reports)
+    void launch_save_update(const WarmTerms<T>& w, T* xsave, T* errpart, T step) {
+        hipLaunchKernelGGL((k_save_update<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, w.n_max, (const T*)x, zc, xsave, errpart, ps, theta, step, npart, w);
+    }
+    // Step reports: one-shard handles, unless TSGO_STEP_DRAINS=1 asks for copy + synchronise (host/knobs.h)
+    bool reports() const { return !step_drains && !collective() && h_rep != nullptr; }
+    // n partials at src -> the pinned report buffer, then the next sequence number into its word (k_report); wait_report(the number returned) is the host's side
+    uint64_t launch_report(const T* src, size_t n) {
+        const uint64_t seq = ++rep_seq;
+        hipLaunchKernelGGL((k_report<T>), dim3(1), dim3(kBlock), 0, stream, (int)n, src, rep_data(), reinterpret_cast<unsigned long long*>(h_rep), (unsigned long long)seq);
+        return seq;
+    }
     static int grid_for(int n, int per_thread_lanes = 1) { return std::max(1, (int)(((size_t)n * per_thread_lanes + kBlock - 1) / kBlock)); }
 
     // One Galerkin product from its pair lists (TRANS 0: T = A P; 1: A_next = P^T T, upper blocks): a lane per output block, or 8 / 16 / 64 lanes

@@ -10,10 +10,31 @@
         return 0;
     }
 
+    // The host's side of a step report (k_report): polls the report word until it holds `seq`, with do_solve_paced's pause / yield pattern
+    // and its 30 s limit — an error return, never an endless wait.  The partials are then in rep_data().
+    int wait_report(uint64_t seq) {
+        const auto w0 = std::chrono::steady_clock::now();
+        long spins = 0;
+        while (__atomic_load_n(h_rep, __ATOMIC_ACQUIRE) < seq) {
+            __builtin_ia32_pause();
+            if ((spins & 0x3f) == 0x3f) std::this_thread::yield();
+            if ((++spins & 0xfffff) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count() > 30.0)
+                return set_error(-20, "step report: the device stopped reporting (30 s without a report)");
+        }
+        return 0;
+    }
     // one linearisation; chi2 on the host
     int do_linearize(double* chi2) {
         launch_lin();
         if (int rc = allreduce(part, (size_t)pr.P * 18 + nbP)) return rc;
+        // Step reports: the chi^2 partials are final here (k_lin_pose wrote them; nothing below touches them).  Ahead of a paced solve the
+        // report leaves now: the host's wait at the end of this function is then over while k_pose_finalize, or a hierarchy build, still runs,
+        // and the solve's first launches queue up behind them.  Ahead of a burst or a replay it leaves at the end of the chain, so that the
+        // host goes on when the stream is empty, as it does after a copy + synchronise: those paths time their solves by the wall clock
+        // (do_solve_once: dev_us_per_iter) and must keep seeing the solve alone.
+        const bool report = reports(), early = report && paced();
+        uint64_t rseq = 0;
+        if (early) rseq = launch_report(part + (size_t)pr.P * 18, (size_t)nbP);
         launch_finalize();
         if (amg_on) {
             // The Galerkin hierarchy is a preconditioner, not the operator: level 0 (the Schur products, its diagonal
@@ -34,10 +55,17 @@
                 }
             }
         }
-        HIP_OK(hipMemcpyAsync(h_scratch, part + (size_t)pr.P * 18, sizeof(T) * nbP, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipStreamSynchronize(stream));
+        const T* h = h_scratch;
+        if (report) {
+            if (!early) rseq = launch_report(part + (size_t)pr.P * 18, (size_t)nbP);
+            if (int rc = wait_report(rseq)) return rc;
+            h = rep_data();
+        } else {
+            HIP_OK(hipMemcpyAsync(h_scratch, part + (size_t)pr.P * 18, sizeof(T) * nbP, hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+        }
         double s = 0;
-        for (int k = 0; k < nbP; ++k) s += (double)h_scratch[k];
+        for (int k = 0; k < nbP; ++k) s += (double)h[k];
         *chi2 = s;
         return 0;
     }
@@ -191,12 +219,13 @@
         auto since = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count(); };
         int launched = 0, seen_last = 0; long spins = 0;
         double t_last_gate = 0;        // when the newest gate was seen (or the last launch made): a healthy long solve keeps moving this
+        double t_first_gate = -1;      // when the first gate of this solve was seen
         uint64_t w = 0;
         for (;;) {
             w = __atomic_load_n(hw, __ATOMIC_ACQUIRE);      // seq << 32 | done << 31 | fail << 28 | iterations completed (k_iter_gate)
             const int32_t rel = (int32_t)((uint32_t)(w >> 32) - base);
             const int seen = rel > 0 ? (int)rel : 0;          // reports of earlier solves count as "nothing seen yet"
-            if (seen != seen_last) { seen_last = seen; t_last_gate = since(); }
+            if (seen != seen_last) { seen_last = seen; t_last_gate = since(); if (t_first_gate < 0) t_first_gate = t_last_gate; }
             if (seen > 0 && ((w >> 31) & 1)) break;
             if (launched - seen < pace_lead) {
                 if (launched > cfg.pcg_max_iters + 4) { paced_base = base + (uint32_t)launched; return set_error(-20, "PCG did not terminate"); }
@@ -210,7 +239,9 @@
         }
         paced_base = base + (uint32_t)launched;
         solve_done((int)(w & 0x0fffffffu), (int)((w >> 28) & 7), iters, fail);
-        const double wall = since();
+        // Under step reports the linearisation's last kernels, or a hierarchy build, may still have been running when this solve was enqueued:
+        // its time per iteration is counted from its first gate (n iterations lie between the first gate and the one that reports `done`)
+        const double wall = since() - (reports() && t_first_gate > 0 ? t_first_gate : 0.0);
         if (timing) std::fprintf(stderr, "[tsgo] solve (paced): %d iterations launched, done reported after %d at %.0f us\n", launched, *iters, wall);
         // a host that cannot stay ahead shows as iterations that take longer than the burst path measured: then the handle goes over to replay
         if (cfg.use_graphs == 2 && *iters >= 8 && !*fail && mem.ref_us_per_iter > 0 && !hook_force_paced) {
@@ -280,15 +311,19 @@
 
     // landmarks: dl = u - Dl^-1 W^T x (+ optional update); poses: update.  Returns ||delta_p||^2 (identical on every
     // rank: pose vectors are replicated) and THIS rank's ||delta_l||^2 (landmark deltas are shard-local).
-    int do_backsub_update(T step, double* np2_out, double* nl2_local_out) {
+    // Step reports (one-shard handles): a step that is taken runs k_save_x and k_pose_update as ONE launch in front of the landmark pass (which
+    // reads zc and lmrec, neither ps nor theta), the partials come back through k_report, and `after` (the step's closing event) is recorded behind it.
+    int do_backsub_update(T step, double* np2_out, double* nl2_local_out, hipEvent_t after = nullptr) {
         const int P = pr.P;
+        const bool report = reports(), fused = report && step != T(0);
         if (step != T(0)) {
             std::rotate(hist, hist + kMaxWarm - 1, hist + kMaxWarm);      // the oldest buffer takes this delta; hist[1..] are the deltas before it
             WarmTerms<T> w{};
             warm_coefficients(w);
             for (int j = 0; j + 1 < kMaxWarm; ++j) w.v[j] = hist[j + 1];
             w.n_max = std::min({mem.n_prev, (int)cfg.warm_start, kMaxWarm - 1});      // orders that can be tested on this delta
-            launch_save_x(w, hist[0], warm_err);
+            if (fused) launch_save_update(w, hist[0], warm_err, step);
+            else launch_save_x(w, hist[0], warm_err);
             mem.n_tested = w.n_max; mem.have_prev = true; mem.n_prev = std::min(mem.n_prev + 1, kMaxWarm);
         } else {      // a probe (step 0) leaves nothing to carry over
             launch_pack_x(WarmTerms<T>{}, (int*)nullptr);
@@ -297,13 +332,21 @@
         if (tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
             launch_table(k_schur_lm<T, g, 1, 0>, nbL, tl, 0, st[0], (const T*)ninv, (const T*)nullptr, (const T*)nullptr, tl, (const T*)zc, lmrec, tvec, step, dl, npart + nbC, (const float*)nullptr, (float*)nullptr, no_gate(), T(0), (T*)nullptr);
         });
-        hipLaunchKernelGGL((k_pose_update<T>), dim3(nbC), dim3(kBlock), 0, stream, P, x, ps, theta, step, npart);
+        if (!fused) hipLaunchKernelGGL((k_pose_update<T>), dim3(nbC), dim3(kBlock), 0, stream, P, x, ps, theta, step, npart);
         const int nl = tl.n_slices > 0 ? nbL : 0;
-        HIP_OK(hipMemcpyAsync(h_scratch, npart, sizeof(T) * (size_t)(nbC + nl), hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipStreamSynchronize(stream));
+        const T* h = h_scratch;
+        if (report) {
+            const uint64_t rseq = launch_report(npart, (size_t)(nbC + nl));
+            if (after) HIP_OK(hipEventRecord(after, stream));
+            if (int rc = wait_report(rseq)) return rc;
+            h = rep_data();
+        } else {
+            HIP_OK(hipMemcpyAsync(h_scratch, npart, sizeof(T) * (size_t)(nbC + nl), hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+        }
         double np2 = 0, nl2 = 0;
-        for (int k = 0; k < nbC; ++k) np2 += (double)h_scratch[k];
-        for (int k = 0; k < nl; ++k) nl2 += (double)h_scratch[nbC + k];
+        for (int k = 0; k < nbC; ++k) np2 += (double)h[k];
+        for (int k = 0; k < nl; ++k) nl2 += (double)h[nbC + k];
         *np2_out = np2; *nl2_local_out = nl2;
         return 0;
     }
@@ -330,7 +373,7 @@
     // estimates, back-substitution + update with step 1 (the landmarks' predicted decrease in the same pass, k_schur_lm<.., 2>; the poses'
     // in k_pose_update_lm), chi^2 at the trial point (k_chi2).  Nothing of the step enters the warm start's history: a full step leaves
     // no remainder to start from, and a rejected one must leave nothing at all.
-    int do_lm_step(double lam, double* np2, double* nl2, double* pred, double* chi2_trial) {
+    int do_lm_step(double lam, double* np2, double* nl2, double* pred, double* chi2_trial, hipEvent_t after = nullptr) {
         const int P = pr.P, L = pr.L, nl = lm_nl();
         T* norm_p = lm_red; T* norm_l = lm_red + nbC; T* pred_p = norm_l + nl; T* pred_l = pred_p + nbC; T* chi = pred_l + nl;
         launch(k_lm_state<T, 0>, grid_for(std::max(P, L)), P, L, ps, theta, lmrec, snap_ps, snap_theta, snap_lm);
@@ -342,9 +385,17 @@
         launch(k_pose_update_lm<T>, nbC, P, (const T*)x, ps, theta, (const T*)part, (T)lam, norm_p, pred_p);
         launch_chi2(chi);
         const size_t n = (size_t)2 * (nbC + nl) + nbP;
-        HIP_OK(hipMemcpyAsync(h_lm, lm_red, sizeof(T) * n, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipStreamSynchronize(stream));
-        auto sum = [&](size_t from, int count) { double v = 0; for (int k = 0; k < count; ++k) v += (double)h_lm[from + k]; return v; };
+        const T* h = h_lm;
+        if (reports()) {      // (the trial keeps its own kernels: k_pack_x takes no history and k_pose_update_lm reads the gradient as well)
+            const uint64_t rseq = launch_report(lm_red, n);
+            if (after) HIP_OK(hipEventRecord(after, stream));
+            if (int rc = wait_report(rseq)) return rc;
+            h = rep_data();
+        } else {
+            HIP_OK(hipMemcpyAsync(h_lm, lm_red, sizeof(T) * n, hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+        }
+        auto sum = [&](size_t from, int count) { double v = 0; for (int k = 0; k < count; ++k) v += (double)h[from + k]; return v; };
         *np2 = sum(0, nbC); *nl2 = sum(nbC, nl);
         *pred = sum((size_t)nbC + nl, nbC) + sum((size_t)2 * nbC + nl, nl);
         *chi2_trial = sum((size_t)2 * (nbC + nl), nbP);
@@ -354,14 +405,34 @@
         launch(k_lm_state<T, 1>, grid_for(std::max(pr.P, pr.L)), pr.P, pr.L, ps, theta, lmrec, snap_ps, snap_theta, snap_lm);
         return 0;
     }
-    int end_step_timing(tsgo_stats& s) {      // ev[0..2] stand before a step's linearisation, solve and update: closes the update, waits, adds the device times
+    int add_step_times(hipEvent_t* e, tsgo_stats& s) {
         float ms = 0;
-        HIP_OK(hipEventRecord(ev[3], stream));
-        HIP_OK(hipEventSynchronize(ev[3]));
-        HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1])); s.ms_linearize += ms;
-        HIP_OK(hipEventElapsedTime(&ms, ev[1], ev[2])); s.ms_solve += ms;
-        HIP_OK(hipEventElapsedTime(&ms, ev[2], ev[3])); s.ms_update += ms;
+        HIP_OK(hipEventElapsedTime(&ms, e[0], e[1])); s.ms_linearize += ms;
+        HIP_OK(hipEventElapsedTime(&ms, e[1], e[2])); s.ms_solve += ms;
+        HIP_OK(hipEventElapsedTime(&ms, e[2], e[3])); s.ms_update += ms;
         return 0;
+    }
+    // evc[0..2] stand before a step's linearisation, solve and update.  Copy + synchronise: closes the update, waits, adds the device times.
+    // Step reports: evc[3] already stands behind the report the host has seen (do_backsub_update / do_lm_step), and no second wait is
+    // spent on it: the set is read at the end of the NEXT step, when its events lie a whole step back in the stream, while that step
+    // records the other set; the last step's set is read by flush_step_timing, once per tsgo_optimize.
+    hipEvent_t step_end_event() const { return reports() ? evc[3] : (hipEvent_t) nullptr; }
+    int end_step_timing(tsgo_stats& s) {
+        if (!reports()) {
+            HIP_OK(hipEventRecord(evc[3], stream));
+            HIP_OK(hipEventSynchronize(evc[3]));
+            return add_step_times(evc, s);
+        }
+        if (ev_pending) { if (int rc = add_step_times(ev_pending, s)) return rc; }
+        ev_pending = evc; evc = evc == ev ? ev_b : ev;
+        return 0;
+    }
+    int flush_step_timing(tsgo_stats& s) {
+        hipEvent_t* e = ev_pending;
+        ev_pending = nullptr; evc = ev;
+        if (!e) return 0;
+        HIP_OK(hipEventSynchronize(e[3]));      // (it stands right behind a report that has arrived)
+        return add_step_times(e, s);
     }
     // The loop.  One trial = linearise (H + lambda I, b zeroed at fixed vertices), solve, tentative full step, decide; a rejected trial is
     // followed by a fresh linearisation at the restored point: lambda is baked into the landmark inverses and the pose diagonals.
@@ -369,22 +440,22 @@
         double lam = std::min(std::max(cfg.lm_lambda0, kLmLambdaMin), kLmLambdaMax), nu = 2;
         for (int it = 0; it < iterations; ++it) {
             double err = 0;
-            HIP_OK(hipEventRecord(ev[0], stream));
+            HIP_OK(hipEventRecord(evc[0], stream));
             lambda = lam;
             if (int rc = do_linearize(&err)) return rc;
-            HIP_OK(hipEventRecord(ev[1], stream));
+            HIP_OK(hipEventRecord(evc[1], stream));
             const bool traced = it < TSGO_MAX_TRACE;
             if (traced) { s.chi2[it] = err; s.lm_lambda[it] = lam; }
             s.chi2_last = err; s.lambda_last = lam;
             s.iterations_run = it + 1; s.trace_len = std::min(it + 1, TSGO_MAX_TRACE);
             int cg = 0, fail = 0;
             if (int rc = do_solve(&cg, &fail)) return rc;
-            HIP_OK(hipEventRecord(ev[2], stream));
+            HIP_OK(hipEventRecord(evc[2], stream));
             if (traced) s.pcg_iters[it] = cg;
             s.pcg_iters_total += cg;
             if (fail != 0) { s.stop_reason = TSGO_STOP_SOLVER; break; }
             double np2 = 0, nl2 = 0, pred = 0, trial = 0;
-            if (int rc = do_lm_step(lam, &np2, &nl2, &pred, &trial)) return rc;
+            if (int rc = do_lm_step(lam, &np2, &nl2, &pred, &trial, step_end_event())) return rc;
             if (int rc = end_step_timing(s)) return rc;
             s.last_delta_norm = std::sqrt(np2 + nl2);
             const double gain = pred != 0 ? (err - trial) / pred : 0.0;
@@ -400,7 +471,7 @@
                 lam *= nu; nu *= 2;
             }
         }
-        return 0;
+        return flush_step_timing(s);
     }
 
     // rules 0 and 1: Gauss-Newton with the reference's stop rules (OptimizerCpu.h:80-180 / graph_optimizer.py:24-92)
@@ -414,7 +485,7 @@
         const double step = step_scale();
         for (int it = 0; it < iterations; ++it) {
             double err = 0;
-            HIP_OK(hipEventRecord(ev[0], stream));
+            HIP_OK(hipEventRecord(evc[0], stream));
             if (py_rules()) {
                 // lambda follows the chi^2 of THIS linearisation (:41-42), which the linearisation itself needs: it is run with the
                 // value a non-increasing chi^2 gives (the common case) and repeated with the other one when chi^2 did rise
@@ -426,7 +497,7 @@
                 lambda = 0;
                 if (int rc = do_linearize(&err)) return rc;
             }
-            HIP_OK(hipEventRecord(ev[1], stream));
+            HIP_OK(hipEventRecord(evc[1], stream));
             if (it < TSGO_MAX_TRACE) s.chi2[it] = err;
             s.chi2_last = err;
             s.iterations_run = it + 1; s.trace_len = std::min(it + 1, TSGO_MAX_TRACE);
@@ -437,12 +508,12 @@
             }
             int cg = 0, fail = 0;
             if (int rc = do_solve(&cg, &fail)) return rc;
-            HIP_OK(hipEventRecord(ev[2], stream));
+            HIP_OK(hipEventRecord(evc[2], stream));
             if (it < TSGO_MAX_TRACE) s.pcg_iters[it] = cg;
             s.pcg_iters_total += cg;
             if (fail != 0) { s.stop_reason = TSGO_STOP_SOLVER; break; }       // breakdown, or pcg_max_iters reached without convergence: no step is taken
             double np2 = 0, nl2 = 0;
-            if (int rc = do_backsub_update((T)step, &np2, &nl2)) return rc;   // :159-165 / graph_optimizer.py:66-75
+            if (int rc = do_backsub_update((T)step, &np2, &nl2, step_end_event())) return rc;   // :159-165 / graph_optimizer.py:66-75
             if (int rc = end_step_timing(s)) return rc;
             nl2_whole = !collective();
             const bool last = it + 1 == iterations;
@@ -463,7 +534,7 @@
             if (int rc = landmark_norm_allreduce(&nl2_last)) return rc;
             s.last_delta_norm = (py_rules() ? step : 1.0) * std::sqrt(np2_last + nl2_last);
         }
-        return 0;
+        return flush_step_timing(s);
     }
 
     int optimize(int iterations, tsgo_stats* out) override {
@@ -485,6 +556,7 @@
         const int fallbacks0 = n_fallbacks, dropped0 = n_carry_dropped;
         const bool started_carried = mem.carried;
         replayed = false;
+        ev_pending = nullptr; evc = ev;      // (a call that ended in an error may have left a set unread)
         s.stop_reason = TSGO_STOP_CAP;
         const auto wall0 = std::chrono::steady_clock::now();
         if (int rc = lm_rules() ? lm_loop(iterations, s) : gn_loop(iterations, s)) return rc;

@@ -25,3 +25,9 @@
 #else
 #define TSGO_CYCLE_VEC64() false
 #endif
+
+// The A/B switch of how the host thread follows the device through a Gauss-Newton step (engine/engine_solve.inc).
+// It changes no result: every build reads it, once per handle (tsgo_create), so that the product library can be measured both ways.
+//   TSGO_STEP_DRAINS=1  chi^2 and ||delta|| come back by copy command + stream synchronisation, k_save_x and k_pose_update are two launches
+//                       (default: the device reports them into pinned memory, k_report, and the host polls; one launch, k_save_update)
+inline bool tsgo_step_drains() { const char* e = std::getenv("TSGO_STEP_DRAINS"); return e && std::atoi(e) != 0; }

@@ -265,6 +265,12 @@ template <typename T> struct Engine : IEngine {
     CgState<T>* h_state = nullptr;     // pinned
     int* h_flag = nullptr;             // pinned, coherent: what the gate of the last launched iteration saw (k_iter_gate, do_solve_paced)
     T* h_scratch = nullptr;            // pinned, partial sums
+    // Step reports (one-shard handles; k_report, engine_solve.inc: wait_report): the device stores chi^2 / ||delta|| partials into h_rep
+    // and then a sequence number into its first word; the host thread polls that word instead of draining the stream.  Pinned, coherent;
+    // one cache line for the word, the partials behind it.  Sized by the largest graph the handle has seen, freed with the handle.
+    uint64_t* h_rep = nullptr; size_t rep_cap = 0;
+    static constexpr size_t kRepHead = 64 / sizeof(T);      // the word's cache line, in elements of T
+    T* rep_data() const { return reinterpret_cast<T*>(h_rep) + kRepHead; }
     // rules = 2 only (null otherwise): the estimates before a trial's step (k_lm_state), and the partials one trial brings back in one copy:
     // lm_red = [ |d_p|^2 (nbC) | |d_l|^2 (nbL) | pred, poses (nbC) | pred, landmarks (nbL) | chi^2 at the trial point (nbP) ], h_lm its pinned twin
     T *snap_ps = nullptr, *snap_theta = nullptr, *snap_lm = nullptr, *lm_red = nullptr, *h_lm = nullptr;
@@ -273,6 +279,9 @@ template <typename T> struct Engine : IEngine {
     double hier_shift_cfg = 0;         // the hier_shift a graph starts with (0; research: TSGO_HIER_SHIFT)
     bool fold_gate = true;             // the stopping rule in workgroup 0 of the iteration's first product (research: TSGO_FOLD_GATE=0 = its own kernel)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // step reports: a second set, so that a step's device times are read while the next step runs (end_step_timing); evc = the set being recorded
+    hipEvent_t ev_b[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t* evc = ev; hipEvent_t* ev_pending = nullptr;
     static constexpr int kDecideSolves = 3;
     bool replayed = false;             // the last tsgo_optimize replayed captured iterations (tsgo_stats.graph_replay)
     // ---- What the solver learns while it runs has one of three lifetimes; a new member goes into one of the three groups.
@@ -328,6 +337,7 @@ template <typename T> struct Engine : IEngine {
     }
     // 3. Belongs to the HANDLE: never reset.  (With tsgo_robust robust, engine_launch.inc.)
     int n_fallbacks = 0, n_hier_retries = 0, n_hier_shifts = 0, n_cycle_f32_switches = 0, n_carried = 0, n_carry_dropped = 0, structure_reuses = 0;
+    uint64_t rep_seq = 0;              // step reports sent so far (64 bits, per handle: no wrap-around path)
     uint32_t paced_base = 0;           // sequence numbers grow ACROSS solves: a gate of an earlier solve that is still queued when a retry
                                        // starts the next one (pace_lead > 1, hierarchy / block-Jacobi repeats) reports a number <= base and is ignored
     // (these two survive tsgo_set_graph while the counters that derive them — n_decided, n_slow_seen, n_host_slow, n_paced_slow — do not)
@@ -384,6 +394,7 @@ template <typename T> struct Engine : IEngine {
     bool hook_force_host_slow = false;         // TSGO_FORCE_HOST_SLOW: the handle believes its host thread is too slow for eager launches
     bool hook_force_paced = false;             // TSGO_FORCE_PACED: paced eager launches from the first solve on (no timing heuristics)
     int pace_lead = kPaceLead;                 // TSGO_PACE_LEAD: iterations enqueued ahead of the gate that has reported
+    bool step_drains = false;                  // TSGO_STEP_DRAINS=1 (every build, host/knobs.h; same results): copy + synchronise instead of device reports
     explicit Engine(const tsgo_config& c) : cfg(c) {
         say_env = c.verbose || getenv("TSGO_VERBOSE") != nullptr;
         solve_timing = getenv("TSGO_SOLVE_TIMING") != nullptr;
@@ -403,10 +414,11 @@ template <typename T> struct Engine : IEngine {
         hook_inject_amg_failure = TSGO_RESEARCH_ENV("TSGO_INJECT_AMG_FAILURE") != nullptr;
         hook_force_host_slow = TSGO_RESEARCH_ENV("TSGO_FORCE_HOST_SLOW") != nullptr;
         hook_force_paced = TSGO_RESEARCH_ENV("TSGO_FORCE_PACED") != nullptr;
+        step_drains = tsgo_step_drains();
         mem = fresh_memory();
     }
 
-    ~Engine() override { release(); for (Slab& sl : slabs) (void)hipFree(sl.base); if (carry_dev) (void)hipFree(carry_dev); if (stage) (void)hipHostFree(stage); if (stream) (void)hipStreamDestroy(stream); if (stream2) (void)hipStreamDestroy(stream2); for (auto& e : ev) if (e) (void)hipEventDestroy(e); for (auto& m : prof) (void)hipEventDestroy(m.e); }
+    ~Engine() override { release(); for (Slab& sl : slabs) (void)hipFree(sl.base); if (carry_dev) (void)hipFree(carry_dev); if (stage) (void)hipHostFree(stage); if (h_rep) (void)hipHostFree(h_rep); if (stream) (void)hipStreamDestroy(stream); if (stream2) (void)hipStreamDestroy(stream2); for (auto& e : ev) if (e) (void)hipEventDestroy(e); for (auto& e : ev_b) if (e) (void)hipEventDestroy(e); for (auto& m : prof) (void)hipEventDestroy(m.e); }
 
     void release() {
         if (amg_builder.joinable()) amg_builder.join();
@@ -429,11 +441,24 @@ template <typename T> struct Engine : IEngine {
         return 0;
     }
 
+    // The report buffer survives release() like the staging buffer: n elements of T behind the word's cache line.  A larger graph gets a
+    // larger buffer; nothing is in flight into the old one (every report is waited for), the synchronisation is for error paths.
+    int rep_reserve(size_t n) {
+        if (h_rep && n <= rep_cap) return 0;
+        if (h_rep) { HIP_OK(hipStreamSynchronize(stream)); (void)hipHostFree(h_rep); h_rep = nullptr; rep_cap = 0; }
+        n += n / 4;
+        HIP_OK(hipHostMalloc((void**)&h_rep, (kRepHead + n) * sizeof(T), hipHostMallocCoherent));
+        std::memset(h_rep, 0, kRepHead * sizeof(T));      // (rep_seq keeps counting: the next report's number is above anything the word has held)
+        rep_cap = n;
+        return 0;
+    }
+
     int init() {
         HIP_OK(hipSetDevice(cfg.device));
         HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         HIP_OK(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
         for (auto& e : ev) HIP_OK(hipEventCreate(&e));
+        for (auto& e : ev_b) HIP_OK(hipEventCreate(&e));
         return 0;
     }
 

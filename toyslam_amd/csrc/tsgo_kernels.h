@@ -812,8 +812,7 @@ __global__ __launch_bounds__(kBlock) void k_pack_x(int P, int n_max, int n_teste
 // The solved delta x -> zc[.][0..2] and -> xsave (the newest entry of the warm start's history), and what every order would
 // have made of predicting it from the deltas before it (w.v, newest first; orders 1..w.n_max): errpart[m-1][block].
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_save_x(int P, int n_max, const T* __restrict__ x, T* __restrict__ zc, T* __restrict__ xsave, T* __restrict__ errpart, const WarmTerms<T> w) {      // (n_max: w's, in the plain head; read from there alone)
-    __shared__ T red[kWavesPerBlock];
+__device__ __forceinline__ void save_x_body(int P, int n_max, const T* __restrict__ x, T* __restrict__ zc, T* __restrict__ xsave, T* __restrict__ errpart, const WarmTerms<T>& w, T* red) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     T err[kMaxWarm];
 #pragma unroll
@@ -842,6 +841,11 @@ __global__ __launch_bounds__(kBlock) void k_save_x(int P, int n_max, const T* __
         const T total = block_sum<T>(err[m], red);
         if (threadIdx.x == 0) errpart[(size_t)m * gridDim.x + blockIdx.x] = total;
     }
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_save_x(int P, int n_max, const T* __restrict__ x, T* __restrict__ zc, T* __restrict__ xsave, T* __restrict__ errpart, const WarmTerms<T> w) {      // (n_max: w's, in the plain head; read from there alone)
+    __shared__ T red[kWavesPerBlock];
+    save_x_body<T>(P, n_max, x, zc, xsave, errpart, w, red);
 }
 
 // History across requests (tsgo_config.warm_requests): a delta of the previous graph, in ITS pose numbering, into this graph's —
@@ -897,9 +901,7 @@ __global__ __launch_bounds__(kBlock) void k_warm_scale(int n, const T* b_part, c
 // pose (+)= step * delta: VertexSe2::Update (remote/graph/vertex/VertexSe2.h:16-27) with the 0.2 of
 // OptimizerCpu.h:164 — theta = atan2(sin, cos) + step*dth, translation added in the world frame.
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_pose_update(int P, const T* __restrict__ x, T* __restrict__ ps,
-                                                        T* __restrict__ theta, T step, T* __restrict__ norm_part) {
-    __shared__ T red[kWavesPerBlock];
+__device__ __forceinline__ void pose_update_body(int P, const T* __restrict__ x, T* __restrict__ ps, T* __restrict__ theta, T step, T* __restrict__ norm_part, T* red) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     T nrm = 0;
     if (i < P) {
@@ -914,6 +916,35 @@ __global__ __launch_bounds__(kBlock) void k_pose_update(int P, const T* __restri
     }
     const T total = block_sum<T>(nrm, red);
     if (threadIdx.x == 0) norm_part[blockIdx.x] = total;
+}
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_pose_update(int P, const T* __restrict__ x, T* __restrict__ ps,
+                                                        T* __restrict__ theta, T step, T* __restrict__ norm_part) {
+    __shared__ T red[kWavesPerBlock];
+    pose_update_body<T>(P, x, ps, theta, step, norm_part, red);
+}
+
+// k_save_x and k_pose_update in one launch (one-shard handles, a step that is taken): both are thread = pose over the same grid and read the
+// same x, and the landmark back-substitution that used to run between them reads zc and lmrec, neither ps nor theta.  The two bodies are
+// the two kernels' own, one after the other: every partial keeps its slot and its bits.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_save_update(int P, int n_max, const T* __restrict__ x, T* __restrict__ zc, T* __restrict__ xsave, T* __restrict__ errpart,
+                                                        T* __restrict__ ps, T* __restrict__ theta, T step, T* __restrict__ norm_part, const WarmTerms<T> w) {
+    __shared__ T red[kWavesPerBlock];
+    save_x_body<T>(P, n_max, x, zc, xsave, errpart, w, red);
+    pose_update_body<T>(P, x, ps, theta, step, norm_part, red);
+}
+
+// Step report (Engine::launch_report / wait_report): ONE workgroup copies n partials into pinned host memory with plain coalesced
+// stores, fences at system scope, and one lane then publishes the report's 64-bit sequence number with a system-scope release store,
+// the form in which iter_gate_body publishes a gate.  The host thread polls the word and then sums the partials in the order it
+// always did.  The kernel waits for nothing.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_report(int n, const T* __restrict__ src, T* __restrict__ host_dst, unsigned long long* host_word, unsigned long long seq) {
+    for (int k = threadIdx.x; k < n; k += kBlock) host_dst[k] = src[k];
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(host_word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 }  // namespace tsgo
