@@ -451,6 +451,60 @@ int tsgo_set_edge_information(tsgo_optimizer* opt, int64_t n, const int64_t* edg
                               tsgo_edge_info_stats* stats /* may be NULL */);
 int tsgo_get_edge_information(tsgo_optimizer* opt, double* e_inf_out, int64_t cap_edges);
 
+/* Graduated non-convexity with the truncated-least-squares surrogate (Yang, Antonante, Tzoumas, Carlone 2020; GTSAM's GncOptimizer with
+ * known inliers): the outer loop for a graph whose start cannot be trusted, where an M-estimator of tsgo_set_robust
+ * only helps near the optimum.  Every round re-evaluates every edge on the device, turns its squared residual into a weight in [0, 1] and
+ * scatters weight * base information into the tables (what tsgo_edge_report, host arithmetic and tsgo_set_edge_information would do in
+ * three calls and two transfers), then runs the handle's own tsgo_optimize.
+ *   Base information: what the handle holds when the call starts (tsgo_get_edge_information).  s = sum_k base_k e_k^2 of an edge never
+ *   depends on the weight the tables hold at that moment.  A dormant edge (base 0) has s = 0, w = 1 and stays dormant.
+ *   Subject edges: barc2[e_type] > 0 and (subject == NULL or subject[e] != 0); n_mask must equal n_edges when a mask is given.  Every other
+ *   edge is exempt (a known inlier): w = 1, and its information is never written.  Without known inliers nothing anchors the first rounds
+ *   (all weights start small together): mask the edges that are trusted, typically the odometry chain.
+ *   The loop: a probe pass finds q_max = max over subject edges of s / barc2[class].  2 q_max - 1 <= 0: nothing is written, rounds = 0,
+ *   TSGO_GNC_ALL_INLIERS.  Otherwise mu = 1 / (2 q_max - 1), and each round
+ *     reweights   q = s / barc2:  w = 1 when q <= mu / (mu + 1), w = 0 when q >= (mu + 1) / mu, else w = sqrt(mu (mu + 1) / q) - mu (f64, in
+ *                 that form); the tables receive w * base_k on the axes the class uses;
+ *     invalidates as tsgo_set_edge_information does (the next linearisation builds a fresh multigrid hierarchy; the history stays);
+ *     optimises   tsgo_optimize(inner_iterations) under the handle's own rules, odom_jacobian and robust setting.  The call does NOT touch
+ *                 the robust setting: textbook GNC is tsgo_set_robust with NONE on every class, set by the caller beforehand;
+ *     stops       with TSGO_GNC_BINARY when every subject weight of this round was 0 or 1, with TSGO_GNC_SOLVER when the inner run ended
+ *                 with TSGO_STOP_SOLVER, with TSGO_GNC_ROUNDS after rounds_max rounds; otherwise mu *= mu_step.
+ *   keep_weights = 1: on return the tables hold w * base of the last round (a later tsgo_set_graph replaces them, as after an edit).
+ *   keep_weights = 0: the base information is restored bit for bit; the estimates stay where the loop left them.
+ * w_out (may be NULL) receives the last round's weight of every edge in input order, 1 for exempt edges (all 1 after ALL_INLIERS).
+ * precision 64 only.  Errors (< 0, text in tsgo_last_error; everything is validated before anything is launched, the handle is exactly as
+ * before): a NULL handle or params; no graph set; n_mask != n_edges with a mask given; cap_edges < n_edges with w_out given; mu_step not
+ * finite or <= 1; rounds_max outside [1, TSGO_GNC_MAX_ROUNDS]; inner_iterations < 0; a barc2 that is not finite; keep_weights not 0 or 1;
+ * no subject edge; precision = 32; an edge-sharded handle (world > 1). */
+#define TSGO_GNC_MAX_ROUNDS 128
+enum { TSGO_GNC_ALL_INLIERS = 0, TSGO_GNC_BINARY = 1, TSGO_GNC_ROUNDS = 2, TSGO_GNC_SOLVER = 3 };
+typedef struct tsgo_gnc_params {
+    double  barc2[5];           /* indexed by tsgo_graph.e_type: inlier threshold on s; <= 0: the class is exempt.  Defaults: the 99 % chi^2
+                                   quantiles of tsgo_gate_edges, 11.345 for types 0 and 3 (3 dof), 9.210 for types 1, 2 and 4 (2 dof) */
+    double  mu_step;            /* > 1; default 1.4 */
+    int32_t rounds_max;         /* 1 .. TSGO_GNC_MAX_ROUNDS; default 64 */
+    int32_t inner_iterations;   /* tsgo_optimize's `iterations` of every round; default 10.  0: the round reweights only */
+    int32_t keep_weights;       /* 1 (default) or 0 */
+    int32_t reserved;           /* 0 */
+} tsgo_gnc_params;
+typedef struct tsgo_gnc_stats {
+    int32_t rounds, stop_reason;                          /* rounds run; TSGO_GNC_* */
+    double  q_max;                                        /* of the probe pass */
+    double  mu[TSGO_GNC_MAX_ROUNDS];                      /* per round: the control parameter, */
+    double  cost[TSGO_GNC_MAX_ROUNDS];                    /* ... sum of w s over subject edges at the reweighting point, */
+    double  chi2_inner[TSGO_GNC_MAX_ROUNDS];              /* ... tsgo_stats.chi2_last of the inner run (0 with inner_iterations = 0), */
+    int32_t inner_iterations_run[TSGO_GNC_MAX_ROUNDS];    /* ... its iterations_run */
+    int32_t inner_stop[TSGO_GNC_MAX_ROUNDS];              /* ... and stop_reason (TSGO_STOP_*), */
+    int64_t n_zero[TSGO_GNC_MAX_ROUNDS], n_one[TSGO_GNC_MAX_ROUNDS], n_between[TSGO_GNC_MAX_ROUNDS];   /* ... subject weights = 0, = 1, in between */
+    int64_t subject_by_class[5];                          /* subject edges per tsgo_graph.e_type */
+    int64_t pcg_iters_total;                              /* over all inner runs */
+    double  ms_total, ms_reweight, ms_inner;              /* whole call; hipEvent time of the reweighting passes (probe included); wall time of the inner runs */
+} tsgo_gnc_stats;
+void tsgo_default_gnc(tsgo_gnc_params* p);                /* host-only too */
+int tsgo_gnc(tsgo_optimizer* opt, const tsgo_gnc_params* params, const uint8_t* subject /* may be NULL */, int64_t n_mask,
+             double* w_out /* 1 per edge, may be NULL */, int64_t cap_edges, tsgo_gnc_stats* stats /* may be NULL */);
+
 const char* tsgo_last_error(void);
 
 /* ---- host-only: wire codec (libtsgo_host.so and libtsgo_hip.so) ---------------------------------

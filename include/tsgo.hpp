@@ -242,6 +242,29 @@ public:
         if (tsgo_get_edge_information(handle, inf.empty() ? nullptr : inf.data(), n)) throw std::runtime_error(tsgo_last_error());
         return inf;
     }
+    // Graduated non-convexity, truncated least squares (tsgo_gnc), on the graph last handed to Optimize or SetGraph: rounds of on-device
+    // reweighting and Optimize-style inner runs under the handle's own rules and robust setting (textbook GNC: SetRobust NONE on every
+    // class first).  params: DefaultGnc() adjusted; subject: empty = every edge of a class with barc2 > 0, otherwise one byte per edge
+    // (nonzero = may be down-weighted; the others are known inliers).  Returns the last round's weight of every edge (1 for exempt ones);
+    // the graph's positions are updated in place when `graph` is given.  Throws on an error (no graph yet, a mask of the wrong length, a
+    // parameter out of range, no subject edge, precision 32, an edge-sharded handle).
+    static tsgo_gnc_params DefaultGnc() { tsgo_gnc_params p; tsgo_default_gnc(&p); return p; }
+    std::vector<double> Gnc(const tsgo_gnc_params& params, const std::vector<uint8_t>& subject = std::vector<uint8_t>(), Graph* graph = nullptr,
+                            tsgo_gnc_stats* stats = nullptr) {
+        tsgo_edge_report_stats s;
+        if (tsgo_edge_report(handle, nullptr, 0, &s)) throw std::runtime_error(tsgo_last_error());
+        int64_t n = 0;
+        for (const tsgo_edge_class_summary& c : s.cls) n += c.edges;
+        std::vector<double> w((size_t)n, 1.0);
+        if (tsgo_gnc(handle, &params, subject.empty() ? nullptr : subject.data(), (int64_t)subject.size(), w.empty() ? nullptr : w.data(), n, stats))
+            throw std::runtime_error(tsgo_last_error());
+        if (graph) {
+            std::vector<double> out(graph->VertexCount() * 3);
+            if (tsgo_get_vertices(handle, out.data())) throw std::runtime_error(tsgo_last_error());
+            graph->SetPositions(out);
+        }
+        return w;
+    }
     // Hands the graph to the handle without optimising it (what InitEstimates, EdgeReport or GateEdges need before a first Optimize).
     void SetGraph(const Graph& graph) {
         const tsgo_graph g = graph.View();

@@ -64,6 +64,23 @@ class tsgo_edge_info_stats(C.Structure):
                 ("ms_total", C.c_double), ("ms_host", C.c_double), ("ms_device", C.c_double)]
 
 
+TSGO_GNC_MAX_ROUNDS = 128
+GNC_STOP = {0: "all_inliers", 1: "binary", 2: "rounds", 3: "solver_failed"}      # TSGO_GNC_*
+
+
+class tsgo_gnc_params(C.Structure):
+    _fields_ = [("barc2", C.c_double * 5), ("mu_step", C.c_double), ("rounds_max", C.c_int32), ("inner_iterations", C.c_int32),
+                ("keep_weights", C.c_int32), ("reserved", C.c_int32)]
+
+
+class tsgo_gnc_stats(C.Structure):
+    _R = TSGO_GNC_MAX_ROUNDS
+    _fields_ = [("rounds", C.c_int32), ("stop_reason", C.c_int32), ("q_max", C.c_double), ("mu", C.c_double * _R), ("cost", C.c_double * _R),
+                ("chi2_inner", C.c_double * _R), ("inner_iterations_run", C.c_int32 * _R), ("inner_stop", C.c_int32 * _R),
+                ("n_zero", C.c_int64 * _R), ("n_one", C.c_int64 * _R), ("n_between", C.c_int64 * _R), ("subject_by_class", C.c_int64 * 5),
+                ("pcg_iters_total", C.c_int64), ("ms_total", C.c_double), ("ms_reweight", C.c_double), ("ms_inner", C.c_double)]
+
+
 ROBUST_KERNELS = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}      # TSGO_ROBUST_*
 ROBUST_CLASSES = ("odom", "lm", "virtual", "pose_prior", "lm_prior")            # = tsgo_graph.e_type 0 .. 4
 
@@ -96,13 +113,13 @@ class tsgo_amg_info(C.Structure):
                 ("agg_min", C.c_int32 * 8), ("agg_max", C.c_int32 * 8), ("checksum", C.c_uint64)]
 
 
-HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_last_error", "tsgo_wire_decode", "tsgo_wire_new", "tsgo_wire_decode_into", "tsgo_wire_view", "tsgo_wire_free",
+HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_default_gnc", "tsgo_last_error", "tsgo_wire_decode", "tsgo_wire_new", "tsgo_wire_decode_into", "tsgo_wire_view", "tsgo_wire_free",
                 "tsgo_wire_encode_response", "tsgo_wire_encode_request", "tsgo_synth_create", "tsgo_synth_view",
                 "tsgo_synth_truth", "tsgo_synth_free", "tsgo_layout_probe", "tsgo_amg_probe", "tsgo_amg_probe_shard", "tsgo_init_tree"]
 DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_graph", "tsgo_reset_history", "tsgo_optimize", "tsgo_get_vertices",
                   "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
                   "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust", "tsgo_edge_report", "tsgo_gate_edges", "tsgo_init_estimates",
-                  "tsgo_set_edge_information", "tsgo_get_edge_information"]
+                  "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
 
@@ -110,6 +127,7 @@ def _declare_host(L):
     vp, u8p = C.c_void_p, C.POINTER(C.c_uint8)
     L.tsgo_default_config.argtypes = [C.POINTER(tsgo_config)]; L.tsgo_default_config.restype = None
     L.tsgo_default_robust.argtypes = [C.POINTER(tsgo_robust)]; L.tsgo_default_robust.restype = None
+    L.tsgo_default_gnc.argtypes = [C.POINTER(tsgo_gnc_params)]; L.tsgo_default_gnc.restype = None
     L.tsgo_last_error.restype = C.c_char_p
     L.tsgo_wire_decode.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp)]
     L.tsgo_wire_new.argtypes = []; L.tsgo_wire_new.restype = vp
@@ -157,6 +175,7 @@ def _declare_device(L):
     L.tsgo_init_estimates.argtypes = [vp, C.c_int32, vp, C.c_int64, C.POINTER(tsgo_init_stats)]
     L.tsgo_set_edge_information.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(tsgo_edge_info_stats)]
     L.tsgo_get_edge_information.argtypes = [vp, vp, C.c_int64]
+    L.tsgo_gnc.argtypes = [vp, C.POINTER(tsgo_gnc_params), vp, C.c_int64, vp, C.c_int64, C.POINTER(tsgo_gnc_stats)]
 
 
 def _declare_testing(L):

@@ -21,6 +21,13 @@ extern "C" void tsgo_default_robust(tsgo_robust* r) {
     r->reserved = 0;
 }
 
+extern "C" void tsgo_default_gnc(tsgo_gnc_params* p) {
+    if (!p) return;
+    static const double quantile99[5] = {11.345, 9.210, 9.210, 11.345, 9.210};      // chi^2, 3 dof (types 0, 3) and 2 dof (types 1, 2, 4)
+    for (int k = 0; k < 5; ++k) p->barc2[k] = quantile99[k];
+    p->mu_step = 1.4; p->rounds_max = 64; p->inner_iterations = 10; p->keep_weights = 1; p->reserved = 0;
+}
+
 extern "C" int tsgo_layout_probe(const tsgo_graph* g, int32_t rank, int32_t world, int32_t lanes_per_pose,
                                  int32_t lanes_per_lm, tsgo_layout_info* out) {
     if (!g || !out) return tsgo::set_error(-1, "tsgo_layout_probe: null argument");

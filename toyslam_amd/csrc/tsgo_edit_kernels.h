@@ -24,16 +24,10 @@ template <typename T> struct EditTables {      // the writable static planes of 
     T* pri_p; T* pri_l;
 };
 
-// One thread per LISTED edge: edge list[i] (i when list is null) takes inf[3 i ..].
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_set_edge_inf(int n, const int64_t* __restrict__ list, const double* __restrict__ inf, const uint32_t* __restrict__ map,
-                                                         const uint8_t* __restrict__ cls, EditTables<T> t) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const size_t e = list ? (size_t)list[i] : (size_t)i;
-    const uint2 at = *reinterpret_cast<const uint2*>(map + 2 * e);
-    const T w0 = (T)inf[3 * (size_t)i], w1 = (T)inf[3 * (size_t)i + 1], w2 = (T)inf[3 * (size_t)i + 2];
-    switch (cls[e]) {
+// (T)(w0, w1, w2) into every location of ONE edge: its class byte and the two words of its map entry say where (the table above).  The one
+// statement of "where a weight lives" for writers: k_set_edge_inf below and the reweighting pass of tsgo_gnc (tsgo_gnc_kernels.h).
+template <typename T> __device__ __forceinline__ void edge_inf_store(const EditTables<T>& t, uint8_t cls, uint2 at, T w0, T w1, T w2) {
+    switch (cls) {
     case kClassLm:
         st2<T>(t.st_p + 2 * (t.slots_p + at.x), w0, w1);
         st2<T>(t.st_l + 2 * (t.slots_l + at.y), w0, w1);
@@ -58,6 +52,17 @@ __global__ __launch_bounds__(kBlock) void k_set_edge_inf(int n, const int64_t* _
     }
     default: break;
     }
+}
+
+// One thread per LISTED edge: edge list[i] (i when list is null) takes inf[3 i ..].
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_set_edge_inf(int n, const int64_t* __restrict__ list, const double* __restrict__ inf, const uint32_t* __restrict__ map,
+                                                         const uint8_t* __restrict__ cls, EditTables<T> t) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const size_t e = list ? (size_t)list[i] : (size_t)i;
+    const uint2 at = *reinterpret_cast<const uint2*>(map + 2 * e);
+    edge_inf_store<T>(t, cls[e], at, (T)inf[3 * (size_t)i], (T)inf[3 * (size_t)i + 1], (T)inf[3 * (size_t)i + 2]);
 }
 
 // One thread per edge of the graph: what its FIRST location holds, widened; entries the class does not use are 0.

@@ -1,6 +1,6 @@
 // tsgo_hip.hip — device side of the C ABI in include/tsgo.h: buffers, launches, the Gauss-Newton
 // loop with the reference's stop rules (remote/optimizer/OptimizerCpu.h:80-180), hipGraph replay of
-// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h.
+// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h, tsgo_gnc_kernels.h.
 //
 // One translation unit; the engine class is laid out over this file and engine/*.inc (each included inside the class body):
 //   this file                      members (what the solver learns grouped by lifetime: SolverMemory; the structure index and its device maps), configuration / environment (host/knobs.h), device slabs, call-scoped device scratch (CallScratch, EventPair) and upload helpers; the C ABI at the end
@@ -17,6 +17,7 @@
 //   engine/engine_gate.inc         tsgo_gate_edges: candidate edges against the joint marginal of their vertices (Mahalanobis gate)
 //   engine/engine_init.inc         tsgo_init_estimates: estimates from an odometry spanning tree (pointer jumping), landmarks from their observations
 //   engine/engine_edit.inc         tsgo_set_edge_information / tsgo_get_edge_information: the information diagonal of listed edges, in place
+//   engine/engine_gnc.inc          tsgo_gnc: graduated non-convexity (truncated least squares), one reweighting pass over the tables per round
 //   engine/engine_testing.inc      tsgo_testing_apply (TSGO_TESTING builds only): the operators PCG applies, read out column by column
 //
 // There is NO CPU fallback in this file: every entry point that computes needs a gfx950 device and
@@ -53,6 +54,7 @@
 #include "tsgo_amg_kernels.h"
 #include "tsgo_edit_kernels.h"
 #include "tsgo_gate_kernels.h"
+#include "tsgo_gnc_kernels.h"
 #include "tsgo_init_kernels.h"
 #include "tsgo_kernels.h"
 #include "tsgo_lm_kernels.h"
@@ -163,6 +165,7 @@ struct IEngine {
     virtual int init_estimates(int what, const uint8_t* mask, int64_t n_mask, tsgo_init_stats* st) = 0;
     virtual int set_edge_information(int64_t n, const int64_t* edge_idx, const double* e_inf, tsgo_edge_info_stats* st) = 0;
     virtual int get_edge_information(double* e_inf_out, int64_t cap_edges) = 0;
+    virtual int gnc(const tsgo_gnc_params& p, const uint8_t* subject, int64_t n_mask, double* w_out, int64_t cap_edges, tsgo_gnc_stats* st) = 0;
 #ifdef TSGO_TESTING
     virtual int testing_apply(int which, const double* in, double* out, int n_cols) = 0;
 #endif
@@ -538,6 +541,7 @@ template <typename T> struct Engine : IEngine {
 #include "engine/engine_report.inc"
 #include "engine/engine_init.inc"
 #include "engine/engine_edit.inc"
+#include "engine/engine_gnc.inc"
 #ifdef TSGO_TESTING
 #include "engine/engine_testing.inc"
 #endif
@@ -667,6 +671,10 @@ int tsgo_set_edge_information(tsgo_optimizer* o, int64_t n, const int64_t* edge_
 int tsgo_get_edge_information(tsgo_optimizer* o, double* e_inf_out, int64_t cap_edges) {
     if (!o) return tsgo::set_error(-1, "tsgo_get_edge_information: null handle");
     return o->eng->get_edge_information(e_inf_out, cap_edges);
+}
+int tsgo_gnc(tsgo_optimizer* o, const tsgo_gnc_params* params, const uint8_t* subject, int64_t n_mask, double* w_out, int64_t cap_edges, tsgo_gnc_stats* stats) {
+    if (!o || !params) return tsgo::set_error(-1, "tsgo_gnc: null handle or params");
+    return o->eng->gnc(*params, subject, n_mask, w_out, cap_edges, stats);
 }
 void tsgo_reset_history(tsgo_optimizer* o) {
     if (o && o->eng) o->eng->reset_history();

@@ -59,6 +59,15 @@ template <typename T> TSGO_HD void robust_eval(int kind, T delta, T s, T& rho, T
     }
 }
 
+// Graduated non-convexity, truncated least squares (tsgo_gnc, include/tsgo.h; Yang, Antonante, Tzoumas, Carlone 2020, eq. 14): the weight
+// of an edge at control parameter mu, q = s / barc2 its squared residual over the class's inlier threshold.  Exactly 1 up to mu / (mu + 1),
+// exactly 0 from (mu + 1) / mu on, sqrt(mu (mu + 1) / q) - mu in between (one square root, one division, one subtraction; f64 only).
+TSGO_HD double gnc_tls_weight(double q, double mu) {
+    if (q <= mu / (mu + 1.0)) return 1.0;
+    if (q >= (mu + 1.0) / mu) return 0.0;
+    return sqrt(mu * (mu + 1.0) / q) - mu;
+}
+
 // How an edge function robustifies its chi^2: HuberDefault = the compile-time Huber above (what every existing signature below means, and
 // what the device kernels' RK = 0 instantiations pass), Robust<T> = a kind and a width read at run time (RK = 1: the class's entry of the
 // handle's setting).  One body per edge function serves both, so the residual arithmetic exists once.

@@ -263,6 +263,50 @@ class HipOptimizer:
         _lib.check(self.lib, self.lib.tsgo_get_edge_information(self.h, out.ctypes.data if self.n_edges else None, self.n_edges), "tsgo_get_edge_information")
         return out
 
+    def gnc(self, barc2=None, subject=None, mu_step=None, rounds_max=None, inner_iterations=None, keep_weights=True, weights=True):
+        """Graduated non-convexity with the truncated-least-squares surrogate (tsgo_gnc): rounds of on-device reweighting, each followed
+        by optimize(inner_iterations) under the handle's own rules and robust setting (textbook GNC: set_robust(all="none") first).
+        barc2: the inlier threshold on s per class, a dict over _lib.ROBUST_CLASSES (classes left out keep the default, the 99 % chi^2
+        quantile; a value <= 0 exempts the class) or a sequence of five.  subject: one entry per edge, nonzero = the edge may be
+        down-weighted; None = every edge of a class with barc2 > 0.  Edges that are not subject are known inliers: weight 1, never
+        written.  keep_weights=False restores the information the handle held before the call, bit for bit.  Returns a dict: w (n_edges,)
+        the last round's weights (None with weights=False: nothing but a few partials per round is copied back), rounds, stop, q_max,
+        the per-round traces mu, cost, chi2_inner, inner_iters, inner_stop, n_zero, n_one, n_between, and subject_by_class,
+        cg_total, ms_total, ms_reweight, ms_inner."""
+        p = _lib.tsgo_gnc_params()
+        self.lib.tsgo_default_gnc(C.byref(p))
+        if isinstance(barc2, dict):
+            for k, c in enumerate(_lib.ROBUST_CLASSES):
+                if c in barc2:
+                    p.barc2[k] = float(barc2[c])
+            if set(barc2) - set(_lib.ROBUST_CLASSES):
+                raise ValueError("gnc: barc2 has unknown classes %s" % sorted(set(barc2) - set(_lib.ROBUST_CLASSES)))
+        elif barc2 is not None:
+            vals = [float(v) for v in barc2]
+            if len(vals) != 5:
+                raise ValueError("gnc: barc2 is a dict over %s or five numbers" % (_lib.ROBUST_CLASSES,))
+            for k, v in enumerate(vals):
+                p.barc2[k] = v
+        if mu_step is not None:
+            p.mu_step = float(mu_step)
+        if rounds_max is not None:
+            p.rounds_max = int(rounds_max)
+        if inner_iterations is not None:
+            p.inner_iterations = int(inner_iterations)
+        p.keep_weights = 1 if keep_weights else 0
+        m = None if subject is None else np.ascontiguousarray(np.asarray(subject).reshape(-1) != 0, dtype=np.uint8)
+        w = np.ones(self.n_edges) if weights else None
+        st = _lib.tsgo_gnc_stats()
+        _lib.check(self.lib, self.lib.tsgo_gnc(self.h, C.byref(p), None if m is None else m.ctypes.data, 0 if m is None else len(m),
+                                               w.ctypes.data if weights and self.n_edges else None, self.n_edges, C.byref(st)), "tsgo_gnc")
+        n = st.rounds
+        return dict(w=w, rounds=n, stop=_lib.GNC_STOP[st.stop_reason], q_max=st.q_max, mu=np.array(st.mu[:n]), cost=np.array(st.cost[:n]),
+                    chi2_inner=np.array(st.chi2_inner[:n]), inner_iters=np.array(st.inner_iterations_run[:n], dtype=np.int64),
+                    inner_stop=[STOP[k] for k in st.inner_stop[:n]], n_zero=np.array(st.n_zero[:n], dtype=np.int64),
+                    n_one=np.array(st.n_one[:n], dtype=np.int64), n_between=np.array(st.n_between[:n], dtype=np.int64),
+                    subject_by_class={c: st.subject_by_class[k] for k, c in enumerate(_lib.ROBUST_CLASSES)}, cg_total=st.pcg_iters_total,
+                    ms_total=st.ms_total, ms_reweight=st.ms_reweight, ms_inner=st.ms_inner)
+
     def time_kernel(self, which, reps=50):
         us = C.c_double(); nbytes = C.c_double()
         _lib.check(self.lib, self.lib.tsgo_time_kernel(self.h, which, reps, C.byref(us), C.byref(nbytes)),
