@@ -317,6 +317,43 @@ int tsgo_marginals(tsgo_optimizer* opt, const uint32_t* ids, int32_t n_ids, doub
 int tsgo_joint_marginals(tsgo_optimizer* opt, const uint32_t* ids, int32_t n_ids, double rel_tol,
                          double* cov_out, int64_t cov_cap, int32_t* dim_out, tsgo_marginal_stats* stats /* may be NULL */);
 
+/* Posterior samples and the marginal covariance of EVERY vertex: "how uncertain is the whole map?" for K solves
+ * instead of the 3 P + 2 L columns tsgo_marginals would need.  Perturb-and-MAP: sample k solves H delta = b_k, the H of tsgo_marginals
+ * exactly (one linearisation at the current estimates: the robust weights of tsgo_set_robust, gamma_v = 1e6 x occurrences of v in the fixed
+ * list, the handle's odom_jacobian, virtual-landmark and prior edges, no rules = 1 damping), with
+ *   b_k = sum over edges e of J_e^T eta_e  +  sqrt(gamma_v) n_v on every axis of every vertex with gamma_v > 0,
+ *   eta_e,j = sqrt(a_j) n_j, a_j = w_e inf_j the robust-weighted information of the linearisation (a zero information gives 0),
+ *   n = noise(seed, 0, e, k) for input edge e (its first 3 normals for types 0 and 3, 2 for types 1, 2 and 4),
+ *   n = noise(seed, 1, v, k) for the gauge term of the vertex at position v of the tsgo_graph vertex arrays,
+ * J_e = [A | B] the Jacobians that linearisation uses (ODOM: -I, +I under odom_jacobian = 0, the analytic ones under 1; LM: A = [-R^T |
+ * (ppy, -ppx)], B = R^T; virtual landmark: A = [I | u1], B = -[I | u2]; pose prior: blockdiag(R_m^T, 1); landmark prior: I).  Cov(b) = H, so
+ * delta ~ N(0, H^-1) exactly, and the second moments of K samples estimate every diagonal block of H^-1 with relative standard error
+ * sqrt(2 / K) on a variance, whatever the correlations.
+ *   noise(seed, tag, index, k): Philox4x32-10 with key (seed low 32 bits, seed high 32 bits) and counter (index, tag, k, 0); its words
+ *   r0 .. r3 give four normals by Box-Muller in f64: u1 = (r0 + 0.5) / 2^32, u2 = (r1 + 0.5) / 2^32, n0 = sqrt(-2 ln u1) cos(2 pi u2),
+ *   n1 = sqrt(-2 ln u1) sin(2 pi u2); (r2, r3) give n2, n3 the same way.  tsgo_sample_noise is that function on the host.
+ * cov_out receives 9 doubles per vertex of the graph, in tsgo_graph vertex order, in the format of tsgo_marginals (a pose's 3x3 row-major,
+ * a landmark's 2x2 in the leading 2x2, the other five entries 0): (1 / K) sum_k delta_k delta_k^T — the mean is known to be 0, so no
+ * K - 1 — exactly symmetric.  samples_out (may be NULL) receives sample k of the vertex at position v at [(k V + v) 3]; a landmark's third
+ * entry is 0.  rel_tol <= 0: the handle's pcg_rel_tol.  The same call twice gives the same bits; sample k depends on (seed, k, graph,
+ * estimates, settings) only, not on n_samples or on its place in a batch; another seed gives other samples.  The state rule of
+ * tsgo_marginals holds: nothing the next tsgo_optimize reads changes.
+ * Errors (< 0, text in tsgo_last_error; everything is validated before anything is launched, the handle stays usable): those of
+ * tsgo_marginals (NULL handle, no graph, neither a fixed vertex nor a full pose prior, precision = 32, world > 1); n_samples outside
+ * [1, 65536]; cov_out == NULL or cap_vertices < n_vertices; samples_cap < n_samples * n_vertices * 3 when samples_out is given. */
+typedef struct tsgo_sample_stats {
+    int32_t samples, reserved;
+    tsgo_marginal_stats solve;              /* columns = samples; batches, width, iterations, fallbacks, ms */
+    double ms_total, ms_noise, ms_readout;  /* whole call; hipEvent time of the right-hand-side kernels / of the read-out kernels */
+} tsgo_sample_stats;
+int tsgo_sample_marginals(tsgo_optimizer* opt, int32_t n_samples, uint64_t seed, double rel_tol,
+                          double* cov_out /* 9 per vertex, tsgo_graph order */, int64_t cap_vertices,
+                          double* samples_out /* may be NULL: [n_samples][n_vertices][3] */, int64_t samples_cap,
+                          tsgo_sample_stats* stats /* may be NULL */);
+/* host-only too (libtsgo_host.so): the generator alone, for CPU tests */
+void tsgo_sample_noise(uint64_t seed, uint32_t tag, uint32_t index, uint32_t sample,
+                       uint32_t words_out[4] /* may be NULL */, double normals_out[4] /* may be NULL */);
+
 /* Per-edge residual report: which edges the robust kernels down-weighted, and by how much (what g2o's per-edge chi2() and Ceres' residual
  * evaluation answer).  Everything is evaluated at the handle's CURRENT estimates under its current tsgo_set_robust setting, by the edge
  * functions every linearisation runs; odom_jacobian, rules, damping and the fixed list do not enter.  rec_out receives six doubles per edge,

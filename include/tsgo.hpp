@@ -177,6 +177,19 @@ public:
         return cov;
     }
 
+    // Posterior samples and the marginal covariance of every vertex (tsgo_sample_marginals): 9 doubles per vertex of the graph last handed
+    // to Optimize or SetGraph, in its vertex order, in the format of Marginals, estimated from n_samples perturb-and-MAP samples (relative
+    // standard error sqrt(2 / n_samples) on a variance); *samples (if given) receives them, [n_samples][vertices][3].  Throws on an error
+    // (those of Marginals, n_samples outside 1 .. 65536).
+    std::vector<double> SampleMarginals(size_t n_vertices, int n_samples, uint64_t seed = 0, std::vector<double>* samples = nullptr, tsgo_sample_stats* stats = nullptr) {
+        std::vector<double> cov(n_vertices * 9);
+        if (samples) samples->assign((size_t)(n_samples > 0 ? n_samples : 0) * n_vertices * 3, 0.0);
+        if (tsgo_sample_marginals(handle, n_samples, seed, 0.0, cov.data(), (int64_t)n_vertices, samples ? samples->data() : nullptr,
+                                  samples ? (int64_t)samples->size() : 0, stats))
+            throw std::runtime_error(tsgo_last_error());
+        return cov;
+    }
+
     // Per-edge residual report at the current estimates (tsgo_edge_report): six doubles per edge of the graph last handed to Optimize, in
     // its edge order: (e0, e1, e2, s, rho, w); *stats (if given) receives the per-class summary.  EdgeSummary: the summary alone (no per-edge
     // buffer anywhere).  Both throw on an error (no graph yet, an edge-sharded handle).

@@ -51,6 +51,11 @@ class tsgo_gate_stats(C.Structure):
                 ("solve", tsgo_marginal_stats), ("ms_total", C.c_double), ("ms_readout", C.c_double)]
 
 
+class tsgo_sample_stats(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("reserved", C.c_int32), ("solve", tsgo_marginal_stats),
+                ("ms_total", C.c_double), ("ms_noise", C.c_double), ("ms_readout", C.c_double)]
+
+
 class tsgo_init_stats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("poses_set", "landmarks_set", "roots_fixed", "roots_free", "edges_usable", "tree_edges", "landmarks_unobserved")] + \
                [("depth_max", C.c_int32), ("rounds", C.c_int32), ("ms_total", C.c_double), ("ms_tree", C.c_double), ("ms_device", C.c_double)]
@@ -115,11 +120,11 @@ class tsgo_amg_info(C.Structure):
 
 HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_default_gnc", "tsgo_last_error", "tsgo_wire_decode", "tsgo_wire_new", "tsgo_wire_decode_into", "tsgo_wire_view", "tsgo_wire_free",
                 "tsgo_wire_encode_response", "tsgo_wire_encode_request", "tsgo_synth_create", "tsgo_synth_view",
-                "tsgo_synth_truth", "tsgo_synth_free", "tsgo_layout_probe", "tsgo_amg_probe", "tsgo_amg_probe_shard", "tsgo_init_tree"]
+                "tsgo_synth_truth", "tsgo_synth_free", "tsgo_layout_probe", "tsgo_amg_probe", "tsgo_amg_probe_shard", "tsgo_init_tree", "tsgo_sample_noise"]
 DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_graph", "tsgo_reset_history", "tsgo_optimize", "tsgo_get_vertices",
                   "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
                   "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust", "tsgo_edge_report", "tsgo_gate_edges", "tsgo_init_estimates",
-                  "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc"]
+                  "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc", "tsgo_sample_marginals"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
 
@@ -145,6 +150,7 @@ def _declare_host(L):
     L.tsgo_amg_probe.argtypes = [C.POINTER(tsgo_graph), C.POINTER(tsgo_amg_info)]
     L.tsgo_amg_probe_shard.argtypes = [C.POINTER(tsgo_graph), C.c_int32, C.c_int32, C.POINTER(tsgo_amg_info), C.POINTER(C.c_int64)]
     L.tsgo_init_tree.argtypes = [C.POINTER(tsgo_graph), vp, C.c_int64, vp, vp, vp, C.POINTER(tsgo_init_stats)]
+    L.tsgo_sample_noise.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]; L.tsgo_sample_noise.restype = None
     del u8p
 
 
@@ -168,6 +174,7 @@ def _declare_device(L):
     L.tsgo_profile_iteration.argtypes = [vp, C.c_int32, C.POINTER(tsgo_prof_entry), C.c_int32]
     L.tsgo_marginals.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.POINTER(tsgo_marginal_stats)]
     L.tsgo_joint_marginals.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.c_int64, C.POINTER(C.c_int32), C.POINTER(tsgo_marginal_stats)]
+    L.tsgo_sample_marginals.argtypes = [vp, C.c_int32, C.c_uint64, C.c_double, vp, C.c_int64, vp, C.c_int64, C.POINTER(tsgo_sample_stats)]
     L.tsgo_set_robust.argtypes = [vp, C.POINTER(tsgo_robust)]
     L.tsgo_get_robust.argtypes = [vp, C.POINTER(tsgo_robust)]
     L.tsgo_edge_report.argtypes = [vp, vp, C.c_int64, C.POINTER(tsgo_edge_report_stats)]

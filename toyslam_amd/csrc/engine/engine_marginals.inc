@@ -79,14 +79,22 @@
         launch(k_mb_smooth0<T, NV, 1>, gv, P, (const T*)minv, (const T*)omega_dev, r, (const T*)B.s0, z, stop);
     }
 
-    // PCG on one batch (columns already in B.cols): X = S^-1 B, column by column.  out: the batch and its largest / summed iterations
-    // counted in s, and whether any column broke down (1) or ran out of iterations (2).
-    template <int NV> int mb_solve(MbBuf& B, bool mg, double tol, tsgo_marginal_stats& s, int* fail_out) {
+    // The right-hand side of the three readers whose columns are unit columns (B.cols): what mb_for_batches passes unless told otherwise
+    template <int NV> auto mb_unit_rhs(MbBuf& B) {
+        return [this, &B](int, int) -> int {
+            HIP_OK(hipMemsetAsync(B.r, 0, (size_t)pr.P * NV * 3 * sizeof(T), stream));
+            launch_wave(k_mb_rhs<T, NV>, 1, tl, pr.by_lm.G, (const T*)ps, (const T*)lmrec, (const MbColumn*)B.cols, B.r);
+            return 0;
+        };
+    }
+    // PCG on one batch: X = S^-1 B, column by column; rhs() writes B into B.r (every entry, or zeroes it first), so that a repeat of the
+    // batch rebuilds it.  out: the batch and its largest / summed iterations counted in s, and whether any column broke down (1) or ran
+    // out of iterations (2).
+    template <int NV, typename Rhs> int mb_solve(MbBuf& B, bool mg, double tol, tsgo_marginal_stats& s, int* fail_out, Rhs&& rhs) {
         const int P = pr.P;
         const size_t vb = (size_t)P * NV * 3 * sizeof(T);
         HIP_OK(hipMemsetAsync(B.x, 0, vb, stream));
-        HIP_OK(hipMemsetAsync(B.r, 0, vb, stream));
-        launch_wave(k_mb_rhs<T, NV>, 1, tl, pr.by_lm.G, (const T*)ps, (const T*)lmrec, (const MbColumn*)B.cols, B.r);
+        if (int rc = rhs()) return rc;
         const int gv = grid_for(P * NV);
         // z = M^-1 r (the cycle, or Minv inside k_mb_dots) and the partials of r^T z, folded
         auto precondition = [&](const int* stop) {
@@ -165,8 +173,13 @@
     }
     // Every reader of the batched solve.  For each range (j0, nc) of `all`: the columns go to B.cols (padded to kMbMaxWidth with "none"),
     // mb_batch solves them (and ends with the one host synchronisation of a batch), after(b, j0, nc) reads X out of B.x with the copies and waits it needs.
+    // rhs(j0, nc): the batch's right-hand side (mb_solve); the overload without one takes the unit columns of B.cols (mb_unit_rhs).
     template <int NV, typename After>
     int mb_for_batches(MbBuf& B, const std::vector<MbColumn>& all, const BatchRanges& ranges, double tol, tsgo_marginal_stats& s, After&& after) {
+        return mb_for_batches<NV>(B, all, ranges, tol, s, mb_unit_rhs<NV>(B), after);
+    }
+    template <int NV, typename Rhs, typename After>
+    int mb_for_batches(MbBuf& B, const std::vector<MbColumn>& all, const BatchRanges& ranges, double tol, tsgo_marginal_stats& s, Rhs&& rhs, After&& after) {
         s.batch_width = NV; s.preconditioner = amg_on ? 1 : 0;
         float ms = 0;
         for (size_t b = 0; b < ranges.size(); ++b) {
@@ -174,7 +187,7 @@
             std::vector<MbColumn> cols(kMbMaxWidth, MbColumn{-1, 0, 0, 0});
             std::copy(all.begin() + j0, all.begin() + j0 + nc, cols.begin());
             HIP_OK(hipMemcpyAsync(B.cols, cols.data(), cols.size() * sizeof(MbColumn), hipMemcpyHostToDevice, stream));
-            if (int rc = mb_batch<NV>(B, tol, s, &ms)) return rc;
+            if (int rc = mb_batch<NV>(B, tol, s, &ms, [&]() -> int { return rhs(j0, nc); })) return rc;
             if (int rc = after((int)b, j0, nc)) return rc;
             s.columns += nc;
         }
@@ -186,13 +199,13 @@
             for (int b = 0; b < 3; ++b) out[3 * a + b] = 0.5 * (m[3 * a + b] + m[3 * b + a]);
     }
     // one batch: the handle's preconditioner, repeated with block-Jacobi after a breakdown of the cycle
-    template <int NV> int mb_batch(MbBuf& B, double tol, tsgo_marginal_stats& s, float* ms_acc) {
+    template <int NV, typename Rhs> int mb_batch(MbBuf& B, double tol, tsgo_marginal_stats& s, float* ms_acc, Rhs&& rhs) {
         HIP_OK(hipEventRecord(ev[0], stream));
         int fail = 0;
-        if (int rc = mb_solve<NV>(B, amg_on, tol, s, &fail)) return rc;
+        if (int rc = mb_solve<NV>(B, amg_on, tol, s, &fail, rhs)) return rc;
         if (fail == 1 && amg_on) {
             ++s.fallbacks; s.preconditioner = 0;
-            if (int rc = mb_solve<NV>(B, false, tol, s, &fail)) return rc;
+            if (int rc = mb_solve<NV>(B, false, tol, s, &fail, rhs)) return rc;
         }
         HIP_OK(hipEventRecord(ev[1], stream));
         HIP_OK(hipEventSynchronize(ev[1]));
@@ -255,6 +268,13 @@
     // The shell both entry points share.  mb_queries: the handle's checks and the id -> (pose | landmark, index) map (`name` prefixes
     // the errors; out_null: the caller's output pointer is missing where it is required).  n_ids == 0 returns 0 with qs empty before
     // the fixed-vertex check.
+    // H is regular: a fixed vertex, or a pose prior on every axis (which anchors H to the world frame)
+    bool mb_anchored() const {
+        bool fixed = false;
+        for (double g : pr.gauge_p) fixed |= g > 0;
+        for (double g : pr.gauge_l) fixed |= g > 0;
+        return fixed || has_full_pose_prior();
+    }
     int mb_queries(const char* name, const uint32_t* ids, int n_ids, bool out_null, std::vector<MbQuery>& qs) {
         const std::string nm(name);
         qs.clear();
@@ -263,11 +283,7 @@
         if (!have_graph_data) return set_error(-3, nm + ": no graph set");
         if (n_ids < 0 || (n_ids > 0 && (!ids || out_null))) return set_error(-1, nm + ": bad argument");
         if (n_ids == 0) return 0;
-        bool fixed = false;
-        for (double g : pr.gauge_p) fixed |= g > 0;
-        for (double g : pr.gauge_l) fixed |= g > 0;
-        fixed |= has_full_pose_prior();      // a pose prior on every axis anchors H to the world frame
-        if (!fixed) return set_error(-1, nm + ": marginals need a fixed vertex (without one H is singular)");
+        if (!mb_anchored()) return set_error(-1, nm + ": marginals need a fixed vertex (without one H is singular)");
         qs.resize((size_t)n_ids);
         const VertexIndex& vi = vertices();
         for (int k = 0; k < n_ids; ++k) {

@@ -4,6 +4,10 @@
 #include "problem.h"
 #include "amg.h"
 #include "init_tree.h"
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>      // (this file is also compiled into the device library: TSGO_HD of tsgo_math.h then needs the runtime's attributes)
+#endif
+#include "../tsgo_math.h"         // noise(): philox4x32_10, box_muller
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -26,6 +30,12 @@ extern "C" void tsgo_default_gnc(tsgo_gnc_params* p) {
     static const double quantile99[5] = {11.345, 9.210, 9.210, 11.345, 9.210};      // chi^2, 3 dof (types 0, 3) and 2 dof (types 1, 2, 4)
     for (int k = 0; k < 5; ++k) p->barc2[k] = quantile99[k];
     p->mu_step = 1.4; p->rounds_max = 64; p->inner_iterations = 10; p->keep_weights = 1; p->reserved = 0;
+}
+
+extern "C" void tsgo_sample_noise(uint64_t seed, uint32_t tag, uint32_t index, uint32_t sample, uint32_t words_out[4], double normals_out[4]) {
+    const tsgo::Philox4 p = tsgo::philox4x32_10(index, tag, sample, 0u, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32));
+    if (words_out) for (int k = 0; k < 4; ++k) words_out[k] = p.r[k];
+    if (normals_out) { tsgo::box_muller(p.r[0], p.r[1], normals_out[0], normals_out[1]); tsgo::box_muller(p.r[2], p.r[3], normals_out[2], normals_out[3]); }
 }
 
 extern "C" int tsgo_layout_probe(const tsgo_graph* g, int32_t rank, int32_t world, int32_t lanes_per_pose,

@@ -1,6 +1,6 @@
 // tsgo_hip.hip — device side of the C ABI in include/tsgo.h: buffers, launches, the Gauss-Newton
 // loop with the reference's stop rules (remote/optimizer/OptimizerCpu.h:80-180), hipGraph replay of
-// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h, tsgo_gnc_kernels.h.
+// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_sample_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h, tsgo_gnc_kernels.h.
 //
 // One translation unit; the engine class is laid out over this file and engine/*.inc (each included inside the class body):
 //   this file                      members (what the solver learns grouped by lifetime: SolverMemory; the structure index and its device maps), configuration / environment (host/knobs.h), device slabs, call-scoped device scratch (CallScratch, EventPair) and upload helpers; the C ABI at the end
@@ -13,6 +13,7 @@
 //   engine/engine_probes.inc       timing probes (bench.py)
 //   engine/engine_marginals.inc    tsgo_marginals, tsgo_joint_marginals: batched PCG for blocks of H^-1, one column-batch driver for every reader (mb_for_batches)
 //   host/batch_plan.h              (host only, no HIP) how the readers cut their columns into batches; the gate's per-batch lists
+//   engine/engine_sample.inc       tsgo_sample_marginals: posterior samples by perturb-and-MAP and every vertex's covariance from their second moments
 //   engine/engine_report.inc       tsgo_edge_report: per-edge residual records and the per-class summary
 //   engine/engine_gate.inc         tsgo_gate_edges: candidate edges against the joint marginal of their vertices (Mahalanobis gate)
 //   engine/engine_init.inc         tsgo_init_estimates: estimates from an odometry spanning tree (pointer jumping), landmarks from their observations
@@ -60,6 +61,7 @@
 #include "tsgo_lm_kernels.h"
 #include "tsgo_marginal_kernels.h"
 #include "tsgo_report_kernels.h"
+#include "tsgo_sample_kernels.h"
 #include "tsgo_sym_kernels.h"
 
 namespace {
@@ -159,6 +161,8 @@ struct IEngine {
     virtual void get_robust(tsgo_robust* out) const = 0;
     virtual int marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, tsgo_marginal_stats* st) = 0;
     virtual int joint_marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, int64_t cov_cap, int* dim_out, tsgo_marginal_stats* st) = 0;
+    virtual int sample_marginals(int n_samples, uint64_t seed, double rel_tol, double* cov, int64_t cap_vertices, double* samples, int64_t samples_cap,
+                                 tsgo_sample_stats* st) = 0;
     virtual int edge_report(double* rec_out, int64_t cap_edges, tsgo_edge_report_stats* st) = 0;
     virtual int gate_edges(int n, const uint32_t* e_type, const uint32_t* e_ids, const double* e_meas, const double* e_inf, double rel_tol, double* rec_out,
                            double* innov_out, tsgo_gate_stats* st) = 0;
@@ -328,6 +332,11 @@ template <typename T> struct Engine : IEngine {
         uint8_t* edit_cls = nullptr;               // [E]
         char* edit_buf = nullptr;                  // [32 E] bytes: (3 n doubles | n int64) of a set call; 3 E doubles of a get call
         bool edit_ready = false;
+        // tsgo_sample_marginals (engine_sample.inc): slot -> input edge of by_lm (the other tables' are the report's), internal pose /
+        // landmark -> position in the request's vertex arrays
+        uint32_t* smp_lm_edge = nullptr;
+        int *smp_pose_vertex = nullptr, *smp_lm_vertex = nullptr;
+        bool smp_ready = false;
     } maps;
     void drop_structure_maps() { sindex.clear(); maps = StructureMaps(); }
     const VertexIndex& vertices() { return sindex.vertices(structure.v_id, pr); }
@@ -539,6 +548,7 @@ template <typename T> struct Engine : IEngine {
 #include "engine/engine_marginals.inc"
 #include "engine/engine_gate.inc"
 #include "engine/engine_report.inc"
+#include "engine/engine_sample.inc"
 #include "engine/engine_init.inc"
 #include "engine/engine_edit.inc"
 #include "engine/engine_gnc.inc"
@@ -650,6 +660,11 @@ int tsgo_joint_marginals(tsgo_optimizer* o, const uint32_t* ids, int32_t n_ids, 
                          tsgo_marginal_stats* stats) {
     if (!o) return tsgo::set_error(-1, "tsgo_joint_marginals: null handle");
     return o->eng->joint_marginals(ids, n_ids, rel_tol, cov_out, cov_cap, dim_out, stats);
+}
+int tsgo_sample_marginals(tsgo_optimizer* o, int32_t n_samples, uint64_t seed, double rel_tol, double* cov_out, int64_t cap_vertices, double* samples_out,
+                          int64_t samples_cap, tsgo_sample_stats* stats) {
+    if (!o) return tsgo::set_error(-1, "tsgo_sample_marginals: null handle");
+    return o->eng->sample_marginals(n_samples, seed, rel_tol, cov_out, cap_vertices, samples_out, samples_cap, stats);
 }
 int tsgo_edge_report(tsgo_optimizer* o, double* rec_out, int64_t cap_edges, tsgo_edge_report_stats* stats) {
     if (!o) return tsgo::set_error(-1, "tsgo_edge_report: null handle");

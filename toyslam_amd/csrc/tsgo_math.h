@@ -21,6 +21,8 @@
 #define TSGO_HD inline
 #endif
 
+#include <stdint.h>
+
 #include <cmath>
 
 namespace tsgo {
@@ -298,6 +300,48 @@ template <typename T> TSGO_HD void inv_sym3(const T* m, T* o) {
     o[3] = (m[0] * m[5] - m[2] * m[2]) * r;
     o[4] = (m[1] * m[2] - m[0] * m[4]) * r;
     o[5] = (m[0] * m[3] - m[1] * m[1]) * r;
+}
+
+// ---- noise(seed, tag, index, k): the standard normals of posterior sampling (tsgo_sample_marginals, include/tsgo.h) -------------------
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw 2011; the Random123 known answers are in tests/test_sample_marginals_cpu.py): a counter-based
+// generator, so any (edge | vertex, sample) draws its numbers without a state that would tie it to a lane, a slot or a batch.
+// Key = (seed low, seed high), counter = (index, tag, k, 0); tag 0: input edge `index`, tag 1: the gauge term of the vertex at position `index`.
+struct Philox4 { uint32_t r[4]; };
+TSGO_HD Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int round = 0; round < 10; ++round) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return Philox4{{c0, c1, c2, c3}};
+}
+// Box-Muller in f64 on two words: u1 = (a + 0.5) / 2^32 in (0, 1), u2 likewise; (sqrt(-2 ln u1) cos(2 pi u2), ... sin(2 pi u2)).  |n| < 6.7.
+// The device takes sin and cos of pi x (no argument reduction against pi: 2 u2 is exact); host and device agree to a few ulp.
+TSGO_HD void box_muller(uint32_t a, uint32_t b, double& n0, double& n1) {
+    const double u1 = ((double)a + 0.5) * (1.0 / 4294967296.0), u2 = ((double)b + 0.5) * (1.0 / 4294967296.0);
+    const double rad = sqrt(-2.0 * log(u1));
+#if defined(__HIP_DEVICE_COMPILE__)
+    double sn, cs;
+    sincospi(2.0 * u2, &sn, &cs);
+#else
+    const double ang = 6.283185307179586476925286766559 * u2, sn = sin(ang), cs = cos(ang);
+#endif
+    n0 = rad * cs; n1 = rad * sn;
+}
+struct SampleSeed { uint32_t lo, hi; };
+TSGO_HD void sample_noise2(SampleSeed s, uint32_t tag, uint32_t index, uint32_t k, double& n0, double& n1) {
+    const Philox4 p = philox4x32_10(index, tag, k, 0u, s.lo, s.hi);
+    box_muller(p.r[0], p.r[1], n0, n1);
+}
+TSGO_HD void sample_noise3(SampleSeed s, uint32_t tag, uint32_t index, uint32_t k, double& n0, double& n1, double& n2) {
+    const Philox4 p = philox4x32_10(index, tag, k, 0u, s.lo, s.hi);
+    double n3;
+    box_muller(p.r[0], p.r[1], n0, n1);
+    box_muller(p.r[2], p.r[3], n2, n3);
 }
 
 template <typename T> TSGO_HD void sym3_mul(const T* m, T v0, T v1, T v2, T& o0, T& o1, T& o2) {

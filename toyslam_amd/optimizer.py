@@ -173,6 +173,22 @@ class HipOptimizer:
                                                             C.byref(dim), C.byref(st)), "tsgo_joint_marginals")
         return cov, offsets, {f: getattr(st, f) for f, _t in st._fields_}
 
+    def sample_marginals(self, n_samples, seed=0, rel_tol=0.0, samples=False):
+        """Posterior samples by perturb-and-MAP and the marginal covariance of EVERY vertex from their second moments
+        (tsgo_sample_marginals): dict(cov (V, 3, 3) in the vertex order of the graph given to set_graph, a landmark's block in
+        cov[v, :2, :2]; samples (K, V, 3) with samples=True, else None; stats).  A variance has relative standard error sqrt(2 / K).
+        rel_tol <= 0: the handle's pcg_rel_tol."""
+        K, V = int(n_samples), self.n_vertices
+        cov = np.zeros((V, 3, 3))
+        smp = np.zeros((K, V, 3)) if samples and 1 <= K <= 65536 else None      # (outside that range the call refuses before it looks at samples_out)
+        st = _lib.tsgo_sample_stats()
+        _lib.check(self.lib, self.lib.tsgo_sample_marginals(self.h, K, int(seed) & 0xFFFFFFFFFFFFFFFF, float(rel_tol), cov.ctypes.data, V,
+                                                             smp.ctypes.data if smp is not None else None, smp.size if smp is not None else 0,
+                                                             C.byref(st)), "tsgo_sample_marginals")
+        stats = {f: getattr(st, f) for f, _t in st._fields_ if f not in ("solve", "reserved")}
+        stats["solve"] = {f: getattr(st.solve, f) for f, _t in st.solve._fields_}
+        return dict(cov=cov, samples=smp, stats=stats)
+
     def edge_report(self, records=True):
         """Per-edge residual report at the current estimates under the handle's robust setting (tsgo_edge_report): (rec, summary).
         rec: dict of views over one (E, 6) array in the edge order of the graph given to set_graph — e (E, 3), s, rho, w (E,) — and the
