@@ -34,6 +34,63 @@ int tsgo_comm_init_local(tsgo_optimizer* opt, tsgo_local_group* group);
  *            no column is stopped.  which <= 2 loop over the columns. */
 int tsgo_testing_apply(tsgo_optimizer* opt, int32_t which, const double* in, double* out, int32_t n_cols);
 
+/* ---- the device pattern builders (toyslam_amd/csrc/tsgo_sym_kernels.h) on caller-given integer arrays: tests/test_gpu_sym_patterns.py.
+ * No handle, no graph, no linearisation: each call allocates its own device scratch, launches the kernels through the launch helpers the
+ * engine itself uses (the same geometry) on the null stream, copies everything they wrote back and frees the scratch before it returns.
+ * A refused input or a capacity that is too small is an error return (tsgo_last_error), never a write past the end of an array. */
+
+/* k_sym_scan: out[0 .. n] = exclusive scan of in[0 .. n), out[n] = the total.  n >= 0; entries >= 0.  The kernel returns int: a total of
+ * 2^31 or more is refused here — in the engine the host builder refuses such a hierarchy ("exceed 2^31 pairs") where the device's
+ * count would wrap. */
+int tsgo_testing_sym_scan(int32_t n, const int32_t* in, int32_t* out);
+
+typedef struct tsgo_testing_sym_out {
+    int64_t cap_blocks, cap_pairs; /* in: entries the caller's arrays hold (zcol, mirror, upper: cap_blocks; pl_ptr: cap_blocks + 1; px, py: cap_pairs) */
+    int32_t* zptr;                 /* n + 1 */
+    int32_t* zcol;                 /* the distinct columns of every row, ascending */
+    int32_t* pl_ptr;               /* nnz + 1: the list offsets per block */
+    int32_t* px;                   /* the lists: x block (or its alias) ... */
+    int32_t* py;                   /* ... and y block of every pair, in walking order within a block */
+    int32_t* mirror;               /* upper: per block below the diagonal the block it mirrors, -1 elsewhere (may be null when upper = 0) */
+    int32_t* upper;                /* upper: the blocks on or above the diagonal, in block order (may be null when upper = 0) */
+    int32_t* n_upper;              /* upper: n entries, blocks on or above the diagonal per row (may be null when upper = 0) */
+    int64_t nnz, pairs, upper_blocks;   /* out: entries written */
+    int32_t declined;              /* out: the count pass raised its overflow word; nothing else was launched, nothing else is returned */
+    int32_t not_symmetric;         /* out: k_sym_mirror's `bad` / the host builder's error text; every array is returned all the same */
+} tsgo_testing_sym_out;
+
+/* Z = X * Y on patterns with the pair lists of every Z block.  X: n rows (xptr, xcol; x_alias optional, one entry per X block),
+ * Y: ny rows and nc columns (yptr, ycol).  builder = 1: the device sequence of the engine (count, two scans, fill; upper: the scan of
+ * n_upper and k_sym_mirror).  builder = 0: the host builder (host/amg.cpp: spgemm_sym) on the same arrays; it never declines, and its
+ * `upper` / `n_upper` are read off Z (column >= row).  upper = 1 is the symmetric product: only blocks on or above the diagonal get lists.
+ * Refused: n < 1, upper with nc != n, pointers that do not rise from 0, an X column outside [0, ny), a Y column outside [0, nc), a Y row
+ * that holds a column twice (the kernels' precondition: "a Y row has every column once"), more than 2^31 - 1 pairs. */
+int tsgo_testing_sym_product(int32_t builder, int32_t upper, int32_t n, const int32_t* xptr, const int32_t* xcol, const int32_t* x_alias, int32_t ny, int32_t nc,
+                             const int32_t* yptr, const int32_t* ycol, tsgo_testing_sym_out* out);
+
+typedef struct tsgo_testing_schur_out {
+    int64_t cap_blocks, cap_pairs, cap_od;   /* in: zcol: cap_blocks; sc_ptr, sc_optr: cap_blocks + 1; slot_i, slot_k: cap_pairs; os: cap_od */
+    int32_t* zptr;                 /* P + 1 */
+    int32_t* zcol;
+    int32_t* sc_ptr;               /* nnz + 1: offsets of a block's pairs */
+    int32_t* sc_optr;              /* nnz + 1: offsets of a block's odometry slots */
+    uint32_t* slot_i;
+    uint32_t* slot_k;
+    uint32_t* os;
+    int64_t nnz, pairs, od;        /* out */
+    int32_t declined;              /* out: k_s0_count's overflow word; k_s0_fill was not launched */
+    int32_t reserved;
+} tsgo_testing_schur_out;
+
+/* Level 0: the pattern of the explicit Schur complement with its slot-pair and odometry lists (k_s0_count, three scans, k_s0_fill) from the
+ * nine arrays of host/amg.h: SchurCsr.  builder must be 1: the host's level-0 builder reads the slot tables of a whole graph, not these lists
+ * (tests/test_gpu_parity.py compares the two through the engine).  Refused: pointers that do not rise from 0, a landmark outside [0, L), a
+ * pose outside [0, P), an odometry neighbour that is the pose itself, slots of one pose's edge or odometry list that do not rise, and two
+ * entries of ONE pose in ONE observer list whose slots do not rise (the contract the kernel's comment states). */
+int tsgo_testing_schur_pattern(int32_t builder, int32_t P, int32_t L, const int32_t* pp_ptr, const int32_t* pp_lm, const uint32_t* pp_slot, const int32_t* obs_ptr,
+                               const int32_t* obs_pose, const uint32_t* obs_slot, const int32_t* od_ptr, const int32_t* od_col, const uint32_t* od_slot,
+                               int32_t max_pair_degree, tsgo_testing_schur_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -613,6 +613,85 @@ def test_pair_lists_built_on_the_device_equal_the_hosts(monkeypatch, n_poses, lc
     np.testing.assert_array_equal(vd, vh)
 
 
+def crowded_place(n_poses=640, window=64, stride=5, seed=47):
+    """A crowded place: poses one unit apart along a line, joined by odometry; landmark j is observed by the `window` poses
+    [stride * j, stride * j + window), so every landmark has exactly `window` observers and an interior pose 2 * (window - 1) co-observers.
+    Noise, information and f32 rounding as toyslam_amd/csrc/host/synth.cpp makes them; estimates = truth + a small drift; pose 0 fixed."""
+    rng = np.random.default_rng(seed)
+    f32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)  # noqa: E731
+    P = n_poses
+    L = (P - window) // stride + 1
+    sig_xy, sig_th, sig_lidar = 0.25, (7.1 * np.pi / 180.0) ** 2, 0.15 * 0.15
+    truth = np.zeros((P + L, 3))
+    truth[:P, 0] = np.arange(P)
+    truth[:P, 1] = 0.5 * np.sin(0.05 * np.arange(P))
+    truth[:P, 2] = 0.05 * np.cos(0.05 * np.arange(P))
+    truth[P:, 0] = stride * np.arange(L) + 0.5 * window
+    truth[P:, 1] = 3.0 + (np.arange(L) % 3)
+    v_pos = truth.copy()
+    v_pos[1:P] += 0.05 * rng.standard_normal((P - 1, 3)) * [1.0, 1.0, 0.1]
+    v_pos[P:, :2] += 0.05 * rng.standard_normal((L, 2))
+    e_type, e_ids, e_meas, e_inf = [], [], [], []
+    for a in range(P - 1):
+        ca, sa = np.cos(truth[a, 2]), np.sin(truth[a, 2])
+        d = truth[a + 1] - truth[a]
+        mx, my = ca * d[0] + sa * d[1] + sig_xy * rng.standard_normal(), -sa * d[0] + ca * d[1] + sig_xy * rng.standard_normal()
+        mt = d[2] + sig_th * rng.standard_normal()
+        e_type.append(0); e_ids.append([a, a + 1])
+        e_meas.append([np.cos(mt), -np.sin(mt), mx, np.sin(mt), np.cos(mt), my, 0, 0, 1]); e_inf.append([1 / sig_xy, 1 / sig_xy, 1 / sig_th])
+    for j in range(L):
+        for i in range(stride * j, stride * j + window):
+            c, s = np.cos(truth[i, 2]), np.sin(truth[i, 2])
+            d = truth[P + j, :2] - truth[i, :2]
+            mx, my = c * d[0] + s * d[1] + sig_lidar * rng.standard_normal(), -s * d[0] + c * d[1] + sig_lidar * rng.standard_normal()
+            e_type.append(1); e_ids.append([i, P + j])
+            e_meas.append([np.hypot(mx, my), np.arctan2(my, mx), 0, 0, 0, 0, 0, 0, 0]); e_inf.append([1 / sig_lidar, 1 / sig_lidar, 0.0])
+    v_type = np.r_[np.zeros(P, np.uint32), np.ones(L, np.uint32)]
+    return GraphArrays(np.arange(P + L, dtype=np.uint32), v_type, f32(v_pos), np.array(e_type, np.uint32), np.array(e_ids, np.uint32), f32(e_meas), f32(e_inf),
+                       np.array([0], np.uint32))
+
+
+def test_pair_lists_of_a_crowded_place_equal_the_hosts(monkeypatch):
+    """test_pair_lists_built_on_the_device_equal_the_hosts on a graph whose rows are long: 640 poses along a line, every landmark observed
+    by exactly 64 poses (the most that still couple, host/amg.h: kMaxPairDegree), every interior pose with 126 co-observers — level-0 rows of
+    127 blocks and observer lists that fill a wavefront, where the synthetic graphs have a few dozen blocks and about five observers.
+    The window of 64 observers at stride 5 coarsens to the limits the engine requires as it is: nothing had to be shrunk."""
+    import ctypes as C
+    from toyslam_amd import _lib
+    g = crowded_place()
+    lib = _lib.host_lib()
+    info = _lib.tsgo_amg_info()
+    cg = g.c_struct()
+    _lib.check(lib, lib.tsgo_amg_probe(C.byref(cg), C.byref(info)), "tsgo_amg_probe")
+    assert info.rows[0] == 640 and info.blocks[0] > 64 * info.rows[0], (info.rows[0], info.blocks[0])
+    res = {}
+    for host in (True, False):
+        if host:
+            monkeypatch.setenv("TSGO_HOST_PRODUCTS", "1")
+        else:
+            monkeypatch.delenv("TSGO_HOST_PRODUCTS", raising=False)
+        o = HipOptimizer(pcg_rel_tol=1e-12, testing=host)      # the host builder is forced in the TSGO_TESTING build; the device builder runs in the PRODUCT library
+        try:
+            o.set_graph(g); res[host] = (o.optimize(5), o.vertices())
+        finally:
+            o.close()
+    (rh, vh), (rd, vd) = res[True], res[False]
+    np.testing.assert_array_equal(rd["chi2"], rh["chi2"])
+    np.testing.assert_array_equal(rd["cg_iters"], rh["cg_iters"])
+    np.testing.assert_array_equal(vd, vh)
+    # one Gauss-Newton step against the CPU twin, at the tolerances of test_c2_10k_poses_against_sparse_cpu_twin (chi^2 1e-9 relative, 1e-7 on the vertices' change)
+    o = HipOptimizer(pcg_rel_tol=1e-12)
+    try:
+        o.set_graph(g); step = o.solve_step()
+    finally:
+        o.close()
+    ref = oracle.sparse_step(util.to_oracle(g), 1e-12, precond="amg")
+    print("crowded place: blocks[0] = %d, PCG iterations %s, one step: chi^2 off by %.3g (relative), delta off by %.3g of %.3g" % (
+        info.blocks[0], list(rd["cg_iters"]), abs(step["chi2"] - ref["chi2"]) / ref["chi2"], np.abs(step["delta"] - ref["delta"]).max(), np.abs(ref["delta"]).max()))
+    np.testing.assert_allclose(step["chi2"], ref["chi2"], rtol=1e-9)
+    assert np.abs(step["delta"] - ref["delta"]).max() < 1e-7
+
+
 @pytest.mark.parametrize("bits", [1, 2, 4, 7])
 def test_device_pattern_builders_hand_back_to_the_host(monkeypatch, bits):
     """A row with more distinct columns than the device builders' LDS tables hold (1 024) makes them decline: level 0, or a level's

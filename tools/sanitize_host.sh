@@ -21,4 +21,9 @@ src="host/problem.cpp host/amg.cpp host/codec.cpp host/synth.cpp host/host_api.c
   echo "ThreadSanitizer: layout (parallel slot fill) + multigrid patterns (parallel products, helper thread for the next level's aggregates), whole graph and one shard of two, 6 threads"
   (cd toyslam_amd/csrc && g++ -O1 -g -std=c++17 -pthread -fsanitize=thread -o /tmp/tsgo_tsan_driver ../../tools/tsan_driver.cpp $src)
   TSGO_HOST_THREADS=6 /tmp/tsgo_tsan_driver 2>&1 | tail -12
+  echo "stand-alone ASan + UBSan: the host builder of the pair-list products (tests/cpp/sym_product_dump.cpp) over every product case of tests/sym_patterns.py; lines out = cases"
+  (cd toyslam_amd/csrc && g++ -O1 -g -std=c++17 -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I. -o /tmp/tsgo_sym_product_dump_asan \
+     ../../tests/cpp/sym_product_dump.cpp host/amg.cpp host/problem.cpp)
+  python -c "from tests import sym_patterns as sp; print('\n'.join(p.text(u) for p in sp.product_cases().values() for u in ((0, 1) if p.square else (0,))))" \
+    | ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 TSGO_HOST_THREADS=4 /tmp/tsgo_sym_product_dump_asan | wc -l
 } | tee "$out"

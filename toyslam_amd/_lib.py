@@ -118,6 +118,17 @@ class tsgo_amg_info(C.Structure):
                 ("agg_min", C.c_int32 * 8), ("agg_max", C.c_int32 * 8), ("checksum", C.c_uint64)]
 
 
+class tsgo_testing_sym_out(C.Structure):
+    _fields_ = [("cap_blocks", C.c_int64), ("cap_pairs", C.c_int64)] + [(n, C.c_void_p) for n in ("zptr", "zcol", "pl_ptr", "px", "py", "mirror", "upper", "n_upper")] + \
+               [("nnz", C.c_int64), ("pairs", C.c_int64), ("upper_blocks", C.c_int64), ("declined", C.c_int32), ("not_symmetric", C.c_int32)]
+
+
+class tsgo_testing_schur_out(C.Structure):
+    _fields_ = [("cap_blocks", C.c_int64), ("cap_pairs", C.c_int64), ("cap_od", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("zptr", "zcol", "sc_ptr", "sc_optr", "slot_i", "slot_k", "os")] + \
+               [("nnz", C.c_int64), ("pairs", C.c_int64), ("od", C.c_int64), ("declined", C.c_int32), ("reserved", C.c_int32)]
+
+
 HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_default_gnc", "tsgo_last_error", "tsgo_wire_decode", "tsgo_wire_new", "tsgo_wire_decode_into", "tsgo_wire_view", "tsgo_wire_free",
                 "tsgo_wire_encode_response", "tsgo_wire_encode_request", "tsgo_synth_create", "tsgo_synth_view",
                 "tsgo_synth_truth", "tsgo_synth_free", "tsgo_layout_probe", "tsgo_amg_probe", "tsgo_amg_probe_shard", "tsgo_init_tree", "tsgo_sample_noise"]
@@ -125,7 +136,8 @@ DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_
                   "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
                   "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust", "tsgo_edge_report", "tsgo_gate_edges", "tsgo_init_estimates",
                   "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc", "tsgo_sample_marginals"]
-TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
+TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply",
+                   "tsgo_testing_sym_scan", "tsgo_testing_sym_product", "tsgo_testing_schur_pattern"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
 
 def _declare_host(L):
@@ -191,6 +203,9 @@ def _declare_testing(L):
     L.tsgo_local_group_destroy.argtypes = [vp]; L.tsgo_local_group_destroy.restype = None
     L.tsgo_comm_init_local.argtypes = [vp, vp]
     L.tsgo_testing_apply.argtypes = [vp, C.c_int32, vp, vp, C.c_int32]
+    L.tsgo_testing_sym_scan.argtypes = [C.c_int32, vp, vp]
+    L.tsgo_testing_sym_product.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.POINTER(tsgo_testing_sym_out)]
+    L.tsgo_testing_schur_pattern.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [vp] * 9 + [C.c_int32, C.POINTER(tsgo_testing_schur_out)]
 
 
 _host = None

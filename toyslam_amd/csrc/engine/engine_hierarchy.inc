@@ -115,11 +115,10 @@
         if (int rc = dalloc(&ooff, (size_t)P + 1)) return rc;
         if (int rc = dalloc(&flags, 4)) return rc;
         if (int rc = fill_zero(flags, 4 * sizeof(int))) return rc;
-        hipLaunchKernelGGL(k_s0_count, dim3(P), dim3(kSymWave), 0, cs(), P, (const int*)pp_ptr, (const int*)pp_lm, (const int*)obs_ptr, (const int*)obs_pose, (const int*)od_ptr,
-                           (const int*)od_col, in.max_pair_degree, d, m, mo, flags);
-        hipLaunchKernelGGL(k_sym_scan, dim3(1), dim3(1024), 0, cs(), P, (const int*)d, zptr);
-        hipLaunchKernelGGL(k_sym_scan, dim3(1), dim3(1024), 0, cs(), P, (const int*)m, poff);
-        hipLaunchKernelGGL(k_sym_scan, dim3(1), dim3(1024), 0, cs(), P, (const int*)mo, ooff);
+        launch_s0_count(cs(), P, pp_ptr, pp_lm, obs_ptr, obs_pose, od_ptr, od_col, in.max_pair_degree, d, m, mo, flags);
+        launch_sym_scan(cs(), P, d, zptr);
+        launch_sym_scan(cs(), P, m, poff);
+        launch_sym_scan(cs(), P, mo, ooff);
         int h4[4];
         HIP_OK(hipMemcpyAsync(&h4[0], zptr + P, sizeof(int), hipMemcpyDeviceToHost, cs()));
         HIP_OK(hipMemcpyAsync(&h4[1], poff + P, sizeof(int), hipMemcpyDeviceToHost, cs()));
@@ -135,9 +134,8 @@
         if (int rc = dalloc(&sc_si, (size_t)n_pairs)) return rc;
         if (int rc = dalloc(&sc_sk, (size_t)n_pairs)) return rc;
         if (int rc = dalloc(&sc_os, (size_t)n_od)) return rc;
-        hipLaunchKernelGGL(k_s0_fill, dim3(P), dim3(kSymWave), 0, cs(), P, (const int*)pp_ptr, (const int*)pp_lm, (const uint32_t*)pp_slot, (const int*)obs_ptr, (const int*)obs_pose,
-                           (const uint32_t*)obs_slot, (const int*)od_ptr, (const int*)od_col, (const uint32_t*)od_slot, in.max_pair_degree, (const int*)zptr, (const int*)poff,
-                           (const int*)ooff, zcol, sc_ptr, sc_optr, sc_si, sc_sk, sc_os);
+        launch_s0_fill(cs(), P, pp_ptr, pp_lm, pp_slot, obs_ptr, obs_pose, obs_slot, od_ptr, od_col, od_slot, in.max_pair_degree, zptr, poff, ooff, zcol, sc_ptr, sc_optr, sc_si, sc_sk,
+                       sc_os);
         HIP_OK(hipMemcpyAsync(sc_ptr + nnz, &n_pairs, sizeof(int), hipMemcpyHostToDevice, cs()));
         HIP_OK(hipMemcpyAsync(sc_optr + nnz, &n_od, sizeof(int), hipMemcpyHostToDevice, cs()));
         A0.n_rows = A0.n_cols = P;
@@ -172,9 +170,9 @@
         if (int rc = fill_zero(flags, 4 * sizeof(int))) return rc;
         int h3[3];
         // ---- T = A P
-        hipLaunchKernelGGL((k_sym_count<0>), dim3(n), dim3(kSymWave), 0, cs(), n, (const int*)D.A_ptr, (const int*)D.A_col, (const int*)D.P_ptr, (const int*)D.P_col, d, m, flags);
-        hipLaunchKernelGGL(k_sym_scan, dim3(1), dim3(1024), 0, cs(), n, (const int*)d, tptr);
-        hipLaunchKernelGGL(k_sym_scan, dim3(1), dim3(1024), 0, cs(), n, (const int*)m, tpoff);
+        launch_sym_count<0>(cs(), n, D.A_ptr, D.A_col, D.P_ptr, D.P_col, d, m, flags);
+        launch_sym_scan(cs(), n, d, tptr);
+        launch_sym_scan(cs(), n, m, tpoff);
         HIP_OK(hipMemcpyAsync(&h3[0], tptr + n, sizeof(int), hipMemcpyDeviceToHost, cs()));
         HIP_OK(hipMemcpyAsync(&h3[1], tpoff + n, sizeof(int), hipMemcpyDeviceToHost, cs()));
         HIP_OK(hipMemcpyAsync(&h3[2], flags, sizeof(int), hipMemcpyDeviceToHost, cs()));
@@ -186,8 +184,7 @@
         if (int rc = dalloc(&D.ts_ptr, (size_t)nnzT + 1)) return rc;
         if (int rc = dalloc(&D.ts_x, (size_t)pairsT)) return rc;
         if (int rc = dalloc(&D.ts_y, (size_t)pairsT)) return rc;
-        hipLaunchKernelGGL((k_sym_fill<0>), dim3(n), dim3(kSymWave), 0, cs(), n, (const int*)D.A_ptr, (const int*)D.A_col, (const int*)nullptr, (const int*)D.P_ptr, (const int*)D.P_col,
-                           (const int*)tptr, (const int*)tpoff, tcol, D.ts_ptr, D.ts_x, D.ts_y, (int*)nullptr);
+        launch_sym_fill<0>(cs(), n, D.A_ptr, D.A_col, nullptr, D.P_ptr, D.P_col, tptr, tpoff, tcol, D.ts_ptr, D.ts_x, D.ts_y, nullptr);
         HIP_OK(hipMemcpyAsync(D.ts_ptr + nnzT, &pairsT, sizeof(int), hipMemcpyHostToDevice, cs()));
         // ---- A' = R T, upper blocks listed
         int *zptr = nullptr, *zpoff = nullptr, *nup = nullptr, *uoff = nullptr;
@@ -195,9 +192,9 @@
         if (int rc = dalloc(&zpoff, (size_t)na + 1)) return rc;
         if (int rc = dalloc(&nup, (size_t)na)) return rc;
         if (int rc = dalloc(&uoff, (size_t)na + 1)) return rc;
-        hipLaunchKernelGGL((k_sym_count<1>), dim3(na), dim3(kSymWave), 0, cs(), na, (const int*)D.R_ptr, (const int*)D.R_col, (const int*)tptr, (const int*)tcol, d, m, flags + 1);
-        hipLaunchKernelGGL(k_sym_scan, dim3(1), dim3(1024), 0, cs(), na, (const int*)d, zptr);
-        hipLaunchKernelGGL(k_sym_scan, dim3(1), dim3(1024), 0, cs(), na, (const int*)m, zpoff);
+        launch_sym_count<1>(cs(), na, D.R_ptr, D.R_col, tptr, tcol, d, m, flags + 1);
+        launch_sym_scan(cs(), na, d, zptr);
+        launch_sym_scan(cs(), na, m, zpoff);
         HIP_OK(hipMemcpyAsync(&h3[0], zptr + na, sizeof(int), hipMemcpyDeviceToHost, cs()));
         HIP_OK(hipMemcpyAsync(&h3[1], zpoff + na, sizeof(int), hipMemcpyDeviceToHost, cs()));
         HIP_OK(hipMemcpyAsync(&h3[2], flags + 1, sizeof(int), hipMemcpyDeviceToHost, cs()));
@@ -211,11 +208,10 @@
         if (int rc = dalloc(&D.as_y, (size_t)pairsA)) return rc;
         if (int rc = dalloc(&D.as_mirror, (size_t)nnzN)) return rc;
         if (int rc = dalloc(&D.as_upper, (size_t)nnzN)) return rc;
-        hipLaunchKernelGGL((k_sym_fill<1>), dim3(na), dim3(kSymWave), 0, cs(), na, (const int*)D.R_ptr, (const int*)D.R_col, (const int*)D.r_to_p, (const int*)tptr, (const int*)tcol,
-                           (const int*)zptr, (const int*)zpoff, zcol, D.as_ptr, D.as_x, D.as_y, nup);
+        launch_sym_fill<1>(cs(), na, D.R_ptr, D.R_col, D.r_to_p, tptr, tcol, zptr, zpoff, zcol, D.as_ptr, D.as_x, D.as_y, nup);
         HIP_OK(hipMemcpyAsync(D.as_ptr + nnzN, &pairsA, sizeof(int), hipMemcpyHostToDevice, cs()));
-        hipLaunchKernelGGL(k_sym_scan, dim3(1), dim3(1024), 0, cs(), na, (const int*)nup, uoff);
-        hipLaunchKernelGGL(k_sym_mirror, dim3((na + 255) / 256), dim3(256), 0, cs(), na, (const int*)zptr, (const int*)zcol, (const int*)uoff, D.as_mirror, D.as_upper, flags + 2);
+        launch_sym_scan(cs(), na, nup, uoff);
+        launch_sym_mirror(cs(), na, zptr, zcol, uoff, D.as_mirror, D.as_upper, flags + 2);
         A_next.n_rows = A_next.n_cols = na;
         A_next.ptr.resize((size_t)na + 1); A_next.col.resize((size_t)nnzN);
         HIP_OK(hipMemcpyAsync(A_next.ptr.data(), zptr, ((size_t)na + 1) * sizeof(int), hipMemcpyDeviceToHost, cs()));
@@ -278,12 +274,12 @@
             if (int rc = dalloc(&mirror0, (size_t)L0.nnzA)) return rc;
             if (int rc = dalloc(&upper0, (size_t)L0.nnzA)) return rc;
             if (int rc = fill_zero(flag, 4 * sizeof(int))) return rc;
-            hipLaunchKernelGGL(k_count_upper, dim3((L0.n + 255) / 256), dim3(256), 0, cs(), L0.n, (const int*)L0.A_ptr, (const int*)L0.A_col, nup);
-            hipLaunchKernelGGL(k_sym_scan, dim3(1), dim3(1024), 0, cs(), L0.n, (const int*)nup, uoff);
-            hipLaunchKernelGGL(k_sym_mirror, dim3((L0.n + 255) / 256), dim3(256), 0, cs(), L0.n, (const int*)L0.A_ptr, (const int*)L0.A_col, (const int*)uoff, mirror0, upper0, flag);
+            launch_count_upper(cs(), L0.n, L0.A_ptr, L0.A_col, nup);
+            launch_sym_scan(cs(), L0.n, nup, uoff);
+            launch_sym_mirror(cs(), L0.n, L0.A_ptr, L0.A_col, uoff, mirror0, upper0, flag);
             if (int rc = dalloc(&lower0, (size_t)L0.nnzA)) return rc;
             HIP_OK(hipMemsetAsync(lower0, 0xff, sizeof(int) * (size_t)L0.nnzA, cs()));
-            hipLaunchKernelGGL(k_invert_mirror, dim3((L0.nnzA + 255) / 256), dim3(256), 0, cs(), L0.nnzA, (const int*)mirror0, lower0);
+            launch_invert_mirror(cs(), L0.nnzA, mirror0, lower0);
             int h2[2] = {0, 0};
             HIP_OK(hipMemcpyAsync(&h2[0], uoff + L0.n, sizeof(int), hipMemcpyDeviceToHost, cs()));
             HIP_OK(hipMemcpyAsync(&h2[1], flag, sizeof(int), hipMemcpyDeviceToHost, cs()));

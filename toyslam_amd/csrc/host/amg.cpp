@@ -84,8 +84,8 @@ inline void emit_row(std::vector<Triple>& row, RowsOut& o) {
 // in the final arrays, pass B sorts the row's distinct columns, lays out its groups and scatters the pairs into
 // them in (x, y) walking order.  mirror (for the symmetric product Z = P^T (A P)): only blocks on or above the
 // diagonal get a pair list; a block below it gets the index of its transpose instead (-1 elsewhere).
-std::string spgemm_sym(const BlockCsr& X, const std::vector<int>* x_alias, const BlockCsr& Y, BlockCsr& Z, PairList& pl,
-                       std::vector<int>* mirror = nullptr) {
+}  // namespace
+std::string spgemm_sym(const BlockCsr& X, const std::vector<int>* x_alias, const BlockCsr& Y, BlockCsr& Z, PairList& pl, std::vector<int>* mirror) {
     Z.n_rows = X.n_rows; Z.n_cols = Y.n_cols;
     const int n = X.n_rows, nc = Y.n_cols;
     const bool upper = mirror != nullptr;
@@ -172,6 +172,7 @@ std::string spgemm_sym(const BlockCsr& X, const std::vector<int>* x_alias, const
     }
     return std::string();
 }
+namespace {
 
 void transpose_pattern(const BlockCsr& X, BlockCsr& Xt, std::vector<int>& to_src) {
     Xt.n_rows = X.n_cols; Xt.n_cols = X.n_rows;

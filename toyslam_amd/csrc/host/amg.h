@@ -137,6 +137,12 @@ struct AmgProgress {
     std::function<bool(int level, AmgLevel& L, BlockCsr& A_next, std::string& err)> products;
 };
 
+// The host builder of one pair-list product (amg.cpp): Z = X * Y (patterns) and, per Z block, its (x block, y block) pairs in walking
+// order; x_alias (optional) renames the X blocks in the lists; mirror (optional) makes it the UPPER product of a square pattern.
+// Returns "" or an error text.  Declared here for the tests that compare it, entry by entry, with the device builder
+// (tsgo_sym_kernels.h) and with a reference (tests/cpp/sym_product_dump.cpp, include/tsgo_testing.h: tsgo_testing_sym_product).
+std::string spgemm_sym(const BlockCsr& X, const std::vector<int>* x_alias, const BlockCsr& Y, BlockCsr& Z, PairList& pl, std::vector<int>* mirror = nullptr);
+
 // Builds the hierarchy from the layout of a WHOLE graph (world = 1) INTO `out` (cleared first).  Returns "" or an error text.
 std::string build_amg(const Problem& pr, AmgSym& out, const AmgProgress* progress = nullptr);
 

@@ -20,6 +20,7 @@
 //   engine/engine_edit.inc         tsgo_set_edge_information / tsgo_get_edge_information: the information diagonal of listed edges, in place
 //   engine/engine_gnc.inc          tsgo_gnc: graduated non-convexity (truncated least squares), one reweighting pass over the tables per round
 //   engine/engine_testing.inc      tsgo_testing_apply (TSGO_TESTING builds only): the operators PCG applies, read out column by column
+//   engine/sym_testing.inc         (file scope, TSGO_TESTING builds only) the pattern builders of tsgo_sym_kernels.h on caller-given arrays
 //
 // There is NO CPU fallback in this file: every entry point that computes needs a gfx950 device and
 // returns an error otherwise.
@@ -559,6 +560,10 @@ template <typename T> struct Engine : IEngine {
 
 }  // namespace
 
+#ifdef TSGO_TESTING
+#include "engine/sym_testing.inc"
+#endif
+
 struct tsgo_optimizer {
     tsgo_config cfg;
     IEngine* eng = nullptr;
@@ -650,6 +655,16 @@ int tsgo_comm_init_local(tsgo_optimizer* o, tsgo_local_group* g) {
 int tsgo_testing_apply(tsgo_optimizer* o, int32_t which, const double* in, double* out, int32_t n_cols) {
     if (!o) return tsgo::set_error(-1, "tsgo_testing_apply: null handle");
     return o->eng->testing_apply(which, in, out, n_cols);
+}
+int tsgo_testing_sym_scan(int32_t n, const int32_t* in, int32_t* out) { return sym_scan_run(n, in, out); }
+int tsgo_testing_sym_product(int32_t builder, int32_t upper, int32_t n, const int32_t* xptr, const int32_t* xcol, const int32_t* x_alias, int32_t ny, int32_t nc,
+                             const int32_t* yptr, const int32_t* ycol, tsgo_testing_sym_out* out) {
+    return sym_product_run(builder, upper, n, xptr, xcol, x_alias, ny, nc, yptr, ycol, out);
+}
+int tsgo_testing_schur_pattern(int32_t builder, int32_t P, int32_t L, const int32_t* pp_ptr, const int32_t* pp_lm, const uint32_t* pp_slot, const int32_t* obs_ptr,
+                               const int32_t* obs_pose, const uint32_t* obs_slot, const int32_t* od_ptr, const int32_t* od_col, const uint32_t* od_slot,
+                               int32_t max_pair_degree, tsgo_testing_schur_out* out) {
+    return schur_pattern_run(builder, P, L, pp_ptr, pp_lm, pp_slot, obs_ptr, obs_pose, obs_slot, od_ptr, od_col, od_slot, max_pair_degree, out);
 }
 #endif
 int tsgo_marginals(tsgo_optimizer* o, const uint32_t* ids, int32_t n_ids, double rel_tol, double* cov_out, tsgo_marginal_stats* stats) {

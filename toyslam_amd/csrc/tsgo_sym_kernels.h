@@ -14,10 +14,20 @@
 //                 list offsets; then the pairs themselves, X blocks one after the other (a Y row has every column once, so the
 //                 lanes that share an X block never meet in one output block): within an output block the pairs are in (x, y)
 //                 walking order — the order the host builder produces, so the two builders' lists are IDENTICAL, entry by
-//                 entry (tests compare them), and everything computed from them is bit for bit the same.
+//                 entry, and everything computed from them is bit for bit the same.  tests/test_gpu_sym_patterns.py compares
+//                 them: every kernel of this file on caller-given patterns (include/tsgo_testing.h: tsgo_testing_sym_scan,
+//                 tsgo_testing_sym_product, tsgo_testing_schur_pattern) against the host builder and against a reference
+//                 written from the definition (tests/sym_patterns.py), list by list, at the table edges.
 //   k_sym_mirror  UPPER: mirror index of every block below the diagonal (binary search in the mirror's row), -1 elsewhere
 //
 // Rows whose distinct columns overflow the LDS table (kSymTable / 2) raise a flag: the caller falls back to the host builder.
+//
+// Preconditions (the engine's inputs meet them; the testing entry points refuse anything else): every column index lies inside
+// its matrix, a Y row holds every column once, and every total (blocks, pairs) stays below 2^31 — k_sym_scan returns int, where
+// the host builder refuses ("exceed 2^31 pairs") a device count would wrap.
+//
+// Launch geometry: the launch_* helpers below each kernel are the ONLY launches of these kernels — the engine
+// (engine/engine_hierarchy.inc) and the testing driver (engine/sym_testing.inc) both go through them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -82,6 +92,11 @@ __global__ __launch_bounds__(kSymWave) void k_sym_count(int n, const int* __rest
     if (lane == 0) { d[i] = distinct; m[i] = pairs; }
 }
 
+template <int UPPER>
+inline void launch_sym_count(hipStream_t st, int n, const int* xptr, const int* xcol, const int* yptr, const int* ycol, int* d, int* m, int* overflow) {
+    hipLaunchKernelGGL((k_sym_count<UPPER>), dim3(n), dim3(kSymWave), 0, st, n, xptr, xcol, yptr, ycol, d, m, overflow);
+}
+
 // exclusive scan of n ints by ONE workgroup (n is at most a few million: a row count or a block count); out has n + 1 entries
 __global__ __launch_bounds__(1024) void k_sym_scan(int n, const int* __restrict__ in, int* __restrict__ out) {
     __shared__ long long part[1024];
@@ -98,6 +113,8 @@ __global__ __launch_bounds__(1024) void k_sym_scan(int n, const int* __restrict_
     for (long long k = b; k < e; ++k) { out[k] = (int)run; run += in[k]; }
     if (t == 1023) out[n] = (int)run;       // the last thread's chunk ends at n (possibly empty): run = the total
 }
+
+inline void launch_sym_scan(hipStream_t st, int n, const int* in, int* out) { hipLaunchKernelGGL(k_sym_scan, dim3(1), dim3(1024), 0, st, n, in, out); }
 
 // in-LDS bitonic sort of v[0 .. size) (size a power of two) by one wavefront
 __device__ __forceinline__ void sym_sort(int* v, int size, int lane) {
@@ -184,6 +201,12 @@ __global__ __launch_bounds__(kSymWave) void k_sym_fill(int n, const int* __restr
     }
 }
 
+template <int UPPER>
+inline void launch_sym_fill(hipStream_t st, int n, const int* xptr, const int* xcol, const int* x_alias, const int* yptr, const int* ycol, const int* zptr, const int* poff,
+                            int* zcol, int* pl_ptr, int* px, int* py, int* n_upper) {
+    hipLaunchKernelGGL((k_sym_fill<UPPER>), dim3(n), dim3(kSymWave), 0, st, n, xptr, xcol, x_alias, yptr, ycol, zptr, poff, zcol, pl_ptr, px, py, n_upper);
+}
+
 // blocks on or above the diagonal per row of a pattern with sorted rows (level 0 of the hierarchy: k_schur_blocks sums those only)
 __global__ __launch_bounds__(256) void k_count_upper(int n, const int* __restrict__ zptr, const int* __restrict__ zcol, int* __restrict__ nup) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -193,12 +216,20 @@ __global__ __launch_bounds__(256) void k_count_upper(int n, const int* __restric
     nup[i] = u;
 }
 
+inline void launch_count_upper(hipStream_t st, int n, const int* zptr, const int* zcol, int* nup) {
+    hipLaunchKernelGGL(k_count_upper, dim3((n + 255) / 256), dim3(256), 0, st, n, zptr, zcol, nup);
+}
+
 // lower_of[u] = the block below the diagonal whose mirror u is (-1: a diagonal block), from mirror[] of k_sym_mirror
 __global__ __launch_bounds__(256) void k_invert_mirror(int nnz, const int* __restrict__ mirror, int* __restrict__ lower_of) {
     const int z = blockIdx.x * 256 + threadIdx.x;
     if (z >= nnz) return;
     const int m = mirror[z];
     if (m >= 0) lower_of[m] = z;
+}
+
+inline void launch_invert_mirror(hipStream_t st, int nnz, const int* mirror, int* lower_of) {
+    hipLaunchKernelGGL(k_invert_mirror, dim3((nnz + 255) / 256), dim3(256), 0, st, nnz, mirror, lower_of);
 }
 
 // UPPER products: mirror[z] = the block (c, i) for a block z = (i, c) below the diagonal, -1 on or above it; upper[u] = the
@@ -216,6 +247,9 @@ __global__ __launch_bounds__(256) void k_sym_mirror(int n, const int* __restrict
         if (lo < zptr[c + 1] && zcol[lo] == i) mirror[z] = lo; else { mirror[z] = -1; *bad = 1; }      // not structurally symmetric
     }
 }
+inline void launch_sym_mirror(hipStream_t st, int n, const int* zptr, const int* zcol, const int* uoff, int* mirror, int* upper, int* bad) {
+    hipLaunchKernelGGL(k_sym_mirror, dim3((n + 255) / 256), dim3(256), 0, st, n, zptr, zcol, uoff, mirror, upper, bad);
+}
 
 }  // namespace tsgo
 
@@ -226,6 +260,9 @@ __global__ __launch_bounds__(256) void k_sym_mirror(int n, const int* __restrict
 // Inputs are three CSR lists the host lays out in parallel: a pose's LM edges (landmark, by_pose slot; slots ascending), a
 // landmark's observers (pose, by_pose slot of that edge), a pose's odometry slots (other pose, slot; slots ascending).
 // Lists come out sorted as the host sorts them: pairs by (slot of i, slot of k), odometry slots ascending.
+// Contract on the observer lists: the entries of ONE pose in ONE landmark's list (an edge given twice) come with ascending slots.
+// k_s0_fill keeps their list order where the host sorts by the slot of k; host/problem.cpp fills both tables in edge order and
+// slot_of() rises with the entry's rank, so by_lm's walking order and the by_pose slots of one pose's edges rise together.
 namespace tsgo {
 
 __global__ __launch_bounds__(kSymWave) void k_s0_count(int P, const int* __restrict__ pp_ptr, const int* __restrict__ pp_lm, const int* __restrict__ obs_ptr,
@@ -259,6 +296,10 @@ __global__ __launch_bounds__(kSymWave) void k_s0_count(int P, const int* __restr
     // plus odometry or loop-closure neighbours that are not among them): the host builder takes such a graph
     if (distinct > kSymMaxDistinct) { if (lane == 0) *overflow = 1; return; }
     if (lane == 0) { d[i] = distinct; m[i] = pairs; mo[i] = odn; }
+}
+inline void launch_s0_count(hipStream_t st, int P, const int* pp_ptr, const int* pp_lm, const int* obs_ptr, const int* obs_pose, const int* od_ptr, const int* od_col, int max_deg,
+                            int* d, int* m, int* mo, int* overflow) {
+    hipLaunchKernelGGL(k_s0_count, dim3(P), dim3(kSymWave), 0, st, P, pp_ptr, pp_lm, obs_ptr, obs_pose, od_ptr, od_col, max_deg, d, m, mo, overflow);
 }
 
 __global__ __launch_bounds__(kSymWave) void k_s0_fill(int P, const int* __restrict__ pp_ptr, const int* __restrict__ pp_lm, const uint32_t* __restrict__ pp_slot,
@@ -344,6 +385,12 @@ __global__ __launch_bounds__(kSymWave) void k_s0_fill(int P, const int* __restri
     }
     if (lane == 0)
         for (int e = od_ptr[i]; e < od_ptr[i + 1]; ++e) { const int r = vals[sym_find(keys, od_col[e])]; os[cnt_od[r]++] = od_slot[e]; }
+}
+inline void launch_s0_fill(hipStream_t st, int P, const int* pp_ptr, const int* pp_lm, const uint32_t* pp_slot, const int* obs_ptr, const int* obs_pose, const uint32_t* obs_slot,
+                           const int* od_ptr, const int* od_col, const uint32_t* od_slot, int max_deg, const int* zptr, const int* poff, const int* ooff, int* zcol, int* sc_ptr,
+                           int* sc_optr, uint32_t* slot_i, uint32_t* slot_k, uint32_t* os) {
+    hipLaunchKernelGGL(k_s0_fill, dim3(P), dim3(kSymWave), 0, st, P, pp_ptr, pp_lm, pp_slot, obs_ptr, obs_pose, obs_slot, od_ptr, od_col, od_slot, max_deg, zptr, poff, ooff, zcol,
+                       sc_ptr, sc_optr, slot_i, slot_k, os);
 }
 
 }  // namespace tsgo
