@@ -1,6 +1,6 @@
 // engine/engine_gnc.inc — part of `template <typename T> struct Engine` (tsgo_hip.hip includes it INSIDE the class body):
 // tsgo_gnc.  Graduated non-convexity with the truncated-least-squares surrogate (DESIGN.md section 18): per round ONE pass of
-// k_gnc_reweight (tsgo_gnc_kernels.h) over the tables the edge report walks — evaluate, weight, scatter into the slots the edit knows —
+// k_gnc_reweight (tsgo_gnc_kernels.h; the once-per-edge walk of tsgo_edge_walk.h) — evaluate, weight, scatter into the slots the edit knows —
 // then the handle's own optimize().  Per round one GncPartial per workgroup comes back; the weights cross the bus once, at the end, and
 // only when the caller asks for them or a pose prior's host mirror needs them.
 //
@@ -18,10 +18,9 @@
                 if (report_lm_priors()) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
                     launch(k_gnc_reweight_lm_prior<T, g, pb>, nbL, tl, (const T*)lmrec, (const uint32_t*)maps.rep_pl_edge, part + nbP, lm_prior_args(), ga, edit_tables());
                 });
-                pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) {
-                    launch(k_gnc_reweight<T, g, general, pri, pb>, nbP, tp, to, (const T*)ps, (const T*)lmrec, (const uint32_t*)maps.rep_lm_edge, (const uint32_t*)maps.rep_od_edge,
-                           (const uint32_t*)maps.rep_pp_edge, part, pri ? pose_prior_args() : no_priors(), ga, edit_tables());
-                }); }); });
+                pick_edge_walk([&](auto g, auto general, auto pri) {
+                    launch(k_gnc_reweight<T, g, general, pri, pb>, nbP, tp, to, (const T*)ps, (const T*)lmrec, maps.edge_maps(), part, pri ? pose_prior_args() : no_priors(), ga, edit_tables());
+                });
             });
         }
     }

@@ -115,7 +115,7 @@
                     case 3: launch_lin_lm(); break;
                     case 4: launch_lin_pose_only(); break;
                     case 7: if (!lm_rules()) return set_error(-1, "tsgo_time_kernel: 7 (the chi^2-only pass) needs a handle created with rules = 2"); launch_chi2(lm_red); break;
-                    case 8: launch_report(nullptr); break;
+                    case 8: launch_edge_report(nullptr); break;
                     case 6: if (amg_on) { if (int rc = launch_amg_setup()) return rc; } break;
                     default: if (int rc = launch_iteration(0)) return rc; if (int rc = launch_iteration(1)) return rc; break;
                 }

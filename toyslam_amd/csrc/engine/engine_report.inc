@@ -1,5 +1,5 @@
 // engine/engine_report.inc — part of `template <typename T> struct Engine` (tsgo_hip.hip includes it INSIDE the class body):
-// tsgo_edge_report.  One pass of k_edge_report (tsgo_report_kernels.h) over the handle's tables at its current estimates, on the handle's
+// tsgo_edge_report.  One pass of k_edge_report (tsgo_report_kernels.h; the once-per-edge walk of tsgo_edge_walk.h) at the handle's current estimates, on its
 // stream: per-edge records (e, s, rho, w) in input edge order and / or the per-class summary (DESIGN.md section 14).
 //
 // State rule (that of tsgo_marginals): the pass READS estimates, tables and prior records and writes only buffers of its own — the
@@ -23,15 +23,18 @@
         maps.rep_ready = true;
         return 0;
     }
+    // the template axes of walk_edges_once (tsgo_edge_walk.h) for this handle: f(g, general, pri) — lanes per pose, general pairs, priors
+    template <typename F> void pick_edge_walk(F&& f) {
+        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) { f(g, general, pri); }); }); });
+    }
     // the pass (tsgo_time_kernel 8 too).  rec = nullptr: summary only
-    void launch_report(T* rec) {
+    void launch_edge_report(T* rec) {
         if (report_lm_priors()) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(rk(), [&](auto rk) {
             launch(k_edge_report_lm_prior<T, g, rk>, nbL, tl, (const T*)lmrec, (const uint32_t*)maps.rep_pl_edge, rec, maps.rep_part + (size_t)nbP * kEdgeClasses, lm_prior_args(), robust_args());
         }); });
-        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick<0, 1>(rk(), [&](auto rk) {
-            launch(k_edge_report<T, g, general, pri, rk>, nbP, tp, to, (const T*)ps, (const T*)lmrec, (const uint32_t*)maps.rep_lm_edge, (const uint32_t*)maps.rep_od_edge,
-                   (const uint32_t*)maps.rep_pp_edge, rec, maps.rep_part, pri ? pose_prior_args() : no_priors(), robust_args());
-        }); }); }); });
+        pick_edge_walk([&](auto g, auto general, auto pri) { pick<0, 1>(rk(), [&](auto rk) {
+            launch(k_edge_report<T, g, general, pri, rk>, nbP, tp, to, (const T*)ps, (const T*)lmrec, maps.edge_maps(), rec, maps.rep_part, pri ? pose_prior_args() : no_priors(), robust_args());
+        }); });
     }
     // what k_chi2 reads, 4 B of map per evaluated slot, the partials; with records 6 numbers per edge more
     double bytes_report(bool records) {
@@ -52,7 +55,7 @@
         CallScratch records; T* rec_dev = nullptr;
         if (rec_out && E > 0) records.want(&rec_dev, 6 * E * sizeof(T));
         if (int rc = records.commit()) return rc;
-        launch_report(rec_dev);
+        launch_edge_report(rec_dev);
         HIP_OK(hipGetLastError());
         const size_t n_main = (size_t)nbP * kEdgeClasses, n_lp = report_lm_priors() ? (size_t)nbL : 0;
         std::vector<ReportPartial<T>> hp(n_main + n_lp);

@@ -2,19 +2,16 @@
 // evaluate every edge at the current estimates, turn its squared residual into the truncated-least-squares weight of this round's mu
 // (gnc_tls_weight, tsgo_math.h) and scatter w * base into every place the handle keeps the edge's information.  f64 handles only.
 //
-// The walk is k_edge_report's (tsgo_report_kernels.h): walk_of, the LM rows of the by_pose table, the pose-pose rows with an edge evaluated
-// at its FIRST endpoint only (kDirMask slots skipped before anything of the slot but its index word is read), a vertex's pose priors by
-// its head lane, lm_edge / od_edge / pp_edge for the input index; k_gnc_reweight_lm_prior is to it what k_edge_report_lm_prior is to
-// k_edge_report.  The residual comes from the same edge functions under the "none" selection, handed the BASE information of the edge
-// (base[3 e ..], what the handle held when the call started), so s = sum_k base_k e_k^2 is written term for term as edge_record writes it
-// and does not depend on the weight the tables hold at that moment.  The static planes are read for the measurement only: this pass
-// never loads a weight plane.
+// Which lane meets which edge is tsgo_edge_walk.h's: every input edge once, by one lane, and a skipped slot is left before anything of it
+// but its index and map words is read.  What happens there is GncVisitor's: the residual from the edge functions under the "none"
+// selection, handed the BASE information of the edge (base[3 e ..], what the handle held when the call started), so
+// s = sum_k base_k e_k^2 is written term for term as edge_record writes it and does not depend on the weight the tables hold at that
+// moment.  The static planes are read for the measurement only: this pass never loads a weight plane.
 //
-// Single writer.  Every input edge sits in exactly one evaluated slot or prior record (the structure index's check, host/structure_index.h),
-// so it is evaluated by ONE lane.  No lane of this pass reads a weight plane, and the slot at an edge's second endpoint is skipped before
-// its measurement is loaded, so nothing reads what that lane is about to write.  That lane is the only writer of both locations of the
-// edge (the two words of its EdgeSlots entry, tsgo_edit_kernels.h) and of w_buf[e].  Hence plain stores, no atomics, no read-modify-write,
-// and a repeated launch at the same estimates and mu writes the same bits.
+// Single writer.  One lane visits edge e.  No lane of this pass reads a weight plane, and the walk leaves the slot at the edge's second
+// endpoint before its measurement is loaded, so nothing reads what that lane is about to write.  That lane is the only writer of both
+// locations of the edge (the two words of its EdgeSlots entry, tsgo_edit_kernels.h) and of w_buf[e].  Hence plain stores, no atomics, no
+// read-modify-write, and a repeated launch at the same estimates and mu writes the same bits.
 //
 // Subject edges: barc2[class] > 0 and (subject == nullptr or subject[e] != 0).  An exempt edge gets w_buf[e] = 1 and none of its
 // information is written; a dormant subject edge (base 0) has s = 0, w = 1 and is rewritten as 0.
@@ -23,6 +20,7 @@
 // counts of weights that are 0, 1 and in between — folded across lanes and waves as ReportAcc is and on the host in workgroup order in
 // f64.  The counts are integers and the max is a max: neither depends on the lanes per vertex or on the fold order.
 #pragma once
+#include "tsgo_edge_walk.h"
 #include "tsgo_edit_kernels.h"
 #include "tsgo_kernels.h"
 
@@ -86,83 +84,80 @@ template <typename T, int PROBE> __device__ __forceinline__ void gnc_edge(const 
     ga.w_buf[e] = w;
 }
 
-// Landmark priors (edge type 4): k_edge_report_lm_prior's walk; one GncPartial per workgroup into out[blockIdx.x].  Graphs with priors only.
+// The visit: the slot's measurement planes (the record's measurement), the base information of e, the edge function, gnc_edge.
+template <typename T> __device__ __forceinline__ T gnc_base(const GncArgs& ga, uint32_t e, int m) { return (T)ga.base[3 * (size_t)e + m]; }
+
+// classes 0 .. 3 (walk_edges_once)
+template <typename T, int PROBE> struct GncVisitor {
+    const Table<T>& tb;
+    const Table<T>& od;
+    const GncArgs& ga;
+    const EditTables<T>& et;
+    const Robust<T> none{kRobustNone, T(0)};
+    GncAcc acc;
+    __device__ __forceinline__ T base(uint32_t e, int m) const { return gnc_base<T>(ga, e, m); }
+    __device__ __forceinline__ void put(uint32_t e, const EdgeRecord<T>& r) { gnc_edge<T, PROBE>(ga, et, e, r, acc); }
+    __device__ __forceinline__ void lm(uint32_t e, size_t k, const PoseAt<T>& p, T lx, T ly) {
+        const auto zz = ld2<T>(tb.st + 2 * k);      // the measurement pair alone: the weight pair behind it is this lane's to write
+        const T w0 = base(e, 0), w1 = base(e, 1);
+        put(e, edge_record<T>(lm_linearize<T>(p.x, p.y, p.c, p.s, lx, ly, zz.x, zz.y, w0, w1, none), w0, w1, none));
+    }
+    __device__ __forceinline__ void odom_planes(size_t k, T (&mi)[6]) const {
+#pragma unroll
+        for (int m = 0; m < 6; ++m) mi[m] = od.st[(size_t)(OD_MI0 + m) * od.slots + k];
+    }
+    __device__ __forceinline__ void odom(uint32_t e, size_t k, const PoseAt<T>& p, const T* qj) {
+        T mi[6]; odom_planes(k, mi);
+        const PoseAt<T> pj = pose_at<T>(qj);
+        const T w[3] = {base(e, 0), base(e, 1), base(e, 2)};
+        put(e, edge_record<T>(odom_linearize<T>(p.x, p.y, p.c, p.s, pj.x, pj.y, pj.c, pj.s, mi, w, none), w, none));
+    }
+    __device__ __forceinline__ void vlm(uint32_t e, size_t k, const PoseAt<T>& p, const T* qj) {
+        T mi[6]; odom_planes(k, mi);
+        const PoseAt<T> pj = pose_at<T>(qj);
+        const T w0 = base(e, 0), w1 = base(e, 1);
+        put(e, edge_record<T>(vlm_linearize<T>(p.x, p.y, p.c, p.s, pj.x, pj.y, pj.c, pj.s, mi[0], mi[1], mi[2], mi[3], w0, w1, none), w0, w1, none));
+    }
+    __device__ __forceinline__ void pose_prior(uint32_t e, const T* q, const PoseAt<T>& p) {
+        const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C);
+        const T w0 = base(e, 0), w1 = base(e, 1), w2 = base(e, 2);
+        put(e, edge_record<T>(pose_prior_linearize<T>(m01.x, m01.y, cs.x, cs.y, w0, w1, w2, p.x, p.y, p.c, p.s, none), w0, w1, w2, none));
+    }
+};
+
+// class 4 (walk_lm_priors_once)
+template <typename T, int PROBE> struct GncLmPriorVisitor {
+    const GncArgs& ga;
+    const EditTables<T>& et;
+    GncAcc acc;
+    __device__ __forceinline__ void lm_prior(uint32_t e, const T* q, T lx, T ly) {
+        const auto m = ld2<T>(q + PRL_MX);
+        const Robust<T> none{kRobustNone, T(0)};
+        const T w0 = gnc_base<T>(ga, e, 0), w1 = gnc_base<T>(ga, e, 1);
+        gnc_edge<T, PROBE>(ga, et, e, edge_record<T>(lm_prior_linearize<T>(m.x, m.y, w0, w1, lx, ly, none), w0, w1, none), acc);
+    }
+};
+
+// Landmark priors (class 4): one GncPartial per workgroup into out[blockIdx.x].  Graphs with priors only.
 template <typename T, int G, int PROBE>
 __global__ __launch_bounds__(kBlock) void k_gnc_reweight_lm_prior(Table<T> tb, const T* __restrict__ lmrec, const uint32_t* __restrict__ pri_edge,
                                                                   GncPartial* __restrict__ out, const PriorArgs<T> pa, const GncArgs ga, EditTables<T> et) {
     __shared__ GncPartial red[kWavesPerBlock];
     const Walk wk = walk_of<G>(tb.n_slices, table_xcd8(tb));
-    const int l = wk.vertex;
-    const Robust<T> none{kRobustNone, T(0)};
-    GncAcc acc;
-    if (wk.live && l < tb.n_vertices && wk.head) {
-        const T lx = lmrec[(size_t)l * kLmRec], ly = lmrec[(size_t)l * kLmRec + 1];
-        for (uint32_t k = pa.off[l]; k < pa.off[l + 1]; ++k) {
-            const uint32_t e = pri_edge[k];
-            const auto m = ld2<T>(pa.rec + (size_t)k * PRI_LM_REC + PRL_MX);
-            const T w0 = (T)ga.base[3 * (size_t)e], w1 = (T)ga.base[3 * (size_t)e + 1];
-            gnc_edge<T, PROBE>(ga, et, e, edge_record<T>(lm_prior_linearize<T>(m.x, m.y, w0, w1, lx, ly, none), w0, w1, none), acc);
-        }
-    }
-    acc.block_store(red, out);
+    GncLmPriorVisitor<T, PROBE> v{ga, et};
+    walk_lm_priors_once<T>(wk, tb, lmrec, pri_edge, pa, v);
+    v.acc.block_store(red, out);
 }
 
-// Classes 0 .. 3 (ODOM, LM, virtual landmark, pose prior): k_edge_report's walk and its axes G, OJ, PRI.
+// Classes 0 .. 3 (ODOM, LM, virtual landmark, pose prior); G, OJ, PRI: the walk's axes.
 template <typename T, int G, int OJ, int PRI, int PROBE>
-__global__ __launch_bounds__(kBlock) void k_gnc_reweight(Table<T> tb, Table<T> od, const T* __restrict__ ps, const T* __restrict__ lmrec,
-                                                         const uint32_t* __restrict__ lm_edge, const uint32_t* __restrict__ od_edge,
-                                                         const uint32_t* __restrict__ pp_edge, GncPartial* __restrict__ out, const PriorArgs<T> pa,
-                                                         const GncArgs ga, EditTables<T> et) {
+__global__ __launch_bounds__(kBlock) void k_gnc_reweight(Table<T> tb, Table<T> od, const T* __restrict__ ps, const T* __restrict__ lmrec, const EdgeMaps maps,
+                                                         GncPartial* __restrict__ out, const PriorArgs<T> pa, const GncArgs ga, EditTables<T> et) {
     __shared__ GncPartial red[kWavesPerBlock];
     const Walk wk = walk_of<G>(tb.n_slices, table_xcd8(tb));
-    const int slice = wk.slice, lane = wk.lane, i = wk.vertex;
-    const bool valid = wk.live && i < tb.n_vertices;
-    const Robust<T> none{kRobustNone, T(0)};
-    GncAcc acc;
-    if (wk.live) {
-        const int ic = valid ? i : tb.n_vertices - 1;
-        const auto q01 = ld2<T>(ps + (size_t)ic * 4), q23 = ld2<T>(ps + (size_t)ic * 4 + 2);
-        const T x0 = q01.x, y0 = q01.y, c = q23.x, s = q23.y;
-        for (uint32_t row = tb.row_off[slice], r1 = tb.row_off[slice + 1]; row < r1; ++row) {
-            const size_t k = (size_t)row * 64 + lane;
-            const uint32_t e = lm_edge[k];
-            if (e == kNoEdge) continue;        // padding
-            const uint32_t l = tb.idx[k];
-            const auto zz = ld2<T>(tb.st + 2 * k);      // the measurement pair alone: the weight pair behind it is this lane's to write
-            const auto l01 = ld2<T>(lmrec + (size_t)l * kLmRec);
-            const T w0 = (T)ga.base[3 * (size_t)e], w1 = (T)ga.base[3 * (size_t)e + 1];
-            gnc_edge<T, PROBE>(ga, et, e, edge_record<T>(lm_linearize<T>(x0, y0, c, s, l01.x, l01.y, zz.x, zz.y, w0, w1, none), w0, w1, none), acc);
-        }
-        for (uint32_t row = od.row_off[slice], r1 = od.row_off[slice + 1]; row < r1; ++row) {
-            const size_t k = (size_t)row * 64 + lane;
-            const uint32_t raw = od.idx[k];
-            if (raw & kDirMask) continue;      // the edge's second endpoint: evaluated, and written, at the first
-            const uint32_t e = od_edge[k];
-            if (e == kNoEdge) continue;        // padding
-            const uint32_t j = raw & kPoseIdxMask;
-            T mi[6];
-#pragma unroll
-            for (int m = 0; m < 6; ++m) mi[m] = od.st[(size_t)(OD_MI0 + m) * od.slots + k];
-            const auto j01 = ld2<T>(ps + (size_t)j * 4), j23 = ld2<T>(ps + (size_t)j * 4 + 2);
-            const T w[3] = {(T)ga.base[3 * (size_t)e], (T)ga.base[3 * (size_t)e + 1], (T)ga.base[3 * (size_t)e + 2]};
-            if (OJ && (raw & kVlmMask))
-                gnc_edge<T, PROBE>(ga, et, e, edge_record<T>(vlm_linearize<T>(x0, y0, c, s, j01.x, j01.y, j23.x, j23.y, mi[0], mi[1], mi[2], mi[3], w[0], w[1], none), w[0], w[1], none), acc);
-            else
-                gnc_edge<T, PROBE>(ga, et, e, edge_record<T>(odom_linearize<T>(x0, y0, c, s, j01.x, j01.y, j23.x, j23.y, mi, w, none), w, none), acc);
-        }
-        if constexpr (PRI != 0) {
-            if (valid && wk.head) {
-                for (uint32_t k = pa.off[i]; k < pa.off[i + 1]; ++k) {
-                    const T* q = pa.rec + (size_t)k * PRI_POSE_REC;
-                    const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C);
-                    const uint32_t e = pp_edge[k];
-                    const T w0 = (T)ga.base[3 * (size_t)e], w1 = (T)ga.base[3 * (size_t)e + 1], w2 = (T)ga.base[3 * (size_t)e + 2];
-                    gnc_edge<T, PROBE>(ga, et, e, edge_record<T>(pose_prior_linearize<T>(m01.x, m01.y, cs.x, cs.y, w0, w1, w2, x0, y0, c, s, none), w0, w1, w2, none), acc);
-                }
-            }
-        }
-    }
-    acc.block_store(red, out);
+    GncVisitor<T, PROBE> v{tb, od, ga, et};
+    walk_edges_once<T, OJ, PRI>(wk, tb, od, ps, lmrec, maps, pa, v);
+    v.acc.block_store(red, out);
 }
 
 }  // namespace tsgo

@@ -15,6 +15,10 @@
 //   host/batch_plan.h              (host only, no HIP) how the readers cut their columns into batches; the gate's per-batch lists
 //   engine/engine_sample.inc       tsgo_sample_marginals: posterior samples by perturb-and-MAP and every vertex's covariance from their second moments
 //   engine/engine_report.inc       tsgo_edge_report: per-edge residual records and the per-class summary
+//   tsgo_edge_walk.h               (device only) the once-per-edge walk of the reader kernels, shared by the report and GNC passes: every input edge is visited by ONE lane
+//                                  (pose-pose edges at their first endpoint, padding never), and a skipped slot is left before anything but its index and map words is
+//                                  read — why those passes write per edge with plain stores.  k_chi2 / k_lin_pose (and their landmark twins) intentionally do NOT use it:
+//                                  they have no slot -> edge maps, count padding through its zero weight, and must agree with each other on chi^2 bit for bit
 //   engine/engine_gate.inc         tsgo_gate_edges: candidate edges against the joint marginal of their vertices (Mahalanobis gate)
 //   engine/engine_init.inc         tsgo_init_estimates: estimates from an odometry spanning tree (pointer jumping), landmarks from their observations
 //   engine/engine_edit.inc         tsgo_set_edge_information / tsgo_get_edge_information: the information diagonal of listed edges, in place
@@ -328,6 +332,7 @@ template <typename T> struct Engine : IEngine {
         uint32_t *rep_lm_edge = nullptr, *rep_od_edge = nullptr, *rep_pp_edge = nullptr, *rep_pl_edge = nullptr;
         ReportPartial<T>* rep_part = nullptr;      // [nbP][kEdgeClasses] of k_edge_report, then [nbL] of k_edge_report_lm_prior
         bool rep_ready = false;
+        EdgeMaps edge_maps() const { return EdgeMaps{rep_lm_edge, rep_od_edge, rep_pp_edge}; }      // what walk_edges_once takes (tsgo_edge_walk.h)
         // tsgo_set / get_edge_information (engine_edit.inc): EdgeSlots::loc and cls on the device
         uint32_t* edit_map = nullptr;              // [2 E]
         uint8_t* edit_cls = nullptr;               // [E]

@@ -935,8 +935,8 @@ __global__ __launch_bounds__(kBlock) void k_save_update(int P, int n_max, const 
     pose_update_body<T>(P, x, ps, theta, step, norm_part, red);
 }
 
-// Step report (Engine::launch_report / wait_report): ONE workgroup copies n partials into pinned host memory with plain coalesced
-// stores, fences at system scope, and one lane then publishes the report's 64-bit sequence number with a system-scope release store,
+// Step report (Engine::launch_report / wait_report; not the per-edge report, whose launcher is launch_edge_report): ONE workgroup
+// copies n partials into pinned host memory with plain coalesced stores, fences at system scope, and one lane then publishes the report's 64-bit sequence number with a system-scope release store,
 // the form in which iter_gate_body publishes a gate.  The host thread polls the word and then sums the partials in the order it
 // always did.  The kernel waits for nothing.
 template <typename T>

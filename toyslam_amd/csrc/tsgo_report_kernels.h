@@ -1,20 +1,19 @@
 // tsgo_report_kernels.h — the per-edge residual report (tsgo_edge_report, include/tsgo.h; engine/engine_report.inc).
 //
 // One pass over the graph at the current estimates that keeps what every linearisation computes per edge and folds away: the residual e,
-// s = e^T Omega e with the RAW information, rho(s) and the robust scale w = rho'(s) of the edge's class.  k_edge_report makes k_chi2's walk
-// (tsgo_lm_kernels.h): walk_of, the LM rows of the by_pose table through lm_meas, the pose-pose rows of the odom table through odom_meas
-// with an edge evaluated at its FIRST endpoint only (kDirMask slots skipped, kVlmMask slots to vlm_linearize), a vertex's pose priors by
-// its head lane; k_edge_report_lm_prior is to it what k_chi2_lm_prior is to k_chi2.  The residual arithmetic is not restated: the same edge
-// functions with the same robust_class<RK> selection, and edge_record (tsgo_math.h) for the record.
+// s = e^T Omega e with the RAW information, rho(s) and the robust scale w = rho'(s) of the edge's class.  Which lane meets which edge is
+// tsgo_edge_walk.h's (every input edge once, by one lane); what happens there is ReportVisitor's: the slot's measurement and weights
+// through lm_meas / odom_meas, the prior record's own, the edge functions of the linearisation with the same robust_class<RK> selection,
+// and edge_record (tsgo_math.h) for the record.  The residual arithmetic is not restated.
 //
-// Output.  A live slot k writes its six numbers to rec[6 * edge_of_slot[k]] (three pair stores: 48 B in f64, 16-byte aligned): the
-// slot -> input-edge maps are the host layout's (SellTable::edge, Problem::prior_*_edge), every input edge sits in exactly one evaluated
-// slot, so every record is written once, by one lane, with plain stores.  Padding slots (kNoEdge) write nothing and count nothing.
+// Output.  The lane that visits edge e writes its six numbers to rec[6 * e] (three pair stores: 48 B in f64, 16-byte aligned): one
+// visit per edge, so every record is written once, with plain stores.  Padding is never visited: it writes nothing and counts nothing.
 // rec == nullptr: summary only.  In the same pass every workgroup writes one ReportPartial per edge class — count, down-weighted count,
 // sum of s, sum of rho, the largest s and its edge — which the host folds in workgroup order in f64.  The arg-max rule (the largest s; among
 // equal ones the LOWEST input index) is the same total order in a lane, across a wave, across the waves of a workgroup and on the host,
 // so the edge reported does not depend on the layout.  No atomics.
 #pragma once
+#include "tsgo_edge_walk.h"
 #include "tsgo_kernels.h"
 
 namespace tsgo {
@@ -53,26 +52,64 @@ template <typename T> __device__ __forceinline__ void record_store(T* __restrict
     st2<T>(q, r.e0, r.e1); st2<T>(q + 2, r.e2, r.s); st2<T>(q + 4, r.rho, r.w);
 }
 
-// Landmark priors (edge type 4): k_chi2_lm_prior's walk; one ReportPartial (class 4) per workgroup into out[blockIdx.x].  Graphs with priors only.
+// What the lane that visits an edge does with it: the edge function of the edge's class on the slot's (the record's) own measurement and
+// weights, the record into the class's accumulator and, with rec, into rec[6 e].
+// classes 0 .. 3 (walk_edges_once)
+template <typename T, int RK> struct ReportVisitor {
+    using Kernel = decltype(robust_class<RK>(RobustArgs<T>{}, 0));
+    const Table<T>& tb;
+    const Table<T>& od;
+    const RobustArgs<T>& ra;
+    T* __restrict__ rec;
+    const Kernel rk_lm = robust_class<RK>(ra, kClassLm), rk_odom = robust_class<RK>(ra, kClassOdom);
+    ReportAcc<T> acc[kEdgeClasses];      // the fifth stays empty
+    __device__ __forceinline__ void put(int cls, uint32_t e, const EdgeRecord<T>& r) { acc[cls].add(r, e); if (rec) record_store<T>(rec, e, r); }
+    __device__ __forceinline__ void lm(uint32_t e, size_t k, const PoseAt<T>& p, T lx, T ly) {
+        const LmMeas<T> z = lm_meas<T>(tb, k);
+        put(kClassLm, e, edge_record<T>(lm_linearize<T>(p.x, p.y, p.c, p.s, lx, ly, z.zx, z.zy, z.w0, z.w1, rk_lm), z.w0, z.w1, rk_lm));
+    }
+    __device__ __forceinline__ void odom(uint32_t e, size_t k, const PoseAt<T>& p, const T* qj) {
+        const OdomMeas<T> z = odom_meas<T>(od, k);
+        const PoseAt<T> pj = pose_at<T>(qj);
+        put(kClassOdom, e, edge_record<T>(odom_linearize<T>(p.x, p.y, p.c, p.s, pj.x, pj.y, pj.c, pj.s, z.mi, z.w, rk_odom), z.w, rk_odom));
+    }
+    __device__ __forceinline__ void vlm(uint32_t e, size_t k, const PoseAt<T>& p, const T* qj) {
+        const OdomMeas<T> z = odom_meas<T>(od, k);
+        const PoseAt<T> pj = pose_at<T>(qj);
+        const auto rk = robust_class<RK>(ra, kClassVlm);
+        put(kClassVlm, e, edge_record<T>(vlm_linearize<T>(p.x, p.y, p.c, p.s, pj.x, pj.y, pj.c, pj.s, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1], rk), z.w[0], z.w[1], rk));
+    }
+    __device__ __forceinline__ void pose_prior(uint32_t e, const T* q, const PoseAt<T>& p) {
+        const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C), w01 = ld2<T>(q + PRI_W0);
+        const T w2 = q[PRI_W2];
+        const auto rk = robust_class<RK>(ra, kClassPosePrior);
+        put(kClassPosePrior, e, edge_record<T>(pose_prior_linearize<T>(m01.x, m01.y, cs.x, cs.y, w01.x, w01.y, w2, p.x, p.y, p.c, p.s, rk), w01.x, w01.y, w2, rk));
+    }
+};
+
+// class 4 (walk_lm_priors_once)
+template <typename T, int RK> struct ReportLmPriorVisitor {
+    const RobustArgs<T>& ra;
+    T* __restrict__ rec;
+    ReportAcc<T> acc;
+    __device__ __forceinline__ void lm_prior(uint32_t e, const T* q, T lx, T ly) {
+        const auto m = ld2<T>(q + PRL_MX), w = ld2<T>(q + PRL_W0);
+        const auto rk = robust_class<RK>(ra, kClassLmPrior);
+        const EdgeRecord<T> r = edge_record<T>(lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly, rk), w.x, w.y, rk);
+        acc.add(r, e);
+        if (rec) record_store<T>(rec, e, r);
+    }
+};
+
+// Landmark priors (class 4): one ReportPartial per workgroup into out[blockIdx.x].  Graphs with priors only.
 template <typename T, int G, int RK = 0>
 __global__ __launch_bounds__(kBlock) void k_edge_report_lm_prior(Table<T> tb, const T* __restrict__ lmrec, const uint32_t* __restrict__ pri_edge,
                                                                  T* __restrict__ rec, ReportPartial<T>* __restrict__ out, const PriorArgs<T> pa, const RobustArgs<T> ra) {
     __shared__ ReportPartial<T> red[kWavesPerBlock];
     const Walk wk = walk_of<G>(tb.n_slices, table_xcd8(tb));
-    const int l = wk.vertex;
-    ReportAcc<T> acc;
-    if (wk.live && l < tb.n_vertices && wk.head) {
-        const T lx = lmrec[(size_t)l * kLmRec], ly = lmrec[(size_t)l * kLmRec + 1];
-        const auto rk = robust_class<RK>(ra, kClassLmPrior);
-        for (uint32_t k = pa.off[l]; k < pa.off[l + 1]; ++k) {
-            const T* q = pa.rec + (size_t)k * PRI_LM_REC;
-            const auto m = ld2<T>(q + PRL_MX), w = ld2<T>(q + PRL_W0);
-            const EdgeRecord<T> r = edge_record<T>(lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly, rk), w.x, w.y, rk);
-            const uint32_t e = pri_edge[k];
-            acc.add(r, e);
-            if (rec) record_store<T>(rec, e, r);
-        }
-    }
+    ReportLmPriorVisitor<T, RK> v{ra, rec};
+    walk_lm_priors_once<T>(wk, tb, lmrec, pri_edge, pa, v);
+    ReportAcc<T>& acc = v.acc;
     acc.wave_fold();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc.p;
     __syncthreads();
@@ -84,72 +121,22 @@ __global__ __launch_bounds__(kBlock) void k_edge_report_lm_prior(Table<T> tb, co
     }
 }
 
-// Classes 0 .. 3 (ODOM, LM, virtual landmark, pose prior): k_chi2's walk and template axes.  lm_edge / od_edge: input edge of every slot of
-// tb / od (kNoEdge = padding), pp_edge: of every pose prior record.  out[blockIdx.x * kEdgeClasses + class]; the fifth entry stays empty
-// here (the landmark priors' partials come from k_edge_report_lm_prior, the host folds both).
+// Classes 0 .. 3 (ODOM, LM, virtual landmark, pose prior); G, OJ, PRI: the walk's axes.  out[blockIdx.x * kEdgeClasses + class]; the fifth
+// entry stays empty here (the landmark priors' partials come from k_edge_report_lm_prior, the host folds both).
 template <typename T, int G, int OJ = 0, int PRI = 0, int RK = 0>
-__global__ __launch_bounds__(kBlock) void k_edge_report(Table<T> tb, Table<T> od, const T* __restrict__ ps, const T* __restrict__ lmrec,
-                                                        const uint32_t* __restrict__ lm_edge, const uint32_t* __restrict__ od_edge,
-                                                        const uint32_t* __restrict__ pp_edge, T* __restrict__ rec, ReportPartial<T>* __restrict__ out,
-                                                        const PriorArgs<T> pa, const RobustArgs<T> ra) {
+__global__ __launch_bounds__(kBlock) void k_edge_report(Table<T> tb, Table<T> od, const T* __restrict__ ps, const T* __restrict__ lmrec, const EdgeMaps maps,
+                                                        T* __restrict__ rec, ReportPartial<T>* __restrict__ out, const PriorArgs<T> pa, const RobustArgs<T> ra) {
     __shared__ ReportPartial<T> red[kWavesPerBlock][kEdgeClasses];
     const Walk wk = walk_of<G>(tb.n_slices, table_xcd8(tb));
-    const int slice = wk.slice, lane = wk.lane, i = wk.vertex;
-    const bool valid = wk.live && i < tb.n_vertices;
-    const auto rk_lm = robust_class<RK>(ra, kClassLm), rk_odom = robust_class<RK>(ra, kClassOdom);
-    ReportAcc<T> a_odom, a_lm, a_vlm, a_pp;
-    if (wk.live) {
-        const int ic = valid ? i : tb.n_vertices - 1;
-        const auto q01 = ld2<T>(ps + (size_t)ic * 4), q23 = ld2<T>(ps + (size_t)ic * 4 + 2);
-        const T x0 = q01.x, y0 = q01.y, c = q23.x, s = q23.y;
-#pragma unroll 2
-        for (uint32_t row = tb.row_off[slice], r1 = tb.row_off[slice + 1]; row < r1; ++row) {
-            const size_t k = (size_t)row * 64 + lane;
-            const uint32_t e = lm_edge[k];
-            const uint32_t l = tb.idx[k];
-            const LmMeas<T> z = lm_meas<T>(tb, k);
-            const auto l01 = ld2<T>(lmrec + (size_t)l * kLmRec);
-            const EdgeRecord<T> r = edge_record<T>(lm_linearize<T>(x0, y0, c, s, l01.x, l01.y, z.zx, z.zy, z.w0, z.w1, rk_lm), z.w0, z.w1, rk_lm);
-            if (e != kNoEdge) { a_lm.add(r, e); if (rec) record_store<T>(rec, e, r); }
-        }
-        for (uint32_t row = od.row_off[slice], r1 = od.row_off[slice + 1]; row < r1; ++row) {
-            const size_t k = (size_t)row * 64 + lane;
-            const uint32_t raw = od.idx[k];
-            if (raw & kDirMask) continue;      // the edge's second endpoint: reported at the first
-            const uint32_t e = od_edge[k];
-            if (e == kNoEdge) continue;        // padding
-            const uint32_t j = raw & kPoseIdxMask;
-            const OdomMeas<T> z = odom_meas<T>(od, k);
-            const auto j01 = ld2<T>(ps + (size_t)j * 4), j23 = ld2<T>(ps + (size_t)j * 4 + 2);
-            if (OJ && (raw & kVlmMask)) {
-                const auto rk_vlm = robust_class<RK>(ra, kClassVlm);
-                const EdgeRecord<T> r = edge_record<T>(vlm_linearize<T>(x0, y0, c, s, j01.x, j01.y, j23.x, j23.y, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1], rk_vlm), z.w[0], z.w[1], rk_vlm);
-                a_vlm.add(r, e); if (rec) record_store<T>(rec, e, r);
-            } else {
-                const EdgeRecord<T> r = edge_record<T>(odom_linearize<T>(x0, y0, c, s, j01.x, j01.y, j23.x, j23.y, z.mi, z.w, rk_odom), z.w, rk_odom);
-                a_odom.add(r, e); if (rec) record_store<T>(rec, e, r);
-            }
-        }
-        if constexpr (PRI != 0) {
-            if (valid && wk.head) {
-                const auto rk_pp = robust_class<RK>(ra, kClassPosePrior);
-                for (uint32_t k = pa.off[i]; k < pa.off[i + 1]; ++k) {
-                    const T* q = pa.rec + (size_t)k * PRI_POSE_REC;
-                    const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C), w01 = ld2<T>(q + PRI_W0);
-                    const T w2 = q[PRI_W2];
-                    const EdgeRecord<T> r = edge_record<T>(pose_prior_linearize<T>(m01.x, m01.y, cs.x, cs.y, w01.x, w01.y, w2, x0, y0, c, s, rk_pp), w01.x, w01.y, w2, rk_pp);
-                    const uint32_t e = pp_edge[k];
-                    a_pp.add(r, e); if (rec) record_store<T>(rec, e, r);
-                }
-            }
-        }
-    }
-    a_odom.wave_fold(); a_lm.wave_fold();
-    if constexpr (OJ != 0) a_vlm.wave_fold();
-    if constexpr (PRI != 0) a_pp.wave_fold();
+    ReportVisitor<T, RK> v{tb, od, ra, rec};
+    walk_edges_once<T, OJ, PRI>(wk, tb, od, ps, lmrec, maps, pa, v);
+    v.acc[kClassOdom].wave_fold(); v.acc[kClassLm].wave_fold();
+    if constexpr (OJ != 0) v.acc[kClassVlm].wave_fold();
+    if constexpr (PRI != 0) v.acc[kClassPosePrior].wave_fold();
     if ((threadIdx.x & 63) == 0) {
         ReportPartial<T>* w = red[threadIdx.x >> 6];
-        w[kClassOdom] = a_odom.p; w[kClassLm] = a_lm.p; w[kClassVlm] = a_vlm.p; w[kClassPosePrior] = a_pp.p; w[kClassLmPrior] = ReportAcc<T>{}.p;
+#pragma unroll
+        for (int c = 0; c < kEdgeClasses; ++c) w[c] = v.acc[c].p;
     }
     __syncthreads();
     if (threadIdx.x < kEdgeClasses) {

@@ -8,7 +8,8 @@
 //                                   added to the call's accumulators over the batch's live columns in ascending order, samples staged
 //
 // The two right-hand-side kernels keep the SELL shape of k_mb_schur_lm / k_mb_schur_pose (one wavefront per slice, G lanes per vertex) and
-// walk the tables the way k_edge_report does, with the same slot -> input-edge maps: a slot regenerates the noise of ITS edge from
+// read the slot -> input-edge maps the once-per-edge readers read (EdgeMaps, tsgo_edge_walk.h) but walk differently, at BOTH endpoints of
+// an edge, so they do not use that header's walk: a slot regenerates the noise of ITS edge from
 // noise(seed, 0, edge, sample) (tsgo_math.h), so an edge's noise is computed once per endpoint and never stored.  A, B and the weights
 // a = w_robust * inf come from the edge functions every linearisation runs (lm_linearize, odom_linearize + odom_jacobians, vlm_linearize,
 // the prior functions) with the handle's robust setting read at run time (Robust<T>; the default setting is Huber 1.5, the arithmetic of
