@@ -233,7 +233,12 @@ int tsgo_get_vertices(tsgo_optimizer* opt, double* v_pos_out);
  * order: diag (9 doubles, the dense diagonal block of H incl. the gauge term, row-major, 2x2 blocks
  * use the leading 2x2) and grad (3 doubles, b = -J^T Omega_w e), plus chi2.
  * tsgo_solve_step additionally solves H delta = b and returns delta (3 doubles per vertex, unscaled)
- * without updating the vertices. */
+ * without updating the vertices.
+ * A solve that reaches tsgo_config.pcg_max_iters before it meets pcg_rel_tol returns -22, and what it had is still read out: delta_out
+ * holds the iterate after pcg_max_iters vector updates (poses: x_k of the PCG started from zero on a handle without history; landmarks:
+ * the back-substitution u - D_l^-1 W^T x_k of that pose part) and *pcg_iters_out equals the cap.  With the multigrid preconditioner on
+ * packed cycle storage (cycle_storage = 16) a capped solve is first repeated on f32 copies of the cycle's operators, and the read-out is
+ * the repeat's; cycle_storage = 32 solves once. */
 int tsgo_linearize(tsgo_optimizer* opt, double* diag_out, double* grad_out, double* chi2_out);
 int tsgo_solve_step(tsgo_optimizer* opt, double* delta_out, double* chi2_out, int32_t* pcg_iters_out);
 

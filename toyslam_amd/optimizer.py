@@ -136,11 +136,14 @@ class HipOptimizer:
                    "tsgo_linearize")
         return diag, grad, chi.value
 
-    def solve_step(self):
+    def solve_step(self, allow_unconverged=False):
+        """One linearisation and one solve (tsgo_solve_step): dict(delta, chi2, cg_iters, rc).  allow_unconverged=True: a solve that
+        stopped at pcg_max_iters (-22) does not raise; delta is then the iterate after cg_iters = pcg_max_iters updates and rc is -22."""
         d = np.zeros((self.n_vertices, 3)); chi = C.c_double(); it = C.c_int32()
-        _lib.check(self.lib, self.lib.tsgo_solve_step(self.h, d.ctypes.data, C.byref(chi), C.byref(it)),
-                   "tsgo_solve_step")
-        return dict(delta=d, chi2=chi.value, cg_iters=it.value)
+        rc = self.lib.tsgo_solve_step(self.h, d.ctypes.data, C.byref(chi), C.byref(it))
+        if not (allow_unconverged and rc == -22):
+            _lib.check(self.lib, rc, "tsgo_solve_step")
+        return dict(delta=d, chi2=chi.value, cg_iters=it.value, rc=rc)
 
     def marginals(self, ids, rel_tol=0.0):
         """Marginal covariances (diagonal blocks of H^-1 at the current estimates) of the vertices `ids`, in order: cov[k] is the 3x3
