@@ -209,6 +209,7 @@
         return launch_bottom_setup();
     }
 
+    static double blocks_per_row(int nnz, int n_rows) { return (double)nnz / std::max(1, n_rows); }      // what lanes_for / lanes_for_sweep take
     static int lanes_for(double avg_row) {
         return avg_row <= 4 ? 4 : (avg_row <= 12 ? 8 : (avg_row <= 40 ? 32 : 64));
     }
@@ -221,7 +222,7 @@
         return lanes_for(avg_row);
     }
     // grids of the block-row kernels: levels with at least kXcdMinBlocks workgroups are rounded up to a multiple of 8 and take the XCD-aware
-    // workgroup map (lpr_block(), tsgo_amg_kernels.h): the surplus workgroups clamp to the last row and write nothing
+    // workgroup map (block_row(), tsgo_block_row.h): the surplus workgroups clamp to the last row and write nothing
     static constexpr int kXcdMinBlocks = 64;
     bool lpr_xcd = true;       // research: TSGO_LPR_XCD=0 keeps the round-robin map everywhere
     int lpr_grid(int n_rows, int lanes, int* xcd) const {
@@ -256,7 +257,7 @@
     template <typename VE, typename VZ> void launch_prolong(size_t level, const VE* e, VZ* z, int zs, const CgState<T>* s) {
         DevLevel<T>& L = lv[level];
         float* z32 = (level == 0 && low_cycle && !explicit0) ? zc32 : (float*)nullptr;      // level 0 prolongs into the pose records: keep their f32 copy current
-        pick_block_row(lanes_for((double)L.nnzP / std::max(1, L.n)), L.n, [&](auto lanes, auto pk, int grid, int xcd) {
+        pick_block_row(lanes_for(blocks_per_row(L.nnzP, L.n)), L.n, [&](auto lanes, auto pk, int grid, int xcd) {
             PF(bytes_transfer(L, 2, level == 0), lvl("prolong into", level).c_str(), "k_prolong_add", tname(), lanes, pk, tname_of<VE>(), tname_of<VZ>());
             launch(k_prolong_add<T, lanes, pk, VE, VZ>, grid, L.n, xcd8(xcd, grid), s, L.P_ptr, L.P_col, (const uint32_t*)L.Ppm, e, z, zs, z32);
         });
@@ -272,7 +273,7 @@
             T* a = pw_a; T* b = pw_b;      // (sized for level 0: every level fits; the power iteration runs in T)
             const int n3 = L.n * 3;
             hipLaunchKernelGGL((k_seed_vector<T>), dim3(grid_for(n3)), dim3(kBlock), 0, stream, n3, a);
-            const int lprA = lanes_for((double)L.nnzA / std::max(1, L.n));
+            const int lprA = lanes_for(blocks_per_row(L.nnzA, L.n));
             for (int it = 0; it < kRhoSteps; ++it) {
                 pick<4, 8, 16, 32, 64>(lprA, [&](auto lanes) {     // the block-indexed matrix (PM = 0): level 0 has no cycle-format copy
                     launch(k_bcsr_residual<T, lanes, 2, 0>, grid_for(L.n, lanes), L.n, 0, (const CgState<T>*)st[0], L.A_ptr, L.A_col, (const void*)L.A, (const T*)a, (const T*)a, (const H*)L.Dinv, b, (const T*)omega_dev);
@@ -311,11 +312,16 @@
     int launch_cycle_product(int slot, const GateArgs<T>* gate = nullptr, bool post_smooth = false, bool as_residual = false) {
         if (!explicit0) return launch_matvec(slot, false, low_cycle, gate, post_smooth, as_residual);
         DevLevel<T>& L = lv[0];
-        pick_block_row(lanes_for_sweep((double)L.nnzA / std::max(1, L.n), L.n), L.n, [&](auto lanes, auto pk, int grid, int xcd) {
+        pick_block_row(lanes_for_sweep(blocks_per_row(L.nnzA, L.n), L.n), L.n, [&](auto lanes, auto pk, int grid, int xcd) {
             PF(bytes_sweep(L), "in-cycle product (explicit)", "k_bcsr_apply", tname(), lanes, pk);
             launch(k_bcsr_apply<T, lanes, pk>, grid, L.n, xcd8(xcd, grid), (const CgState<T>*)st[slot], L.A_ptr, L.A_col, (const uint32_t*)L.Apm, (const T*)zc, kPoseRec, sbuf);
         });
         return 0;
+    }
+    // the dense level alone: z = inv_last r, one workgroup
+    template <typename V> void launch_dense_solve(const V* rhs, V* z, const CgState<T>* s) {
+        PF((double)nb_last * 3 * nb_last * 3 * sizeof(T), "dense solve", "k_dense_apply", tname(), tname_of<V>());
+        hipLaunchKernelGGL((k_dense_apply<T, V>), dim3(1), dim3(kBlock), 0, stream, nb_last * 3, (const T*)inv_last, rhs, z, s);
     }
     // the cycle's vectors below level 0 are V (CV<T>; T under cyc64, testing builds only)
     int launch_vcycle(int slot, const GateArgs<T>* gate = nullptr) {
@@ -335,7 +341,7 @@
         if (int rc = launch_cycle_product(slot, gate, false, res_fused)) return rc;
         {
             DevLevel<T>& L = lv[0];
-            const int lpr = lanes_for((double)L.nnzP / std::max(1, L.n_agg));
+            const int lpr = lanes_for(blocks_per_row(L.nnzP, L.n_agg));
             const H* dnext = (bottom_dense && nl == 2) ? (const H*)nullptr : (nl > 1 ? (const H*)lv[1].Dinv : (const H*)nullptr);      // (nl == 3 with the factored level: lv[1] keeps its pre-sweep)
             if (nl > 1 && res_fused) launch_restrict<0>(0, lpr, (const T*)sbuf, (const T*)sbuf, v(lv[1].r), dnext, v(lv[1].z), (const T*)(omega_dev + 1), s);
             else if (nl > 1) launch_restrict<1>(0, lpr, (const T*)r, (const T*)sbuf, v(lv[1].r), dnext, v(lv[1].z), (const T*)(omega_dev + 1), s);
@@ -348,7 +354,7 @@
         for (size_t l = 1; l < std::min(nl, first_dense); ++l) {
             DevLevel<T>& L = lv[l];
             const int nu = nu_at(l);
-            const int lprA = lanes_for_sweep((double)L.nnzA / std::max(1, L.n), L.n);
+            const int lprA = lanes_for_sweep(blocks_per_row(L.nnzA, L.n), L.n);
             V* cur = v(L.z); V* oth = v(L.z2);
             for (int sw = 1; sw < nu; ++sw) {
                 launch_sweep<1>("pre-sweep", l, lprA, cv(L.r), (const V*)cur, oth, (const T*)(omega_dev + l), s);
@@ -356,7 +362,7 @@
             }
             launch_sweep<0>("residual", l, lprA, cv(L.r), (const V*)cur, v(L.res), (const T*)(omega_dev + l), s);
             if (l + 1 < nl) {
-                const int lpr = lanes_for((double)L.nnzP / std::max(1, L.n_agg));
+                const int lpr = lanes_for(blocks_per_row(L.nnzP, L.n_agg));
                 const bool no_presmooth = dense_bottom && !dense_tail2 && l + 2 == nl;      // the dense bottom operator pre-smooths by itself (the factored level wants z1 = W r)
                 launch_restrict<0>(l, lpr, cv(L.res), cv(L.res), v(lv[l + 1].r), no_presmooth ? (const H*)nullptr : (const H*)lv[l + 1].Dinv, v(lv[l + 1].z), (const T*)(omega_dev + l + 1), s);
             }
@@ -386,15 +392,13 @@
         } else if (nl > 1) {   // a last explicit level too long for the one-workgroup kernel (4 lanes per row): the same three steps as launches
             DevLevel<T>& L = lv[nl - 1];
             launch_restrict<0>(nl - 1, 8, cv(L.res), cv(L.res), v(r_last), (const H*)nullptr, (V*)nullptr, (const T*)one_dev, s);
-            PF((double)nb_last * 3 * nb_last * 3 * sizeof(T), "dense solve", "k_dense_apply", tname(), tname_of<V>());
-            hipLaunchKernelGGL((k_dense_apply<T, V>), dim3(1), dim3(kBlock), 0, stream, nb_last * 3, (const T*)inv_last, cv(r_last), v(z_last), s);
+            launch_dense_solve(cv(r_last), v(z_last), s);
             launch_prolong(nl - 1, cv(z_last), down_iter(L, nu_at(nl - 1)), 3, s);
         } else {        // only level 0 above the dense level: residual r - S z is restricted from (r, sbuf)
             DevLevel<T>& L = lv[0];
             if (res_fused) launch_restrict<0>(0, 8, (const T*)sbuf, (const T*)sbuf, v(r_last), (const H*)nullptr, (V*)nullptr, (const T*)one_dev, s);
             else launch_restrict<1>(0, 8, (const T*)r, (const T*)sbuf, v(r_last), (const H*)nullptr, (V*)nullptr, (const T*)one_dev, s);
-            PF((double)nb_last * 3 * nb_last * 3 * sizeof(T), "dense solve", "k_dense_apply", tname(), tname_of<V>());
-            hipLaunchKernelGGL((k_dense_apply<T, V>), dim3(1), dim3(kBlock), 0, stream, nb_last * 3, (const T*)inv_last, cv(r_last), v(z_last), s);
+            launch_dense_solve(cv(r_last), v(z_last), s);
         }
         for (size_t l = nl - 1; l >= 1; --l) {
             DevLevel<T>& L = lv[l];
@@ -402,7 +406,7 @@
             const int nu = nu_at(l);
             V* cur = down_iter(L, nu); V* oth = down_other(L, nu);
             if (l + 1 < nl) launch_prolong(l, cv(lv[l + 1].z2), cur, 3, s);
-            const int lprA = lanes_for_sweep((double)L.nnzA / std::max(1, L.n), L.n);
+            const int lprA = lanes_for_sweep(blocks_per_row(L.nnzA, L.n), L.n);
             for (int sw = 0; sw < nu; ++sw) {
                 launch_sweep<1>("post-sweep", l, lprA, cv(L.r), (const V*)cur, oth, (const T*)(omega_dev + l), s);
                 std::swap(cur, oth);

@@ -6,10 +6,7 @@
 // 100k poses): those kernels are latency-bound by design and kept deliberately simple; the bytes are
 // in level 0, whose residuals reuse the implicit Schur passes of tsgo_kernels.h.
 #pragma once
-#include <hip/hip_fp16.h>
-#include <hip/hip_runtime.h>
-
-#include "tsgo_kernels.h"
+#include "tsgo_block_row.h"      // 3x3 helpers, the cycle format, the block-row walk of the cycle kernels
 
 namespace tsgo {
 
@@ -34,55 +31,6 @@ template <typename T> using CV = typename CycVec<T>::type;
 
 constexpr int kPairBlocksPerWave = 21;   // k_pair_gemm: three lanes per 3x3 output block
 constexpr int kDenseMax = 84;            // coarsest matrix is at most 84 x 84 (host/amg.h: kCoarsestMax * 3)
-
-template <typename T, typename A, typename B> __device__ __forceinline__ void m3_mul_acc(const A* a, const B* b, T* c) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) c[3 * i + j] += T(a[3 * i]) * T(b[j]) + T(a[3 * i + 1]) * T(b[3 + j]) + T(a[3 * i + 2]) * T(b[6 + j]);
-}
-template <typename T, typename A, typename B> __device__ __forceinline__ void m3_tmul_acc(const A* a, const B* b, T* c) {   // c += a^T b
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) c[3 * i + j] += T(a[i]) * T(b[j]) + T(a[3 + i]) * T(b[3 + j]) + T(a[6 + i]) * T(b[6 + j]);
-}
-template <typename T> __device__ __forceinline__ void m3_inv(const T* m, T* o) {
-    const T c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
-    const T det = m[0] * c00 + m[1] * c01 + m[2] * c02;
-    if (!(fabs(det) > T(0))) { for (int k = 0; k < 9; ++k) o[k] = T(0); return; }
-    const T r = T(1) / det;
-    o[0] = c00 * r; o[1] = (m[2] * m[7] - m[1] * m[8]) * r; o[2] = (m[1] * m[5] - m[2] * m[4]) * r;
-    o[3] = c01 * r; o[4] = (m[0] * m[8] - m[2] * m[6]) * r; o[5] = (m[2] * m[3] - m[0] * m[5]) * r;
-    o[6] = c02 * r; o[7] = (m[1] * m[6] - m[0] * m[7]) * r; o[8] = (m[0] * m[4] - m[1] * m[3]) * r;
-}
-
-// cycle format (described further down, "cycle format"): words per 3x3 block, and the packing of one block
-constexpr int kCyWordsF32 = 9, kCyWordsF16 = 5;
-template <int PK> __host__ __device__ constexpr int cy_words() { return PK ? kCyWordsF16 : kCyWordsF32; }
-// the nine values of one block into its cycle-format words (the j-th block of a row of `len` blocks whose words start at `o` = base + j)
-template <int PK> __device__ __forceinline__ void cy_store(const float* v, uint32_t* __restrict__ o, size_t len) {
-    if (PK) {
-        float mx = 0;
-#pragma unroll
-        for (int m = 0; m < 9; ++m) mx = fmaxf(mx, fabsf(v[m]));
-        int e = 0;
-        if (mx > 0.f && mx < 3.0e38f) {
-            e = ilogbf(mx) - 14;                                  // largest entry -> [2^14, 2^15)
-            e = e < -126 ? -126 : (e > 112 ? 112 : e);            // 2^e and 2^-e stay normal floats
-        }
-        const float inv = __uint_as_float((uint32_t)(127 - e) << 23);
-        unsigned short h[9];
-#pragma unroll
-        for (int m = 0; m < 9; ++m) h[m] = __half_as_ushort(__float2half_rn(v[m] * inv));
-#pragma unroll
-        for (int m = 0; m < 4; ++m) o[(size_t)m * len] = (uint32_t)h[2 * m] | ((uint32_t)h[2 * m + 1] << 16);
-        o[(size_t)4 * len] = (uint32_t)h[8] | ((uint32_t)(unsigned short)(short)e << 16);
-    } else {
-#pragma unroll
-        for (int m = 0; m < 9; ++m) o[(size_t)m * len] = __float_as_uint(v[m]);
-    }
-}
 
 // ---- numeric setup ---------------------------------------------------------------------------------
 // Explicit Schur complement blocks S_ik (level 0 of the hierarchy), one thread per block on or above the diagonal.
@@ -146,13 +94,7 @@ __global__ __launch_bounds__(kBlock) void k_schur_blocks(int nnz, const int* __r
     for (int m = 0; m < 9; ++m) o[m] = -acc[m] + d[m];
     if (lower_of) {
         const int lo = lower_of[b];
-        if (lo >= 0) {
-            HT<T>* q = A + (size_t)lo * 9;
-#pragma unroll
-            for (int x = 0; x < 3; ++x)
-#pragma unroll
-                for (int y = 0; y < 3; ++y) q[3 * x + y] = o[3 * y + x];
-        }
+        if (lo >= 0) m3_transpose(o, A + (size_t)lo * 9);
     }
 }
 
@@ -161,11 +103,9 @@ __global__ __launch_bounds__(kBlock) void k_block_inv(int n, const int* __restri
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     T m[9], o[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) m[k] = A[(size_t)diag[i] * 9 + k];
+    m3_copy(A + (size_t)diag[i] * 9, m);
     m3_inv<T>(m, o);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Dinv[(size_t)i * 9 + k] = o[k];
+    m3_copy(o, Dinv + (size_t)i * 9);
 }
 
 // P = Z - w Dinv (A Z), one thread per P block; Z_k = [[1,0,-ry],[0,1,rx],[0,0,1]] (rigid modes).
@@ -186,13 +126,11 @@ __global__ __launch_bounds__(kBlock) void k_prolongator(int nnzP, const int* __r
         const int k = sy[q];
         const T zk[9] = {T(1), T(0), -rel[(size_t)k * 2 + 1], T(0), T(1), rel[(size_t)k * 2], T(0), T(0), T(1)};
         T a[9];
-#pragma unroll
-        for (int m = 0; m < 9; ++m) a[m] = A[(size_t)sx[q] * 9 + m];
+        m3_copy(A + (size_t)sx[q] * 9, a);
         m3_mul_acc<T>(a, zk, acc);
     }
     T d[9], da[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int m = 0; m < 9; ++m) d[m] = Dinv[(size_t)i * 9 + m];
+    m3_copy(Dinv + (size_t)i * 9, d);
     m3_mul_acc<T>(d, acc, da);
     T o[9];
 #pragma unroll
@@ -201,17 +139,15 @@ __global__ __launch_bounds__(kBlock) void k_prolongator(int nnzP, const int* __r
     // coarse space, otherwise the cycle would inject a null-space component that nothing removes
     const bool dead = d[0] == T(0) && d[4] == T(0) && d[8] == T(0);
     if (p_self[pb] && !dead) { o[0] += T(1); o[4] += T(1); o[8] += T(1); o[2] -= rel[(size_t)i * 2 + 1]; o[5] += rel[(size_t)i * 2]; }
-#pragma unroll
-    for (int m = 0; m < 9; ++m) P[(size_t)pb * 9 + m] = o[m];
+    m3_copy(o, P + (size_t)pb * 9);
     // the same block transposed, stored in the order the restriction walks it (rows of R = P^T):
     // reading P through an index there cost 2.7x the bytes (profiles/r01c: 88 MB for a 33 MB operator)
     const int rb = p_to_r[pb];
-    HT<T>* rt = Rv + (size_t)rb * 9;
-    float vp[9], vr[9];
+    m3_transpose(o, Rv + (size_t)rb * 9);
+    float vp[9], vr[9];      // what the cycle format packs: the blocks as stored
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { rt[3 * i + j] = o[3 * j + i]; vp[3 * i + j] = (float)(HT<T>)o[3 * i + j]; vr[3 * i + j] = (float)(HT<T>)o[3 * j + i]; }
+    for (int m = 0; m < 9; ++m) vp[m] = (float)(HT<T>)o[m];
+    m3_transpose(vp, vr);
     {
         const int p0 = p_ptr[i];
         cy_store<PK>(vp, Ppm + (size_t)p0 * cy_words<PK>() + (pb - p0), (size_t)(p_ptr[i + 1] - p0));
@@ -290,17 +226,6 @@ __global__ __launch_bounds__(kBlock) void k_pair_gemm_wave(int n_out, const int*
     }
 }
 
-// The Galerkin product P^T (A P) is symmetric: only its blocks on and above the diagonal are summed from pair
-// lists; a block below it is the transpose of its mirror (host/amg.h: a_mirror).  One thread per element.
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_mirror_blocks(int n_blocks, const int* __restrict__ mirror, HT<T>* A) {
-    const int t = blockIdx.x * kBlock + threadIdx.x;
-    const int b = t / 9, e = t % 9;
-    if (b >= n_blocks) return;
-    const int m = mirror[b];
-    if (m >= 0) A[(size_t)b * 9 + e] = A[(size_t)m * 9 + (e % 3) * 3 + e / 3];
-}
-
 // Dense inverse of the coarsest matrix in LDS (n <= 84), in-place Gauss-Jordan; SPD so no pivoting.
 // One workgroup of 1024 threads as a 32 x 32 tile walking the matrix.
 constexpr int kDenseThreads = 1024;
@@ -335,53 +260,7 @@ __global__ __launch_bounds__(kDenseThreads) void k_dense_inverse(int nb, const i
     for (int e = threadIdx.x; e < n * n; e += kDenseThreads) inv[e] = M[e];
 }
 
-// ---- cycle format --------------------------------------------------------------------------------------------
-// The setup kernels address 3x3 blocks by block index (36 contiguous bytes, "AoS").  Read that way by the cycle kernels —
-// a lane per block, nine loads — every load instruction of a wavefront touches 36-byte-strided words: 18+ cache lines
-// for 256 useful bytes, and the texture addressers, not the memory system, set the pace (profiles/r01e: L1 tag pipes at
-// 40 %).  The cycle therefore reads a COPY in which the blocks of one row are stored plane-major: word m of the j-th
-// block of row i lives at W * ptr[i] + m * len_i + j, so that lanes j, j+1, ... load consecutive words.  One or two lines per
-// load instruction.  The copy is written once per hierarchy build (k_to_planes, 8 lanes per row).  Two encodings:
-//   PK = 0: W = 9 words, the block's nine f32 values.
-//   PK = 1 (tsgo_config.cycle_storage = 16, default): W = 5 words = nine IEEE half floats + a power-of-two exponent (int16) common
-//           to the block: value_k = half_k * 2^e, e chosen so that the block's largest entry sits in [2^14, 2^15) — eleven
-//           significant bits relative to the block's own maximum whatever its magnitude (gauge blocks of 1e6 next to 1e-3).
-//           20 bytes per block instead of 36 and five loads instead of nine: the sweeps of the big levels are byte-bound at
-//           1 M poses and half byte-, half latency-bound at 100 k.  A block and its mirror (A_ij, A_ji^T) have the same maximum,
-//           hence the same exponent and element-wise the same rounding: the rounded matrix is still symmetric, and because
-//           every use inside the cycle (pre-sweeps, residual, post-sweeps; restriction and prolongation through R = P^T copies of
-//           the same rounded blocks) reads THIS copy, the V-cycle stays a symmetric operator.  The setup (Galerkin products,
-//           diagonal inverses) keeps the f32 blocks.
-// (kCyWordsF32 / kCyWordsF16, cy_words<PK>() and cy_store<PK>() are defined at the top of this file: the set-up kernels write the format too)
-
-// the j-th block of a row whose cycle-format words start at `base` (row length len): its words as stored (cy_fetch: loads only, so
-// that several blocks' words can be requested before any is used), and the words as nine values of type T (cy_decode)
-template <int PK> __device__ __forceinline__ void cy_fetch(const uint32_t* __restrict__ base, size_t len, size_t j, uint32_t* w) {
-    const uint32_t* q = base + j;
-#pragma unroll
-    for (int m = 0; m < cy_words<PK>(); ++m) w[m] = q[(size_t)m * len];
-}
-template <typename T, int PK> __device__ __forceinline__ void cy_decode(const uint32_t* w, T* b) {
-    if (PK) {
-        const int e = (int)(short)(w[4] >> 16);
-        const float sc = __uint_as_float((uint32_t)(e + 127) << 23);          // 2^e, e in [-126, 127] by construction
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            b[2 * m] = T(__half2float(__ushort_as_half((unsigned short)(w[m] & 0xffffu))) * sc);
-            b[2 * m + 1] = T(__half2float(__ushort_as_half((unsigned short)(w[m] >> 16))) * sc);
-        }
-        b[8] = T(__half2float(__ushort_as_half((unsigned short)(w[4] & 0xffffu))) * sc);
-    } else {
-#pragma unroll
-        for (int m = 0; m < 9; ++m) b[m] = T(__uint_as_float(w[m]));
-    }
-}
-template <typename T, int PK> __device__ __forceinline__ void cy_load(const uint32_t* __restrict__ base, size_t len, size_t j, T* b) {
-    uint32_t w[cy_words<PK>()];
-    cy_fetch<PK>(base, len, j, w);
-    cy_decode<T, PK>(w, b);
-}
-
+// The cycle-format copy (tsgo_block_row.h) of a block-indexed matrix, 8 lanes per row: the explicit level 0 of tsgo_config.cycle_level0 = 1.
 template <typename T, int PK>
 __global__ __launch_bounds__(kBlock) void k_to_planes(int n_rows, const int* __restrict__ ptr, const HT<T>* __restrict__ src, uint32_t* __restrict__ dst) {
     const int g = (blockIdx.x * kBlock + threadIdx.x) / 8, sub = threadIdx.x % 8;
@@ -389,12 +268,9 @@ __global__ __launch_bounds__(kBlock) void k_to_planes(int n_rows, const int* __r
     const int p0 = ptr[g], len = ptr[g + 1] - p0;
     constexpr int W = cy_words<PK>();
     for (int j = sub; j < len; j += 8) {
-        const HT<T>* b = src + (size_t)(p0 + j) * 9;
-        uint32_t* o = dst + (size_t)p0 * W + j;
         float v[9];
-#pragma unroll
-        for (int m = 0; m < 9; ++m) v[m] = (float)b[m];
-        cy_store<PK>(v, o, (size_t)len);
+        m3_copy(src + (size_t)(p0 + j) * 9, v);
+        cy_store<PK>(v, dst + (size_t)p0 * W + j, (size_t)len);
     }
 }
 
@@ -413,16 +289,9 @@ __global__ __launch_bounds__(kBlock) void k_mirror_pack(int n_blocks, const int*
     const int m = mirror[b];
     float v[9];
     if (m >= 0) {
-#pragma unroll
-        for (int x = 0; x < 3; ++x)
-#pragma unroll
-            for (int y = 0; y < 3; ++y) v[3 * x + y] = (float)A[(size_t)m * 9 + 3 * y + x];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) A[(size_t)b * 9 + k] = v[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) v[k] = (float)A[(size_t)b * 9 + k];
-    }
+        m3_transpose(A + (size_t)m * 9, v);
+        m3_copy(v, A + (size_t)b * 9);
+    } else m3_copy(A + (size_t)b * 9, v);
     if (Apm) {
         const int i = row[b], p0 = ptr[i];
         cy_store<PK>(v, Apm + (size_t)p0 * cy_words<PK>() + (b - p0), (size_t)(ptr[i + 1] - p0));
@@ -430,110 +299,60 @@ __global__ __launch_bounds__(kBlock) void k_mirror_pack(int n_blocks, const int*
 }
 
 // ---- V-cycle ---------------------------------------------------------------------------------------
-// Early exit of a finished solve: every cycle kernel reads st->done.  The flag is REQUESTED first and TESTED only after the loads that
-// depend on the kernel arguments alone (row bounds, the row's own entries) have been issued: tested at the very top it put one
-// more scalar round trip (st -> done) in front of the first vector load of kernels whose whole life is four such trips.
-// The coarse levels hold little work (12.5k / 1.5k / 196 block rows at 100k poses): what matters is the
-// length of the dependent-load chain, so LPR lanes share one block row (one 3x3 block per lane per
-// trip, 72 contiguous bytes per lane) and finish with an LPR-lane xor-shuffle sum.
-
-// The block-row kernels' arguments begin with a plain head (tsgo_kernels.h, "Argument heads"): n, xcd8, st, the row pointer, the column
-// and matrix words and the gathered vector — what is needed until the first dependent vector load is out — and the epilogue's operands behind.
-// Block-row kernels of the big levels take the XCD-aware workgroup map of the table kernels (xcd_block(), tsgo_kernels.h): an XCD walks a
-// contiguous eighth of the rows, so the vector entries a row gathers (its neighbours': nearby rows) are fetched into ONE L2 instead of all
-// eight (PMC, round 3: k_restrict from level 0 fetched 1.74x its algorithmic bytes, k_prolong_add 1.48x).  xcd8 = 0: round-robin, as before.
-__device__ __forceinline__ int lpr_block(int xcd8) { return xcd8 ? xcd_block(xcd8) : (int)blockIdx.x; }      // xcd8: 0, or gridDim.x / 8
+// The block-row kernels: where a lane stands, the early exit of a finished solve, the walk of the row's blocks and the argument heads
+// are tsgo_block_row.h's.  Each kernel below is what it asks for before the walk, the walk, the LPR-lane sum and its epilogue.
 
 // MODE 0: out = r - A z.   MODE 1: out = z + omega Dinv (r - A z)  (smoothing sweep).
 // MODE 2: out = Dinv A z  (power iteration for the smoother's damping).
-// PM: A is the cycle-format copy (above; PK = its encoding); otherwise the block-indexed f32 / HT matrix.
+// PM: A is the cycle-format copy (PK = its encoding); otherwise the block-indexed f32 / HT matrix.
 // V: the vector (and accumulation) type, T by default; the cycle's levels >= 1 run it in CV<T>.
 template <typename T, int LPR, int MODE, int PM = 1, int PK = 0, typename V = T>
 __global__ __launch_bounds__(kBlock) void k_bcsr_residual(int n, int xcd8, const CgState<T>* __restrict__ st, const int* __restrict__ ptr,
                                                           const int* __restrict__ col, const void* __restrict__ Av, const V* __restrict__ z,
                                                           const V* __restrict__ r, const HT<T>* __restrict__ Dinv, V* __restrict__ out,
                                                           const T* __restrict__ omega_ptr) {
-    const int done = MODE != 2 ? st->done : 0;
-    const int g = (lpr_block(xcd8) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
-    // LPR == 64: the row is wave-uniform, its bounds come through the scalar cache (one dependent round trip shorter)
-    const int i = LPR == 64 ? __builtin_amdgcn_readfirstlane(g < n ? g : n - 1) : (g < n ? g : n - 1);
-    V s0 = 0, s1 = 0, s2 = 0;
-    int p0 = ptr[i];
-    const int p1 = ptr[i + 1];
-    issue_before_exit(p0);
-    if (done) return;
-    // What the row's epilogue needs (its right-hand side, its own entry of z, its diagonal inverse) depends on the row
-    // alone: requested now, it arrives while the blocks are walked instead of adding a fourth dependent trip at the end.
-    const bool head = g < n && sub == 0;
+    const BlockRow w = block_row<LPR, MODE != 2, true>(n, xcd8, st, ptr);
+    if (w.done) return;
+    const int i = w.row;
+    // the row's right-hand side, its own entry of z, its diagonal inverse
     V ri0 = 0, ri1 = 0, ri2 = 0, zi0 = 0, zi1 = 0, zi2 = 0;
     HT<T> d[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (head) {
+    if (w.head) {
         if (MODE != 2) { ri0 = r[(size_t)i * 3]; ri1 = r[(size_t)i * 3 + 1]; ri2 = r[(size_t)i * 3 + 2]; }
         if (MODE == 1) { zi0 = z[(size_t)i * 3]; zi1 = z[(size_t)i * 3 + 1]; zi2 = z[(size_t)i * 3 + 2]; }
-        if (MODE != 0) {
-#pragma unroll
-            for (int m = 0; m < 9; ++m) d[m] = Dinv[(size_t)i * 9 + m];
-        }
+        if (MODE != 0) m3_copy(Dinv + (size_t)i * 9, d);
     }
-    const size_t len = (size_t)(p1 - p0);
-    const uint32_t* base = (const uint32_t*)Av + (size_t)p0 * cy_words<PK>();
-    // (Two blocks per trip with every load of the pair issued before either is used — half the dependent round trips of a lane with
-    // two to five blocks — was measured in round 3: 78 instead of 62 VGPRs, six resident waves per SIMD instead of eight, and the
-    // sweeps of levels 1-2 got slower, 7.7 -> 8.4 us and 7.9 -> 8.7 us.  One block per trip it stays.)
-    for (int a = p0 + sub; a < p1; a += LPR) {
-        const V* v = z + (size_t)col[a] * 3;
-        V b[9];
-        if (PM) cy_load<V, PK>(base, len, (size_t)(a - p0), b);
-        else {
-            const HT<T>* q = (const HT<T>*)Av + (size_t)a * 9;
-#pragma unroll
-            for (int m = 0; m < 9; ++m) b[m] = q[m];
-        }
-        const V v0 = v[0], v1 = v[1], v2 = v[2];
-        s0 += b[0] * v0 + b[1] * v1 + b[2] * v2; s1 += b[3] * v0 + b[4] * v1 + b[5] * v2; s2 += b[6] * v0 + b[7] * v1 + b[8] * v2;
-    }
+    V s0 = 0, s1 = 0, s2 = 0;
+    row_dot<LPR>(w, w.sub, col, std::conditional_t<PM != 0, CyBlocks<PK>, IdxBlocks<HT<T>>>(Av, w), VecAt<V>{z, 3}, s0, s1, s2);
     s0 = group_sum<V, LPR>(s0); s1 = group_sum<V, LPR>(s1); s2 = group_sum<V, LPR>(s2);
-    if (head) {
+    if (w.head) {
         if (MODE == 2) {
-            out[(size_t)i * 3] = d[0] * s0 + d[1] * s1 + d[2] * s2; out[(size_t)i * 3 + 1] = d[3] * s0 + d[4] * s1 + d[5] * s2;
-            out[(size_t)i * 3 + 2] = d[6] * s0 + d[7] * s1 + d[8] * s2;
+            out[(size_t)i * 3] = m3_row(d, 0, s0, s1, s2); out[(size_t)i * 3 + 1] = m3_row(d, 1, s0, s1, s2);
+            out[(size_t)i * 3 + 2] = m3_row(d, 2, s0, s1, s2);
             return;
         }
         const V e0 = ri0 - s0, e1 = ri1 - s1, e2 = ri2 - s2;
         if (MODE == 0) { out[(size_t)i * 3] = e0; out[(size_t)i * 3 + 1] = e1; out[(size_t)i * 3 + 2] = e2; }
         else {
             const V omega = (V)*omega_ptr;
-            out[(size_t)i * 3] = zi0 + omega * (d[0] * e0 + d[1] * e1 + d[2] * e2);
-            out[(size_t)i * 3 + 1] = zi1 + omega * (d[3] * e0 + d[4] * e1 + d[5] * e2);
-            out[(size_t)i * 3 + 2] = zi2 + omega * (d[6] * e0 + d[7] * e1 + d[8] * e2);
+            out[(size_t)i * 3] = zi0 + omega * m3_row(d, 0, e0, e1, e2);
+            out[(size_t)i * 3 + 1] = zi1 + omega * m3_row(d, 1, e0, e1, e2);
+            out[(size_t)i * 3 + 2] = zi2 + omega * m3_row(d, 2, e0, e1, e2);
         }
     }
 }
 
-// out = A z with z stored at row stride `zs` (research, TSGO_CYCLE_EXPLICIT0: the explicit level-0 matrix in place of the
-// implicit Schur product inside the cycle; z is the pose-record array zc, stride kPoseRec).  A plane-major (cycle format).
+// out = A z with z stored at row stride `zs`: the explicit level-0 matrix (cycle format) in place of the implicit Schur product inside
+// the cycle, tsgo_config.cycle_level0 = 1; z is the pose-record array zc, stride kPoseRec.
 template <typename T, int LPR, int PK>
 __global__ __launch_bounds__(kBlock) void k_bcsr_apply(int n, int xcd8, const CgState<T>* __restrict__ st, const int* __restrict__ ptr, const int* __restrict__ col,
                                                        const uint32_t* __restrict__ A, const T* __restrict__ z, int zs, T* __restrict__ out) {
-    const int done = st->done;
-    const int g = (lpr_block(xcd8) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
-    const int i = g < n ? g : n - 1;
+    const BlockRow w = block_row<LPR>(n, xcd8, st, ptr);
+    if (w.done) return;
     T s0 = 0, s1 = 0, s2 = 0;
-    int p0 = ptr[i];
-    const int p1 = ptr[i + 1];
-    issue_before_exit(p0);
-    if (done) return;
-    const size_t len = (size_t)(p1 - p0);
-    const uint32_t* base = A + (size_t)p0 * cy_words<PK>();
-    for (int a = p0 + sub; a < p1; a += LPR) {
-        const T* v = z + (size_t)col[a] * zs;
-        T b[9];
-        cy_load<T, PK>(base, len, (size_t)(a - p0), b);
-        const T v0 = v[0], v1 = v[1], v2 = v[2];
-        s0 += b[0] * v0 + b[1] * v1 + b[2] * v2; s1 += b[3] * v0 + b[4] * v1 + b[5] * v2; s2 += b[6] * v0 + b[7] * v1 + b[8] * v2;
-    }
+    row_dot<LPR>(w, w.sub, col, CyBlocks<PK>(A, w), VecAt<T>{z, zs}, s0, s1, s2);
     s0 = group_sum<T, LPR>(s0); s1 = group_sum<T, LPR>(s1); s2 = group_sum<T, LPR>(s2);
-    if (g < n && sub == 0) { out[(size_t)i * 3] = s0; out[(size_t)i * 3 + 1] = s1; out[(size_t)i * 3 + 2] = s2; }
+    if (w.head) { out[(size_t)w.row * 3] = s0; out[(size_t)w.row * 3 + 1] = s1; out[(size_t)w.row * 3 + 2] = s2; }
 }
 
 // rc = P^T v over the rows of R = P^T, and (when dinv_next is given) the next level's pre-smoothing
@@ -545,39 +364,24 @@ __global__ __launch_bounds__(kBlock) void k_restrict(int n_agg, int xcd8, const 
                                                      const VI* __restrict__ vb, VO* __restrict__ rc, const HT<T>* __restrict__ dinv_next,
                                                      VO* __restrict__ z_next, const T* __restrict__ omega_ptr) {
     using A = decltype(VI(0) + VO(0));
-    const int done = st->done;
-    const int g = (lpr_block(xcd8) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
-    const int a = g < n_agg ? g : n_agg - 1;
-    A s0 = 0, s1 = 0, s2 = 0;
-    int p0 = rptr[a];
-    const int p1 = rptr[a + 1];
-    issue_before_exit(p0);
-    if (done) return;
-    const bool head = g < n_agg && sub == 0;
-    HT<T> dn[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // the next level's diagonal inverse: asked for before the walk, used after it
+    const BlockRow w = block_row<LPR>(n_agg, xcd8, st, rptr);
+    if (w.done) return;
+    const int a = w.row;
+    HT<T> dn[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // the next level's diagonal inverse
     A omega = 0;
-    if (head && dinv_next) {
+    if (w.head && dinv_next) {
         omega = (A)*omega_ptr;
-#pragma unroll
-        for (int m = 0; m < 9; ++m) dn[m] = dinv_next[(size_t)a * 9 + m];
+        m3_copy(dinv_next + (size_t)a * 9, dn);
     }
-    const size_t len = (size_t)(p1 - p0);
-    const uint32_t* base = Rv + (size_t)p0 * cy_words<PK>();          // cycle format
-    for (int rb = p0 + sub; rb < p1; rb += LPR) {
-        const size_t i = (size_t)rcol[rb] * 3;
-        A b[9];
-        cy_load<A, PK>(base, len, (size_t)(rb - p0), b);
-        A x0 = va[i], x1 = va[i + 1], x2 = va[i + 2];
-        if (SUB) { x0 -= vb[i]; x1 -= vb[i + 1]; x2 -= vb[i + 2]; }
-        s0 += b[0] * x0 + b[1] * x1 + b[2] * x2; s1 += b[3] * x0 + b[4] * x1 + b[5] * x2; s2 += b[6] * x0 + b[7] * x1 + b[8] * x2;
-    }
+    A s0 = 0, s1 = 0, s2 = 0;
+    row_dot<LPR>(w, w.sub, rcol, CyBlocks<PK>(Rv, w), VecAt<VI, SUB != 0>{va, 3, vb}, s0, s1, s2);
     s0 = group_sum<A, LPR>(s0); s1 = group_sum<A, LPR>(s1); s2 = group_sum<A, LPR>(s2);
-    if (head) {
+    if (w.head) {
         rc[(size_t)a * 3] = s0; rc[(size_t)a * 3 + 1] = s1; rc[(size_t)a * 3 + 2] = s2;
         if (dinv_next) {
-            z_next[(size_t)a * 3] = omega * (dn[0] * s0 + dn[1] * s1 + dn[2] * s2);
-            z_next[(size_t)a * 3 + 1] = omega * (dn[3] * s0 + dn[4] * s1 + dn[5] * s2);
-            z_next[(size_t)a * 3 + 2] = omega * (dn[6] * s0 + dn[7] * s1 + dn[8] * s2);
+            z_next[(size_t)a * 3] = omega * m3_row(dn, 0, s0, s1, s2);
+            z_next[(size_t)a * 3 + 1] = omega * m3_row(dn, 1, s0, s1, s2);
+            z_next[(size_t)a * 3 + 2] = omega * m3_row(dn, 2, s0, s1, s2);
         }
     }
 }
@@ -589,28 +393,15 @@ __global__ __launch_bounds__(kBlock) void k_prolong_add(int n, int xcd8, const C
                                                         const int* __restrict__ pcol, const uint32_t* __restrict__ P, const VE* __restrict__ e,
                                                         VZ* __restrict__ z, int zs, float* __restrict__ z32 = nullptr) {
     using A = decltype(VE(0) + VZ(0));
-    const int done = st->done;
-    const int g = (lpr_block(xcd8) * kBlock + threadIdx.x) / LPR, sub = threadIdx.x % LPR;
-    const int i = g < n ? g : n - 1;
+    const BlockRow w = block_row<LPR>(n, xcd8, st, pptr);
+    if (w.done) return;
+    const int i = w.row;
+    A z0 = 0, z1 = 0, z2 = 0;                          // the entry this row adds to
+    if (w.head) { z0 = z[(size_t)i * zs]; z1 = z[(size_t)i * zs + 1]; z2 = z[(size_t)i * zs + 2]; }
     A s0 = 0, s1 = 0, s2 = 0;
-    int p0 = pptr[i];
-    const int p1 = pptr[i + 1];
-    issue_before_exit(p0);
-    if (done) return;
-    const bool head = g < n && sub == 0;
-    A z0 = 0, z1 = 0, z2 = 0;                          // the entry this row adds to: read before the walk
-    if (head) { z0 = z[(size_t)i * zs]; z1 = z[(size_t)i * zs + 1]; z2 = z[(size_t)i * zs + 2]; }
-    const size_t len = (size_t)(p1 - p0);
-    const uint32_t* base = P + (size_t)p0 * cy_words<PK>();           // cycle format
-    for (int pb = p0 + sub; pb < p1; pb += LPR) {
-        const VE* v = e + (size_t)pcol[pb] * 3;
-        A b[9];
-        cy_load<A, PK>(base, len, (size_t)(pb - p0), b);
-        const A v0 = v[0], v1 = v[1], v2 = v[2];
-        s0 += b[0] * v0 + b[1] * v1 + b[2] * v2; s1 += b[3] * v0 + b[4] * v1 + b[5] * v2; s2 += b[6] * v0 + b[7] * v1 + b[8] * v2;
-    }
+    row_dot<LPR>(w, w.sub, pcol, CyBlocks<PK>(P, w), VecAt<VE>{e, 3}, s0, s1, s2);
     s0 = group_sum<A, LPR>(s0); s1 = group_sum<A, LPR>(s1); s2 = group_sum<A, LPR>(s2);
-    if (head) {
+    if (w.head) {
         z[(size_t)i * zs] = VZ(z0 + s0); z[(size_t)i * zs + 1] = VZ(z1 + s1); z[(size_t)i * zs + 2] = VZ(z2 + s2);
         if (z32) { float* q = z32 + (size_t)i * zs; q[0] = (float)(z0 + s0); q[1] = (float)(z1 + s1); q[2] = (float)(z2 + s2); }     // level 0: the pose records' f32 copy
     }
@@ -624,22 +415,13 @@ __global__ __launch_bounds__(kDenseThreads) void k_coarse_tail(int n, int n_agg,
                                                                const HT<T>* __restrict__ Rv, const int* __restrict__ pptr,
                                                                const int* __restrict__ pcol, const HT<T>* __restrict__ P, const V* __restrict__ res,
                                                                const T* __restrict__ inv, V* __restrict__ z, const CgState<T>* __restrict__ st) {
-    const int done = st->done;
     __shared__ T rc[kDenseMax], zc_[kDenseMax];
     {
         const int a = threadIdx.x / 32, sub = threadIdx.x % 32;
+        const RowBounds rb = row_bounds(st, rptr, a < n_agg ? a : n_agg - 1);
+        if (rb.done) return;
         T s0 = 0, s1 = 0, s2 = 0;
-        const int ac = a < n_agg ? a : n_agg - 1;
-        int rb0 = rptr[ac];
-        const int rb1 = rptr[ac + 1];
-        issue_before_exit(rb0);
-        if (done) return;
-        if (a < n_agg)
-            for (int rb = rb0 + sub; rb < rb1; rb += 32) {
-                const HT<T>* b = Rv + (size_t)rb * 9; const size_t i = (size_t)rcol[rb] * 3;
-                const T x0 = res[i], x1 = res[i + 1], x2 = res[i + 2];
-                s0 += b[0] * x0 + b[1] * x1 + b[2] * x2; s1 += b[3] * x0 + b[4] * x1 + b[5] * x2; s2 += b[6] * x0 + b[7] * x1 + b[8] * x2;
-            }
+        if (a < n_agg) row_dot<32>(rb, sub, rcol, IdxBlocks<HT<T>>(Rv, rb), VecAt<V>{res, 3}, s0, s1, s2);
         s0 = group_sum<T, 32>(s0); s1 = group_sum<T, 32>(s1); s2 = group_sum<T, 32>(s2);
         if (a < n_agg && sub == 0) { rc[3 * a] = s0; rc[3 * a + 1] = s1; rc[3 * a + 2] = s2; }
     }
@@ -650,11 +432,10 @@ __global__ __launch_bounds__(kDenseThreads) void k_coarse_tail(int n, int n_agg,
     {
         const int i = threadIdx.x / 4, sub = threadIdx.x % 4;
         T s0 = 0, s1 = 0, s2 = 0;
-        if (i < n)
-            for (int pb = pptr[i] + sub; pb < pptr[i + 1]; pb += 4) {
-                const HT<T>* b = P + (size_t)pb * 9; const T* v = zc_ + pcol[pb] * 3;
-                s0 += b[0] * v[0] + b[1] * v[1] + b[2] * v[2]; s1 += b[3] * v[0] + b[4] * v[1] + b[5] * v[2]; s2 += b[6] * v[0] + b[7] * v[1] + b[8] * v[2];
-            }
+        if (i < n) {
+            const RowBounds rb{pptr[i], pptr[i + 1], 0};
+            row_dot<4>(rb, sub, pcol, IdxBlocks<HT<T>>(P, rb), VecAt<T>{zc_, 3}, s0, s1, s2);
+        }
         s0 = group_sum<T, 4>(s0); s1 = group_sum<T, 4>(s1); s2 = group_sum<T, 4>(s2);
         if (i < n && sub == 0) { z[(size_t)i * 3] = V(z[(size_t)i * 3] + s0); z[(size_t)i * 3 + 1] = V(z[(size_t)i * 3 + 1] + s1); z[(size_t)i * 3 + 2] = V(z[(size_t)i * 3 + 2] + s2); }
     }
@@ -678,8 +459,7 @@ __global__ __launch_bounds__(kBlock) void k_bottom_scatter(int nnzA, const int* 
         const int i = a_row[t], j = a_col[t];
         const T w = *omega_ptr;
         T d[9], a[9], m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { d[k] = Dinv[(size_t)i * 9 + k]; a[k] = A[(size_t)t * 9 + k]; }
+        m3_copy(Dinv + (size_t)i * 9, d); m3_copy(A + (size_t)t * 9, a);
         m3_mul_acc<T>(d, a, m);
 #pragma unroll
         for (int x = 0; x < 3; ++x)
@@ -780,13 +560,11 @@ __global__ __launch_bounds__(kBlock) void k_tail_E(int n, const int* __restrict_
     if (i >= n) return;
     const T w = *omega_ptr;
     T d[9];
-#pragma unroll
-    for (int m = 0; m < 9; ++m) d[m] = T(Dinv[(size_t)i * 9 + m]);
+    m3_copy(Dinv + (size_t)i * 9, d);
     for (int tb = tptr[i] + lane; tb < tptr[i + 1]; tb += 64) {
         const int c = tcol[tb];
         T t[9], o[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int m = 0; m < 9; ++m) t[m] = T(Tv[(size_t)tb * 9 + m]);
+        m3_copy(Tv + (size_t)tb * 9, t);
         m3_mul_acc<T>(d, t, o);
 #pragma unroll
         for (int x = 0; x < 3; ++x)
@@ -877,26 +655,15 @@ __global__ __launch_bounds__(kBlock) void k_tail_up(int n, int nd, const CgState
                                                     const V* __restrict__ t, const int* __restrict__ col, const uint32_t* __restrict__ Apm, const V* __restrict__ z1,
                                                     const HT<T>* __restrict__ Dinv, const T* __restrict__ omega_ptr, V* __restrict__ z) {
     __shared__ V red6[kWavesPerBlock * 6];
-    const int done = st->done;
     const int i = blockIdx.x;
-    int p0 = ptr[i];
-    const int p1 = ptr[i + 1];
-    issue_before_exit(p0);
-    if (done) return;                                        // workgroup-uniform
+    const RowBounds rb = row_bounds(st, ptr, i);
+    if (rb.done) return;                                     // workgroup-uniform
     // the dense part first: its operands depend on the arguments alone
     const float* g0 = Gf + (size_t)i * 3 * nd;
     V d0 = 0, d1 = 0, d2 = 0;
     for (int m = threadIdx.x; m < nd; m += kBlock) { const V tm = t[m]; d0 += V(g0[m]) * tm; d1 += V(g0[nd + m]) * tm; d2 += V(g0[2 * (size_t)nd + m]) * tm; }
     V s0 = 0, s1 = 0, s2 = 0;
-    const size_t len = (size_t)(p1 - p0);
-    const uint32_t* base = Apm + (size_t)p0 * cy_words<PK>();
-    for (int a = p0 + threadIdx.x; a < p1; a += kBlock) {
-        const V* v = z1 + (size_t)col[a] * 3;
-        V b[9];
-        cy_load<V, PK>(base, len, (size_t)(a - p0), b);
-        const V v0 = v[0], v1 = v[1], v2 = v[2];
-        s0 += b[0] * v0 + b[1] * v1 + b[2] * v2; s1 += b[3] * v0 + b[4] * v1 + b[5] * v2; s2 += b[6] * v0 + b[7] * v1 + b[8] * v2;
-    }
+    row_dot<kBlock>(rb, (int)threadIdx.x, col, CyBlocks<PK>(Apm, rb), VecAt<V>{z1, 3}, s0, s1, s2);
     // six sums, ONE barrier: per-wave shuffles, then thread 0 adds the four waves' partials
     s0 = wave_sum<V>(s0); s1 = wave_sum<V>(s1); s2 = wave_sum<V>(s2); d0 = wave_sum<V>(d0); d1 = wave_sum<V>(d1); d2 = wave_sum<V>(d2);
     if ((threadIdx.x & 63) == 0) { V* q = red6 + (threadIdx.x >> 6) * 6; q[0] = s0; q[1] = s1; q[2] = s2; q[3] = d0; q[4] = d1; q[5] = d2; }
@@ -908,9 +675,9 @@ __global__ __launch_bounds__(kBlock) void k_tail_up(int n, int nd, const CgState
         const V w = (V)*omega_ptr;
         const HT<T>* d = Dinv + (size_t)i * 9;
         const V* zi = z1 + (size_t)i * 3;
-        z[(size_t)i * 3] = V(2) * zi[0] - w * (V(d[0]) * v[0] + V(d[1]) * v[1] + V(d[2]) * v[2]) + v[3];
-        z[(size_t)i * 3 + 1] = V(2) * zi[1] - w * (V(d[3]) * v[0] + V(d[4]) * v[1] + V(d[5]) * v[2]) + v[4];
-        z[(size_t)i * 3 + 2] = V(2) * zi[2] - w * (V(d[6]) * v[0] + V(d[7]) * v[1] + V(d[8]) * v[2]) + v[5];
+        z[(size_t)i * 3] = V(2) * zi[0] - w * m3_row(d, 0, v[0], v[1], v[2]) + v[3];
+        z[(size_t)i * 3 + 1] = V(2) * zi[1] - w * m3_row(d, 1, v[0], v[1], v[2]) + v[4];
+        z[(size_t)i * 3 + 2] = V(2) * zi[2] - w * m3_row(d, 2, v[0], v[1], v[2]) + v[5];
     }
 }
 

@@ -8,6 +8,9 @@
 //   engine/engine_hierarchy.inc    the multigrid hierarchy on the device: patterns, symbolic products, dense bottom operators
 //   engine/engine_graph.inc        tsgo_set_graph: tables, value staging, structure re-use, where SolverMemory starts afresh, solver history across requests
 //   engine/engine_launch.inc       every kernel launch of a linearisation / a hierarchy build / a PCG iteration
+//   tsgo_block_row.h               (device only) the one walk of a 3x3 block row — lane position, early exit, row dot product — of the multigrid cycle's kernels
+//                                  (tsgo_amg_kernels.h), with the 3x3 helpers and the cycle format it reads.  The pair-list products (k_pair_gemm*) and the
+//                                  batched cycle of tsgo_marginal_kernels.h (k_mb_bsr: a thread per (row, column)) do NOT use it: they are other shapes
 //   engine/engine_collective.inc   the all-reduces of an edge-sharded run
 //   engine/engine_solve.inc        the Gauss-Newton and Levenberg-Marquardt loops, the PCG drivers and the retry ladder (do_solve), read-outs
 //   engine/engine_probes.inc       timing probes (bench.py)
