@@ -104,7 +104,11 @@ typedef struct tsgo_config {
                                 chi^2(x) - chi^2(x + d) <= lm_chi2_rel_tol * chi^2(x); TSGO_STOP_DAMPING when a rejection would push lambda past
                                 1e9; TSGO_STOP_CAP; TSGO_STOP_SOLVER.  Meant to be run with odom_jacobian = 1: under the constant Jacobians the
                                 model is wrong and the loop rejects often (and says so in steps_rejected).  precision = 32 and world > 1 are
-                                refused by tsgo_create. */
+                                refused by tsgo_create.
+                                3: Powell's dogleg, the trust-region loop g2o and Ceres offer next to 2 (tsgo_set_dogleg below has the loop
+                                and its parameters): H, b and chi^2 as under 2 with lambda = 0, one linearisation and one solve per ACCEPTED
+                                step, and a rejected trial costs one step from the snapshot and one chi^2 pass.  lm_lambda0 and
+                                lm_chi2_rel_tol are not read.  precision = 32 and world > 1 are refused by tsgo_create. */
     double lr;               /* rules = 1: the step scale `lr` of GraphOptimizer.optimize(iterations, lr) (slam_main.py passes 0.2); ignored by rules = 0 */
     int32_t odom_jacobian;   /* 0 (default): the reference's ODOM Jacobians, the constants A = -I, B = +I (remote/graph/edge/EdgeSe2.h:35-37;
                                 parity).  1: the analytic Jacobians of the same residual under the reference's vertex update (SURVEY 8f
@@ -135,16 +139,18 @@ typedef struct tsgo_config {
 } tsgo_config;
 
 enum { TSGO_STOP_CAP = 0, TSGO_STOP_WORSE = 1, TSGO_STOP_PLATEAU = 2, TSGO_STOP_CONVERGED = 3, TSGO_STOP_SOLVER = 4,
-       TSGO_STOP_DAMPING = 5 /* rules = 2: a rejected trial would have raised lambda past its upper bound */ };
+       TSGO_STOP_DAMPING = 5 /* rules = 2: a rejected trial would have raised lambda past its upper bound */,
+       TSGO_STOP_RADIUS = 6 /* rules = 3: a rejected trial left the trust-region radius below radius_min */ };
 
 #define TSGO_MAX_TRACE 256
 typedef struct tsgo_stats {
-    int32_t iterations_run;              /* Gauss-Newton linearisations performed */
+    int32_t iterations_run;              /* Gauss-Newton linearisations performed (rules = 2 and 3: trials) */
     int32_t stop_reason;                 /* TSGO_STOP_*; rules of OptimizerCpu.h:140-153,167-177 */
     double chi2[TSGO_MAX_TRACE];         /* robustified chi^2 at each linearisation (`err`, :117); the first TSGO_MAX_TRACE of them */
-    int32_t pcg_iters[TSGO_MAX_TRACE];   /* PCG iterations of each solve */
+    int32_t pcg_iters[TSGO_MAX_TRACE];   /* PCG iterations of each solve (rules = 3: of the solve that trial ran, 0 for a trial that reused one;
+                                            pcg_iters_total adds accordingly) */
     double last_delta_norm;              /* ||delta||_2 of the last solve (unscaled, :173) */
-    double ms_total, ms_linearize, ms_solve, ms_update;   /* device time, hipEvent */
+    double ms_total, ms_linearize, ms_solve, ms_update;   /* device time, hipEvent (rules = 3: a trial that reused a solve adds to ms_update alone) */
     double ms_setup;                     /* tsgo_set_graph: host layout build + upload, or the refill when the structure was reused */
     int32_t structure_reused;            /* 1 when the last tsgo_set_graph found the same structure and only refilled values */
     int32_t cycle_storage_now;           /* what the multigrid cycle of this structure reads now: 16 (packed halves) or 32 (f32: chosen by
@@ -162,7 +168,9 @@ typedef struct tsgo_stats {
                                             (it did not fit the new estimates), 0 otherwise */
     int32_t graph_replay;                /* 1 when this run replayed captured hipGraphs of the PCG iteration (tsgo_config.use_graphs), 0: eager launches */
     /* rules = 2 (all zero under rules 0 and 1).  Every trace of a rules = 2 run is PER TRIAL: chi2[it] is the chi^2 at the point trial `it`
-     * linearised (it repeats after a rejection), lambda_last the damping of the last trial, iterations_run the number of trials. */
+     * linearised (it repeats after a rejection), lambda_last the damping of the last trial, iterations_run the number of trials.
+     * rules = 3 fills the same fields per trial: chi2[it] is the chi^2 at the point trial `it` was taken from, steps_rejected, lm_gain, lm_pred
+     * and lm_chi2_trial are as under rules = 2, lm_lambda[] and lambda_last stay 0; the radii and scalars are in tsgo_dogleg_trace. */
     int32_t steps_rejected;              /* trials whose step was rolled back */
     double lm_lambda[TSGO_MAX_TRACE];    /* damping of each trial */
     double lm_gain[TSGO_MAX_TRACE];      /* gain ratio rho of each trial (0 where pred = 0); accepted when > 0 with pred > 0 */
@@ -217,6 +225,45 @@ void tsgo_default_robust(tsgo_robust* r);                        /* host-only to
 int tsgo_set_robust(tsgo_optimizer* opt, const tsgo_robust* r);
 int tsgo_get_robust(tsgo_optimizer* opt, tsgo_robust* out);
 
+/* Powell's dogleg trust-region loop, tsgo_config.rules = 3 (no reference counterpart).  The model is that of rules = 2 with lambda = 0:
+ * chi^2(x + d) ~ chi^2 - 2 b^T d + d^T H d, with H, b and chi^2 from the linearisation of rules = 2 (b zeroed at fixed vertices, the gauge
+ * term inside H; the handle's robust setting, odom_jacobian, virtual-landmark and prior edges apply), g = b the descent direction.
+ *   per SOLVE (at the start and after every accepted step): linearise; solve H d_gn = b (PCG from zero: warm_start is ignored and nothing
+ *     of a trial enters the solver history; a failed solve ends the run with TSGO_STOP_SOLVER); back-substitute the landmarks' part; four
+ *     scalars, folded on the host in f64 from per-workgroup partials: gg = b^T b, gd = b^T d_gn, dd = |d_gn|^2, gHg = b^T H b (one pass
+ *     over the edges: sum of w (J b)^T Omega (J b); H is never formed).  gg == 0: TSGO_STOP_CONVERGED with no step; the linearisation is
+ *     recorded as a trial of kind 0 with zero step, pred and gain.
+ *   per TRIAL with radius D, alpha = gg / gHg, n = sqrt(gg), the step d = c1 b + c2 d_gn:
+ *     kind 0, Gauss-Newton   sqrt(dd) <= D                 c1 = 0, c2 = 1
+ *     kind 2, gradient       else alpha n >= D             c1 = D / n, c2 = 0
+ *     kind 1, dogleg         otherwise                     c1 = alpha (1 - beta), c2 = beta, beta in (0, 1) the positive root of
+ *                            |alpha b + beta (d_gn - alpha b)| = D:  beta = (-h + sqrt(h^2 - a c)) / a  with  a = dd - 2 alpha gd + alpha^2 gg,
+ *                            h = alpha gd - alpha^2 gg,  c = alpha^2 gg - D^2
+ *     pred = 2 (c1 gg + c2 gd) - (c1^2 gHg + 2 c1 c2 gg + c2^2 gd) — the model's decrease 2 b^T d - d^T H d written with H d_gn = b, which
+ *     holds to pcg_rel_tol, not exactly;  step_norm = |d| from the same scalars.  The step is applied FROM THE SNAPSHOT of the estimates
+ *     taken at the solve (poses by the vertex update of rules = 2, landmarks by addition), chi^2 at the trial point comes from the chi^2-only
+ *     pass of rules = 2, gain = (chi^2 - chi^2_trial) / pred (0 where pred == 0).  Accepted iff gain > 0 and pred > 0; a NaN rejects.
+ *   radius, after every trial, in this order: !(gain >= 0.25) -> D = 0.25 step_norm; else gain > 0.75 and kind != 0 -> D = min(2 D,
+ *     radius_max); else unchanged.
+ *   after an accepted trial: TSGO_STOP_CONVERGED when step_norm < 1e-3 or chi^2 - chi^2_trial <= chi2_rel_tol chi^2; otherwise the next
+ *     trial solves again.  After a rejected trial: the estimates are restored bit for bit; TSGO_STOP_RADIUS when the new D < radius_min;
+ *     otherwise the next trial REUSES the linearisation, d_gn and the four scalars: no linearisation, no hierarchy work, no solve.
+ * Trials count against `iterations` (TSGO_STOP_CAP).  Every tsgo_optimize call starts at radius0.  chi^2 never rises.
+ * The parameters belong to the handle: they survive tsgo_set_graph and are read by rules = 3 only.  tsgo_set_dogleg returns an error (< 0,
+ * text in tsgo_last_error, handle unchanged) for a NULL argument, a non-finite value, anything outside 0 < radius_min <= radius0 <=
+ * radius_max, and chi2_rel_tol < 0. */
+typedef struct tsgo_dogleg_params { double radius0, radius_min, radius_max, chi2_rel_tol; } tsgo_dogleg_params;
+void tsgo_default_dogleg(tsgo_dogleg_params* p);                 /* host-only too: 1e4, 1e-9, 1e9, 1e-6 */
+int tsgo_set_dogleg(tsgo_optimizer* opt, const tsgo_dogleg_params* p);
+int tsgo_get_dogleg(tsgo_optimizer* opt, tsgo_dogleg_params* out);
+typedef struct tsgo_dogleg_trace {      /* of the handle's LAST tsgo_optimize; all zero when that was not a rules = 3 run */
+    int32_t trials, solves;             /* solves = linearise + solve pairs run; trials - solves = trials that reused one */
+    int32_t kind[TSGO_MAX_TRACE], solved[TSGO_MAX_TRACE];   /* 0 / 1 / 2 as above; 1 when the trial ran its own solve */
+    double  radius[TSGO_MAX_TRACE], step_norm[TSGO_MAX_TRACE], gg[TSGO_MAX_TRACE], gHg[TSGO_MAX_TRACE], gd[TSGO_MAX_TRACE], dd[TSGO_MAX_TRACE];
+    double  radius_last;                /* the radius the next trial would have used */
+} tsgo_dogleg_trace;
+int tsgo_get_dogleg_trace(tsgo_optimizer* opt, tsgo_dogleg_trace* out);
+
 /* Replaces IOptimizer<T>::Optimize(IGraph*) (remote/optimizer/IOptimizer.h:21; loop semantics of
  * OptimizerCpu.h:25-183) including ISolver<T>::Solve (remote/solver/ISolver.h:10).  The graph held by
  * the handle is updated in place. */
@@ -260,7 +307,9 @@ int tsgo_comm_time_allreduce(tsgo_optimizer* opt, int64_t n_elements, int32_t re
  * which: 0 schur_lm, 1 schur_pose, 2 cg_update, 3 lin_lm, 4 lin_pose, 5 one whole PCG iteration
  * (preconditioner application included), 6 the multigrid numeric setup of one GN iteration, 7 the chi^2-only evaluation pass of a
  * rules = 2 trial (a handle created with rules = 2; to be compared with 3 + 4, the linearisation it stands in for), 8 the summary-only pass
- * of tsgo_edge_report on the handle's graph (to be compared with 7, which reads the same tables). */
+ * of tsgo_edge_report on the handle's graph (to be compared with 7, which reads the same tables), 9 the g^T H g pass of a rules = 3 solve
+ * (a handle created with rules = 3, on which 7 runs too; to be compared with 7, which reads the same tables: 9 gathers the gradient of
+ * both ends of every edge on top). */
 int tsgo_time_kernel(tsgo_optimizer* opt, int32_t which, int32_t reps, double* us_per_launch, double* bytes_per_launch);
 
 /* Timing probe for the multigrid V-cycle's coarse levels (bench.py's per-kernel table): for every explicit level below

@@ -125,6 +125,7 @@ public:
         if (stats.stop_reason == TSGO_STOP_PLATEAU) std::cout << "Plateau: NO MORE OPT\n";
         if (stats.stop_reason == TSGO_STOP_CONVERGED) std::cout << "CONVERGED\n";
         if (stats.stop_reason == TSGO_STOP_DAMPING) std::cout << "Damping at its upper bound: no step lowers the error\n";      // rules = 2 only
+        if (stats.stop_reason == TSGO_STOP_RADIUS) std::cout << "Trust region at its lower bound: no step lowers the error\n";      // rules = 3 only
         const int last = stats.iterations_run > 0 ? (stats.iterations_run < TSGO_MAX_TRACE ? stats.iterations_run : TSGO_MAX_TRACE) - 1 : 0;
         std::cout << "Summary() error = " << stats.chi2[last] << std::endl;
     }
@@ -138,6 +139,30 @@ public:
         tsgo_config c; tsgo_default_config(&c);
         c.rules = 2; c.odom_jacobian = 1; c.lm_lambda0 = lambda0; c.lm_chi2_rel_tol = chi2_rel_tol;
         return c;
+    }
+
+    // rules = 3 (Powell's dogleg, tsgo_config.rules): a config for that loop — the defaults with rules = 3 and the analytic ODOM Jacobians — and
+    // its parameters, which belong to the handle (tsgo_set_dogleg; DefaultDogleg() adjusted).  SetDogleg throws on an error (a non-finite value,
+    // radii outside 0 < radius_min <= radius0 <= radius_max, chi2_rel_tol < 0).  DoglegTrace: what the last Optimize did trial by trial (kind,
+    // solved, radius, step_norm and the four scalars; trials - solves of them reused a solve); StepsRejected / StepAccepted serve this loop too.
+    static tsgo_config DoglegConfig() {
+        tsgo_config c; tsgo_default_config(&c);
+        c.rules = 3; c.odom_jacobian = 1;
+        return c;
+    }
+    static tsgo_dogleg_params DefaultDogleg() { tsgo_dogleg_params p; tsgo_default_dogleg(&p); return p; }
+    void SetDogleg(const tsgo_dogleg_params& params) {
+        if (tsgo_set_dogleg(handle, &params)) throw std::runtime_error(tsgo_last_error());
+    }
+    tsgo_dogleg_params Dogleg() const {
+        tsgo_dogleg_params p;
+        if (tsgo_get_dogleg(handle, &p)) throw std::runtime_error(tsgo_last_error());
+        return p;
+    }
+    tsgo_dogleg_trace DoglegTrace() const {
+        tsgo_dogleg_trace t;
+        if (tsgo_get_dogleg_trace(handle, &t)) throw std::runtime_error(tsgo_last_error());
+        return t;
     }
 
     // Robust kernel of one edge class (tsgo_set_robust): kernel = TSGO_ROBUST_*, delta its width (ignored by TSGO_ROBUST_NONE); the other

@@ -37,6 +37,15 @@ class tsgo_robust(C.Structure):
     _fields_ = [("kernel", C.c_int32 * 5), ("reserved", C.c_int32), ("delta", C.c_double * 5)]
 
 
+class tsgo_dogleg_params(C.Structure):
+    _fields_ = [("radius0", C.c_double), ("radius_min", C.c_double), ("radius_max", C.c_double), ("chi2_rel_tol", C.c_double)]
+
+
+class tsgo_dogleg_trace(C.Structure):
+    _fields_ = [("trials", C.c_int32), ("solves", C.c_int32), ("kind", C.c_int32 * TSGO_MAX_TRACE), ("solved", C.c_int32 * TSGO_MAX_TRACE)] + \
+               [(n, C.c_double * TSGO_MAX_TRACE) for n in ("radius", "step_norm", "gg", "gHg", "gd", "dd")] + [("radius_last", C.c_double)]
+
+
 class tsgo_edge_class_summary(C.Structure):
     _fields_ = [("edges", C.c_int64), ("downweighted", C.c_int64), ("s_sum", C.c_double), ("rho_sum", C.c_double), ("s_max", C.c_double),
                 ("s_max_edge", C.c_int64)]
@@ -129,13 +138,13 @@ class tsgo_testing_schur_out(C.Structure):
                [("nnz", C.c_int64), ("pairs", C.c_int64), ("od", C.c_int64), ("declined", C.c_int32), ("reserved", C.c_int32)]
 
 
-HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_default_gnc", "tsgo_last_error", "tsgo_wire_decode", "tsgo_wire_new", "tsgo_wire_decode_into", "tsgo_wire_view", "tsgo_wire_free",
+HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_default_gnc", "tsgo_default_dogleg", "tsgo_last_error", "tsgo_wire_decode", "tsgo_wire_new", "tsgo_wire_decode_into", "tsgo_wire_view", "tsgo_wire_free",
                 "tsgo_wire_encode_response", "tsgo_wire_encode_request", "tsgo_synth_create", "tsgo_synth_view",
                 "tsgo_synth_truth", "tsgo_synth_free", "tsgo_layout_probe", "tsgo_amg_probe", "tsgo_amg_probe_shard", "tsgo_init_tree", "tsgo_sample_noise"]
 DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_graph", "tsgo_reset_history", "tsgo_optimize", "tsgo_get_vertices",
                   "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
                   "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust", "tsgo_edge_report", "tsgo_gate_edges", "tsgo_init_estimates",
-                  "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc", "tsgo_sample_marginals"]
+                  "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc", "tsgo_sample_marginals", "tsgo_set_dogleg", "tsgo_get_dogleg", "tsgo_get_dogleg_trace"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply",
                    "tsgo_testing_sym_scan", "tsgo_testing_sym_product", "tsgo_testing_schur_pattern"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
@@ -145,6 +154,7 @@ def _declare_host(L):
     L.tsgo_default_config.argtypes = [C.POINTER(tsgo_config)]; L.tsgo_default_config.restype = None
     L.tsgo_default_robust.argtypes = [C.POINTER(tsgo_robust)]; L.tsgo_default_robust.restype = None
     L.tsgo_default_gnc.argtypes = [C.POINTER(tsgo_gnc_params)]; L.tsgo_default_gnc.restype = None
+    L.tsgo_default_dogleg.argtypes = [C.POINTER(tsgo_dogleg_params)]; L.tsgo_default_dogleg.restype = None
     L.tsgo_last_error.restype = C.c_char_p
     L.tsgo_wire_decode.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp)]
     L.tsgo_wire_new.argtypes = []; L.tsgo_wire_new.restype = vp
@@ -189,6 +199,9 @@ def _declare_device(L):
     L.tsgo_sample_marginals.argtypes = [vp, C.c_int32, C.c_uint64, C.c_double, vp, C.c_int64, vp, C.c_int64, C.POINTER(tsgo_sample_stats)]
     L.tsgo_set_robust.argtypes = [vp, C.POINTER(tsgo_robust)]
     L.tsgo_get_robust.argtypes = [vp, C.POINTER(tsgo_robust)]
+    L.tsgo_set_dogleg.argtypes = [vp, C.POINTER(tsgo_dogleg_params)]
+    L.tsgo_get_dogleg.argtypes = [vp, C.POINTER(tsgo_dogleg_params)]
+    L.tsgo_get_dogleg_trace.argtypes = [vp, C.POINTER(tsgo_dogleg_trace)]
     L.tsgo_edge_report.argtypes = [vp, vp, C.c_int64, C.POINTER(tsgo_edge_report_stats)]
     L.tsgo_gate_edges.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_double, vp, vp, C.POINTER(tsgo_gate_stats)]
     L.tsgo_init_estimates.argtypes = [vp, C.c_int32, vp, C.c_int64, C.POINTER(tsgo_init_stats)]

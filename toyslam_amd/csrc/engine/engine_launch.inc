@@ -48,11 +48,13 @@
     double lambda = 0;
     bool py_rules() const { return cfg.rules == 1; }
     bool lm_rules() const { return cfg.rules == 2; }      // Levenberg-Marquardt with step acceptance (engine_solve.inc: lm_loop)
+    bool dogleg_rules() const { return cfg.rules == 3; }  // Powell's dogleg (engine_dogleg.inc: dogleg_loop)
+    bool trial_rules() const { return lm_rules() || dogleg_rules(); }      // full steps taken tentatively: snapshot, chi^2-only pass, b zeroed at fixed vertices
     // pose-pose slots in general form (tsgo_math.h: eight dynamic planes per slot): analytic ODOM Jacobians, or a graph that holds
     // virtual landmark measurements (edge type 2) — the kernels' OJ = 1 instantiations
     bool oj() const { return cfg.odom_jacobian == 1 || pr.has_vlm; }
     int odom_analytic_flag() const { return cfg.odom_jacobian == 1 ? 1 : 0; }
-    double step_scale() const { return lm_rules() ? 1.0 : (py_rules() ? cfg.lr : kStepScale); }
+    double step_scale() const { return trial_rules() ? 1.0 : (py_rules() ? cfg.lr : kStepScale); }
     // a graph with priors (edge types 3, 4) takes the PRI = 1 instantiations; one without launches exactly what it did before priors existed
     PriorArgs<T> pose_prior_args() const { return PriorArgs<T>{pri_p_off, pri_p, pri_lchi, tl.n_slices > 0 ? nbL : 0}; }
     PriorArgs<T> lm_prior_args() const { return PriorArgs<T>{pri_l_off, pri_l, pri_lchi, 0}; }
@@ -87,14 +89,14 @@
         launch_lin_pose_only();
     }
     void launch_lin_lm() {              // (tsgo_time_kernel too)
-        const int zf = (py_rules() || lm_rules()) ? 1 : 0;
+        const int zf = (py_rules() || trial_rules()) ? 1 : 0;
         if (tl.n_slices == 0) return;
         pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick<0, 1>(rk(), [&](auto rk) {
             launch_table(k_lin_lm<T, g, pri, rk>, nbL, tl, zf, lmrec, (const T*)ps, (const T*)gauge_l, ninv, tl, (T)lambda, pri ? lm_prior_args() : no_priors(), robust_args());
         }); }); });
     }
     void launch_lin_pose_only() {       // (tsgo_time_kernel too)
-        const int zf = (py_rules() || lm_rules()) ? 1 : 0;
+        const int zf = (py_rules() || trial_rules()) ? 1 : 0;
         pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick<0, 1>(rk(), [&](auto rk) {
             launch_table(k_lin_pose<T, g, general, pri, rk>, nbP, tp, zf, (const T*)ps, (const T*)lmrec, to.row_off, (const T*)gauge_p, tp, to, pr.pose_first, pr.pose_last, part,
                          part + (size_t)pr.P * 18, (T)lambda, general ? odom_analytic_flag() : 0, pri ? pose_prior_args() : no_priors(), robust_args());

@@ -99,6 +99,11 @@
             if (cfg.world > 1 || collective()) return set_error(-1, "tsgo_time_kernel: 8 (the edge report's pass): edge-sharded handles (world > 1) are not supported");
             if (int rc = report_prepare()) return rc;
         }
+        if (which == 9) {
+            if (!dogleg_rules()) return set_error(-1, "tsgo_time_kernel: 9 (the g'Hg pass) needs a handle created with rules = 3");
+            if (int rc = report_prepare()) return rc;
+            launch_dl_gradient();      // the gradient vectors of this linearisation (x and dl are whatever the last solve left: only the dots read them)
+        }
         for (int pass = 0; pass < 2; ++pass) {
             const int n = pass == 0 ? 3 : reps;
             HIP_OK(hipEventRecord(ev[0], stream));
@@ -114,7 +119,8 @@
                     }
                     case 3: launch_lin_lm(); break;
                     case 4: launch_lin_pose_only(); break;
-                    case 7: if (!lm_rules()) return set_error(-1, "tsgo_time_kernel: 7 (the chi^2-only pass) needs a handle created with rules = 2"); launch_chi2(lm_red); break;
+                    case 7: if (!trial_rules()) return set_error(-1, "tsgo_time_kernel: 7 (the chi^2-only pass) needs a handle created with rules = 2 (or 3)"); launch_chi2(lm_red); break;
+                    case 9: launch_ghg(dl_red + (size_t)3 * dl_nb()); break;
                     case 8: launch_edge_report(nullptr); break;
                     case 6: if (amg_on) { if (int rc = launch_amg_setup()) return rc; } break;
                     default: if (int rc = launch_iteration(0)) return rc; if (int rc = launch_iteration(1)) return rc; break;
@@ -130,8 +136,9 @@
             }
         }
         cfg.pcg_rel_tol = tol_guard.keep;
-        const double tab[9] = {b_lm, b_pose, b_upd, b_linlm, b_linpose, (amg_on ? 3.0 : 1.0) * (b_lm + b_pose) + b_upd, 0.0, bytes_chi2(), which == 8 ? bytes_report(false) : 0.0};
-        *bytes = tab[std::min(std::max(which, 0), 8)];
+        const double tab[10] = {b_lm, b_pose, b_upd, b_linlm, b_linpose, (amg_on ? 3.0 : 1.0) * (b_lm + b_pose) + b_upd, 0.0, bytes_chi2(), which == 8 ? bytes_report(false) : 0.0,
+                                which == 9 ? bytes_ghg() : 0.0};
+        *bytes = tab[std::min(std::max(which, 0), 9)];
         // leave a consistent state behind
         return do_linearize(&chi2);
     }

@@ -1,5 +1,6 @@
 // engine/engine_solve.inc — part of `template <typename T> struct Engine` (tsgo_hip.hip includes it INSIDE the class body):
 // the Gauss-Newton loop: linearise, warm start, PCG (bursts, hipGraph replay, paced eager launches), back-substitution and update, stop rules.
+// (rules = 3, the dogleg loop, is engine_dogleg.inc; tsgo_optimize below picks the loop.)
     int capture_cg_graph() {
         hipGraph_t graph = nullptr;
         HIP_OK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
@@ -559,7 +560,8 @@
         ev_pending = nullptr; evc = ev;      // (a call that ended in an error may have left a set unread)
         s.stop_reason = TSGO_STOP_CAP;
         const auto wall0 = std::chrono::steady_clock::now();
-        if (int rc = lm_rules() ? lm_loop(iterations, s) : gn_loop(iterations, s)) return rc;
+        std::memset(&dl_trace, 0, sizeof(dl_trace));      // of the handle's LAST tsgo_optimize: all zero unless dogleg_loop fills it
+        if (int rc = dogleg_rules() ? dogleg_loop(iterations, s) : (lm_rules() ? lm_loop(iterations, s) : gn_loop(iterations, s))) return rc;
         s.pcg_fallbacks = n_fallbacks - fallbacks0;
         s.history_carried = started_carried ? (n_carry_dropped > dropped0 ? 2 : 1) : 0;
         s.graph_replay = replayed ? 1 : 0;

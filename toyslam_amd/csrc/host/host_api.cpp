@@ -25,6 +25,11 @@ extern "C" void tsgo_default_robust(tsgo_robust* r) {
     r->reserved = 0;
 }
 
+extern "C" void tsgo_default_dogleg(tsgo_dogleg_params* p) {
+    if (!p) return;
+    p->radius0 = 1e4; p->radius_min = 1e-9; p->radius_max = 1e9; p->chi2_rel_tol = 1e-6;
+}
+
 extern "C" void tsgo_default_gnc(tsgo_gnc_params* p) {
     if (!p) return;
     static const double quantile99[5] = {11.345, 9.210, 9.210, 11.345, 9.210};      // chi^2, 3 dof (types 0, 3) and 2 dof (types 1, 2, 4)

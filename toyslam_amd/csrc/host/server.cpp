@@ -7,7 +7,8 @@
 //   GPU with the fewest requests in flight.  One graph per GPU, no collective: how this server uses a node.
 //   RULES "python" or "python:LR": the loop of the reference's in-process Python optimizer instead (lambda * I damping, step LR,
 //   default 0.2 as slam_main.py passes); "lm" or "lm:LAMBDA0": Levenberg-Marquardt with step acceptance (tsgo_config.rules = 2: full steps,
-//   a rejected step is rolled back, ITERATIONS counts trials; best with ODOM_JACOBIAN=analytic); ODOM_JACOBIAN "analytic": the extension of tsgo_config.odom_jacobian.  Both default to
+//   a rejected step is rolled back, ITERATIONS counts trials; best with ODOM_JACOBIAN=analytic); "dogleg" or "dogleg:RADIUS0": Powell's dogleg
+//   (tsgo_config.rules = 3, tsgo_set_dogleg: a rejected trial shrinks the radius and runs no new solve; ITERATIONS counts trials); ODOM_JACOBIAN "analytic": the extension of tsgo_config.odom_jacobian.  Both default to
 //   what the reference's C++ server does.  WARM_REQUESTS 1: tsgo_config.warm_requests (a connection's next request starts its PCG
 //   solves from the history of ITS OWN last one when it gets the same engine handle back; a handle that last served another
 //   connection forgets that history first, so no client's iteration counts or low-order bits depend on other clients' traffic;
@@ -85,6 +86,7 @@ bool write_all(int fd, const void* buf, size_t n) {
 
 struct Server {
     tsgo_config cfg;
+    tsgo_dogleg_params dogleg;              // RULES=dogleg[:RADIUS0]: given to every engine handle when it is created (read by rules = 3 only)
     int max_engines = 2;                    // per listed device
     std::vector<int> devices{0};            // the pool's GPUs (DEVICE argument); the same GPU may be listed twice (two pools on it)
     struct Slot { int created = 0, busy = 0; };
@@ -136,6 +138,7 @@ struct Server {
                 tsgo_config c = cfg; c.device = devices[best];
                 tsgo_optimizer* o = nullptr;
                 if (tsgo_create(&c, &o)) return nullptr;
+                if (c.rules == 3 && tsgo_set_dogleg(o, &dogleg)) { tsgo_destroy(o); return nullptr; }
                 ++created; ++slots[best].created; ++slots[best].busy;
                 slot_of.emplace_back(o, best);
                 return o;
@@ -318,9 +321,16 @@ int main(int argc, char* argv[]) {
             if (colon != std::string::npos) cfg.lm_lambda0 = std::stod(rulesS.substr(colon + 1));
             std::cout << "rules: Levenberg-Marquardt with step acceptance (full steps, gain ratio, lambda from " << cfg.lm_lambda0 << ")\n";
         }
+        tsgo_dogleg_params dogleg; tsgo_default_dogleg(&dogleg);
+        if (rulesS.rfind("dogleg", 0) == 0) {
+            cfg.rules = 3;
+            const size_t colon = rulesS.find(':');
+            if (colon != std::string::npos) dogleg.radius0 = std::stod(rulesS.substr(colon + 1));
+            std::cout << "rules: Powell's dogleg (trust region, one solve per accepted step, radius from " << dogleg.radius0 << ")\n";
+        }
         if (odomS == "analytic") { cfg.odom_jacobian = 1; std::cout << "ODOM Jacobians: analytic (extension)\n"; }
         cfg.warm_requests = warm_requests ? 1 : 0;      // a connection's next request continues from the last one's solver history (tsgo.h)
-        Server srv; srv.iterations = iters; srv.cfg = cfg; srv.max_engines = engines; srv.devices = devices;
+        Server srv; srv.iterations = iters; srv.cfg = cfg; srv.dogleg = dogleg; srv.max_engines = engines; srv.devices = devices;
         if (devices.size() > 1) {
             std::cout << "engine pool over " << devices.size() << " GPUs (";
             for (size_t k = 0; k < devices.size(); ++k) std::cout << (k ? "," : "") << devices[k];

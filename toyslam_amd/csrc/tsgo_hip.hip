@@ -1,6 +1,6 @@
 // tsgo_hip.hip — device side of the C ABI in include/tsgo.h: buffers, launches, the Gauss-Newton
 // loop with the reference's stop rules (remote/optimizer/OptimizerCpu.h:80-180), hipGraph replay of
-// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_sample_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h, tsgo_gnc_kernels.h.
+// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_sample_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h, tsgo_gnc_kernels.h, tsgo_dogleg_kernels.h.
 //
 // One translation unit; the engine class is laid out over this file and engine/*.inc (each included inside the class body):
 //   this file                      members (what the solver learns grouped by lifetime: SolverMemory; the structure index and its device maps), configuration / environment (host/knobs.h), device slabs, call-scoped device scratch (CallScratch, EventPair) and upload helpers; the C ABI at the end
@@ -18,7 +18,7 @@
 //   host/batch_plan.h              (host only, no HIP) how the readers cut their columns into batches; the gate's per-batch lists
 //   engine/engine_sample.inc       tsgo_sample_marginals: posterior samples by perturb-and-MAP and every vertex's covariance from their second moments
 //   engine/engine_report.inc       tsgo_edge_report: per-edge residual records and the per-class summary
-//   tsgo_edge_walk.h               (device only) the once-per-edge walk of the reader kernels, shared by the report and GNC passes: every input edge is visited by ONE lane
+//   tsgo_edge_walk.h               (device only) the once-per-edge walk of the reader kernels, shared by the report, GNC and dogleg g'Hg passes: every input edge is visited by ONE lane
 //                                  (pose-pose edges at their first endpoint, padding never), and a skipped slot is left before anything but its index and map words is
 //                                  read — why those passes write per edge with plain stores.  k_chi2 / k_lin_pose (and their landmark twins) intentionally do NOT use it:
 //                                  they have no slot -> edge maps, count padding through its zero weight, and must agree with each other on chi^2 bit for bit
@@ -26,6 +26,9 @@
 //   engine/engine_init.inc         tsgo_init_estimates: estimates from an odometry spanning tree (pointer jumping), landmarks from their observations
 //   engine/engine_edit.inc         tsgo_set_edge_information / tsgo_get_edge_information: the information diagonal of listed edges, in place
 //   engine/engine_gnc.inc          tsgo_gnc: graduated non-convexity (truncated least squares), one reweighting pass over the tables per round
+//   engine/engine_dogleg.inc       rules = 3, Powell's dogleg trust-region loop: one linearisation and one solve per ACCEPTED step, trials from the snapshot; tsgo_set_dogleg,
+//                                  tsgo_get_dogleg_trace.  Kernels: tsgo_dogleg_kernels.h (f64 only) — the gradient as dense vectors, g'Hg by the once-per-edge walk
+//                                  (a third visitor of tsgo_edge_walk.h), the step from the snapshot
 //   engine/engine_testing.inc      tsgo_testing_apply (TSGO_TESTING builds only): the operators PCG applies, read out column by column
 //   engine/sym_testing.inc         (file scope, TSGO_TESTING builds only) the pattern builders of tsgo_sym_kernels.h on caller-given arrays
 //
@@ -61,6 +64,7 @@
 #include "host/problem.h"
 #include "host/structure_index.h"
 #include "tsgo_amg_kernels.h"
+#include "tsgo_dogleg_kernels.h"
 #include "tsgo_edit_kernels.h"
 #include "tsgo_gate_kernels.h"
 #include "tsgo_gnc_kernels.h"
@@ -167,6 +171,9 @@ struct IEngine {
     virtual void reset_history() = 0;
     virtual int set_robust(const tsgo_robust& r) = 0;
     virtual void get_robust(tsgo_robust* out) const = 0;
+    virtual int set_dogleg(const tsgo_dogleg_params& p) = 0;
+    virtual void get_dogleg(tsgo_dogleg_params* out) const = 0;
+    virtual void get_dogleg_trace(tsgo_dogleg_trace* out) const = 0;
     virtual int marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, tsgo_marginal_stats* st) = 0;
     virtual int joint_marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, int64_t cov_cap, int* dim_out, tsgo_marginal_stats* st) = 0;
     virtual int sample_marginals(int n_samples, uint64_t seed, double rel_tol, double* cov, int64_t cap_vertices, double* samples, int64_t samples_cap,
@@ -561,6 +568,7 @@ template <typename T> struct Engine : IEngine {
 #include "engine/engine_init.inc"
 #include "engine/engine_edit.inc"
 #include "engine/engine_gnc.inc"
+#include "engine/engine_dogleg.inc"
 #ifdef TSGO_TESTING
 #include "engine/engine_testing.inc"
 #endif
@@ -592,6 +600,10 @@ int tsgo_create(const tsgo_config* cfg, tsgo_optimizer** out) {
         if (c.world > 1) return tsgo::set_error(-1, "tsgo_create: rules = 2 (Levenberg-Marquardt) does not support edge-sharded handles (world > 1)");
         if (!(c.lm_lambda0 > 0)) c.lm_lambda0 = 1e-3;
         if (!(c.lm_chi2_rel_tol >= 0)) c.lm_chi2_rel_tol = 1e-6;
+    }
+    if (c.rules == 3) {
+        if (c.precision != 64) return tsgo::set_error(-1, "tsgo_create: rules = 3 (dogleg) needs precision = 64: the gain ratio near the optimum is below f32 resolution");
+        if (c.world > 1) return tsgo::set_error(-1, "tsgo_create: rules = 3 (dogleg) does not support edge-sharded handles (world > 1)");
     }
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
@@ -731,6 +743,25 @@ int tsgo_set_robust(tsgo_optimizer* o, const tsgo_robust* r) {
 int tsgo_get_robust(tsgo_optimizer* o, tsgo_robust* out) {
     if (!o || !out) return tsgo::set_error(-1, "tsgo_get_robust: null argument");
     o->eng->get_robust(out);
+    return 0;
+}
+int tsgo_set_dogleg(tsgo_optimizer* o, const tsgo_dogleg_params* p) {
+    if (!o || !p) return tsgo::set_error(-1, "tsgo_set_dogleg: null argument");
+    if (!(std::isfinite(p->radius0) && std::isfinite(p->radius_min) && std::isfinite(p->radius_max) && std::isfinite(p->chi2_rel_tol)))
+        return tsgo::set_error(-1, "tsgo_set_dogleg: every parameter must be finite");
+    if (!(0 < p->radius_min && p->radius_min <= p->radius0 && p->radius0 <= p->radius_max))
+        return tsgo::set_error(-1, "tsgo_set_dogleg: the radii must satisfy 0 < radius_min <= radius0 <= radius_max");
+    if (p->chi2_rel_tol < 0) return tsgo::set_error(-1, "tsgo_set_dogleg: chi2_rel_tol must not be negative");
+    return o->eng->set_dogleg(*p);
+}
+int tsgo_get_dogleg(tsgo_optimizer* o, tsgo_dogleg_params* out) {
+    if (!o || !out) return tsgo::set_error(-1, "tsgo_get_dogleg: null argument");
+    o->eng->get_dogleg(out);
+    return 0;
+}
+int tsgo_get_dogleg_trace(tsgo_optimizer* o, tsgo_dogleg_trace* out) {
+    if (!o || !out) return tsgo::set_error(-1, "tsgo_get_dogleg_trace: null argument");
+    o->eng->get_dogleg_trace(out);
     return 0;
 }
 int tsgo_comm_selftest(tsgo_optimizer* o, int32_t* ranks_out) {

@@ -11,14 +11,14 @@ import numpy as np
 from . import _lib
 from .graph import GraphArrays
 
-STOP = {0: "cap", 1: "worse", 2: "plateau", 3: "converged", 4: "solver_failed", 5: "damping"}
+STOP = {0: "cap", 1: "worse", 2: "plateau", 3: "converged", 4: "solver_failed", 5: "damping", 6: "radius"}
 
 
 class HipOptimizer:
     def __init__(self, device=0, precision=64, pcg_rel_tol=1e-10, pcg_max_iters=20000, lanes_per_pose=0,
                  lanes_per_lm=0, use_graphs="auto", rank=0, world=1, preconditioner="amg", xcd_map=None, warm_start=None,
                  reuse_structure=None, rules="cpp", lr=0.2, odom_jacobian="constant", cycle_level0="implicit", cycle_storage=16, warm_requests=False, lm_lambda0=None, lm_chi2_rel_tol=None,
-                 testing=False):
+                 dl_radius0=None, dl_radius_min=None, dl_radius_max=None, dl_chi2_rel_tol=None, testing=False):
         # testing=True: libtsgo_hip_testing.so (the same sources with -DTSGO_TESTING: hooks, research variables, in-process group)
         # (TSGO_PY_TESTING_LIB=1: research scripts under tools/research and tests/research that set hook / research variables pick the
         # testing library without being edited; it selects which LIBRARY this Python wrapper loads, the product library reads nothing)
@@ -36,7 +36,7 @@ class HipOptimizer:
             cfg.warm_start = int(warm_start)
         if reuse_structure is not None:
             cfg.reuse_structure = int(reuse_structure)
-        cfg.rules, cfg.lr = {"cpp": 0, "python": 1, "lm": 2}[rules], float(lr)
+        cfg.rules, cfg.lr = {"cpp": 0, "python": 1, "lm": 2, "dogleg": 3}[rules], float(lr)
         # rules="lm": Levenberg-Marquardt with step acceptance (tsgo_config.rules = 2); meant for odom_jacobian="analytic"
         if lm_lambda0 is not None:
             cfg.lm_lambda0 = float(lm_lambda0)
@@ -49,6 +49,13 @@ class HipOptimizer:
         self.cfg = cfg
         self.h = C.c_void_p()
         _lib.check(self.lib, self.lib.tsgo_create(C.byref(cfg), C.byref(self.h)), "tsgo_create")
+        # rules="dogleg": Powell's dogleg trust-region loop (tsgo_config.rules = 3); its parameters go through tsgo_set_dogleg
+        if any(v is not None for v in (dl_radius0, dl_radius_min, dl_radius_max, dl_chi2_rel_tol)):
+            try:
+                self.set_dogleg(radius0=dl_radius0, radius_min=dl_radius_min, radius_max=dl_radius_max, chi2_rel_tol=dl_chi2_rel_tol)
+            except Exception:
+                self.close()
+                raise
         self.n_vertices = 0
         self.n_edges = 0
         self._v_in = None
@@ -112,11 +119,45 @@ class HipOptimizer:
         names = {v: k for k, v in _lib.ROBUST_KERNELS.items()}
         return {c: "none" if r.kernel[k] == 0 else (names[r.kernel[k]], r.delta[k]) for k, c in enumerate(_lib.ROBUST_CLASSES)}
 
+    def set_dogleg(self, radius0=None, radius_min=None, radius_max=None, chi2_rel_tol=None):
+        """Parameters of the dogleg loop (tsgo_set_dogleg; read by rules="dogleg" only): an argument left out keeps what the handle has.
+        They belong to the handle and survive set_graph; every optimize call starts at radius0."""
+        p = _lib.tsgo_dogleg_params()
+        _lib.check(self.lib, self.lib.tsgo_get_dogleg(self.h, C.byref(p)), "tsgo_get_dogleg")
+        for k, v in (("radius0", radius0), ("radius_min", radius_min), ("radius_max", radius_max), ("chi2_rel_tol", chi2_rel_tol)):
+            if v is not None:
+                setattr(p, k, float(v))
+        _lib.check(self.lib, self.lib.tsgo_set_dogleg(self.h, C.byref(p)), "tsgo_set_dogleg")
+
+    @property
+    def dogleg(self):
+        """The handle's dogleg parameters read back (tsgo_get_dogleg) as a dict."""
+        p = _lib.tsgo_dogleg_params()
+        _lib.check(self.lib, self.lib.tsgo_get_dogleg(self.h, C.byref(p)), "tsgo_get_dogleg")
+        return {f: getattr(p, f) for f, _t in p._fields_}
+
+    def dogleg_trace(self, n=None):
+        """tsgo_get_dogleg_trace of the handle's last optimize as a dict: trials, solves, radius_last and the per-trial arrays kind, solved,
+        radius, step_norm, gg, gHg, gd, dd (the first n entries; default min(trials, TSGO_MAX_TRACE)).  All zero after a run under other rules."""
+        tr = _lib.tsgo_dogleg_trace()
+        _lib.check(self.lib, self.lib.tsgo_get_dogleg_trace(self.h, C.byref(tr)), "tsgo_get_dogleg_trace")
+        n = min(tr.trials, _lib.TSGO_MAX_TRACE) if n is None else n
+        out = dict(trials=tr.trials, solves=tr.solves, radius_last=tr.radius_last)
+        for k in ("kind", "solved"):
+            out[k] = np.array(getattr(tr, k)[:n], dtype=np.int64)
+        for k in ("radius", "step_norm", "gg", "gHg", "gd", "dd"):
+            out[k] = np.array(getattr(tr, k)[:n])
+        return out
+
     def optimize(self, iterations):
         st = _lib.tsgo_stats()
         _lib.check(self.lib, self.lib.tsgo_optimize(self.h, iterations, C.byref(st)), "tsgo_optimize")
         n = st.trace_len
-        return dict(iters=st.iterations_run, stop=STOP[st.stop_reason], chi2=np.array(st.chi2[:n]), chi2_last=st.chi2_last,
+        tr = self.dogleg_trace(n)
+        return dict(# rules="dogleg": the per-trial trace of tsgo_get_dogleg_trace (zeros under the other rules) and the linearise + solve pairs run
+                    dl_kind=tr["kind"], dl_solved=tr["solved"], dl_radius=tr["radius"], dl_step_norm=tr["step_norm"], dl_gg=tr["gg"], dl_gHg=tr["gHg"],
+                    dl_gd=tr["gd"], dl_dd=tr["dd"], solves=tr["solves"], dl_radius_last=tr["radius_last"],
+iters=st.iterations_run, stop=STOP[st.stop_reason], chi2=np.array(st.chi2[:n]), chi2_last=st.chi2_last,
                     cg_iters=np.array(st.pcg_iters[:n]), delta_norm=st.last_delta_norm, ms_total=st.ms_total,
                     ms_linearize=st.ms_linearize, ms_solve=st.ms_solve, ms_update=st.ms_update, ms_setup=st.ms_setup, structure_reused=bool(st.structure_reused), lambda_last=st.lambda_last,
                     n_pose=st.n_pose, n_lm=st.n_lm, n_odom_edges=st.n_odom_edges, n_lm_edges=st.n_lm_edges,
@@ -406,7 +447,7 @@ class GraphOptimizer:
         """rules="cpp" (default): the C++ server's loop, whose step is fixed at 0.2 (remote/optimizer/OptimizerCpu.h:164).
         rules="python": the reference's own GraphOptimizer.optimize(iterations, lr) — damping lambda*I, any lr."""
         kw = dict(self.kw)
-        if kw.get("rules", "cpp") == "lm":
+        if kw.get("rules", "cpp") in ("lm", "dogleg"):
             pass                                           # full steps: lr has no meaning
         elif kw.get("rules", "cpp") == "cpp":
             if lr != 0.2:
