@@ -214,7 +214,8 @@ void tsgo_reset_history(tsgo_optimizer* opt);
  * hierarchy; the warm start's history stays (same answer to pcg_rel_tol).  precision 64 and 32.  A handle whose setting equals the default
  * runs the same device code, bit for bit, as one that was never given a setting.  Errors (< 0, text in tsgo_last_error): a NULL argument,
  * an unknown kernel id, a delta that is not finite or outside [1e-6, 1e6] on a class whose kernel uses one, a non-default setting on an
- * edge-sharded handle (world > 1). */
+ * edge-sharded handle (world > 1).  A class is an edge TYPE: to robustify the loop closures and leave the odometry chain quadratic (both
+ * type 0), or to trust one GNSS fix and doubt another, see tsgo_set_edge_robust below. */
 enum { TSGO_ROBUST_NONE = 0, TSGO_ROBUST_HUBER = 1, TSGO_ROBUST_CAUCHY = 2, TSGO_ROBUST_GEMAN_MCCLURE = 3 };
 typedef struct tsgo_robust {
     int32_t kernel[5];   /* indexed by tsgo_graph.e_type: 0 ODOM, 1 LM, 2 virtual landmark, 3 pose prior, 4 landmark prior */
@@ -224,6 +225,49 @@ typedef struct tsgo_robust {
 void tsgo_default_robust(tsgo_robust* r);                        /* host-only too: HUBER, 1.5 everywhere */
 int tsgo_set_robust(tsgo_optimizer* opt, const tsgo_robust* r);
 int tsgo_get_robust(tsgo_optimizer* opt, tsgo_robust* out);
+
+/* Robust kernels per EDGE: a palette of at most TSGO_EDGE_ROBUST_MAX kernels and one byte per edge of the tsgo_graph the handle holds, in
+ * input order (what g2o's per-edge setRobustKernel and GTSAM's per-factor noise model offer).  The usual call: leave
+ * the odometry chain quadratic and robustify the closures, which tsgo_set_robust cannot say because both are type 0.
+ *   entry_of_edge[e] == 0   the edge takes its class's kernel from tsgo_set_robust, looked up at every launch: a later tsgo_set_robust applies
+ *   entry_of_edge[e] == k   (k >= 1) the edge takes entries[k - 1], whatever its class; kernel ids and width rules are tsgo_set_robust's
+ * s = e^T Omega e is unchanged; rho and w = rho'(s) come from the edge's effective kernel.  An edge whose entry is NONE is exempt: rho = s
+ * and w = 1 exactly.  The setting applies wherever a class kernel is evaluated: the linearisation under every `rules`, the chi^2-only pass
+ * of rules 2 and 3, the g'Hg pass of rules 3, tsgo_linearize and tsgo_solve_step, tsgo_edge_report (per record; the class summaries stay
+ * indexed by e_type and `downweighted` counts w < 1 as before), tsgo_marginals, tsgo_joint_marginals, tsgo_gate_edges (Sigma only; the
+ * candidate itself is never robustified) and tsgo_sample_marginals, and the inner runs of tsgo_gnc.
+ *   Clearing: n_entries == 0 with entry_of_edge == NULL and n_mask == 0.  An all-zero mask is the same as cleared (stats->active = 0), and
+ *   tsgo_get_edge_robust then returns no entries and zeros.  A cleared handle runs the same device code, bit for bit, as one that was never
+ *   given a per-edge setting.
+ *   Lifetime: that of an edge-information edit, not of the handle: the next tsgo_set_graph, refill or rebuild, drops the setting, so a
+ *   reused handle does what a fresh one does.  tsgo_set_robust, tsgo_set_edge_information, tsgo_init_estimates, tsgo_gnc and tsgo_optimize
+ *   keep it.
+ *   Solver state: the rule of tsgo_set_robust.  A call that changes anything makes the next linearisation build a fresh multigrid
+ *   hierarchy; the warm start's history stays.
+ * tsgo_get_edge_robust: the number of entries, the entries (entries_out has room for TSGO_EDGE_ROBUST_MAX; those past the count are zero)
+ * and the byte of every edge.  precision 64 only.
+ * Errors (< 0, text in tsgo_last_error; everything is validated before anything changes, the handle is exactly as before): a NULL handle;
+ * no graph set; n_mask != n_edges; n_entries outside [0, TSGO_EDGE_ROBUST_MAX]; entries == NULL with n_entries > 0; entry_of_edge == NULL
+ * with edges to read; an unknown kernel id; a delta that is not finite or outside [1e-6, 1e6] on an entry whose kernel uses one; an
+ * entry_of_edge value above n_entries; precision = 32; an edge-sharded handle (world > 1); for the get call cap_edges < n_edges, or a NULL
+ * output with something to return. */
+#define TSGO_EDGE_ROBUST_MAX 15
+typedef struct tsgo_edge_robust_entry {
+    int32_t kernel;      /* TSGO_ROBUST_* */
+    int32_t reserved;    /* 0 */
+    double  delta;       /* width; ignored by NONE */
+} tsgo_edge_robust_entry;
+typedef struct tsgo_edge_robust_stats {
+    int64_t edges_by_entry[TSGO_EDGE_ROBUST_MAX + 1];   /* [0] = edges left to their class, [k] = edges given entries[k - 1] */
+    int64_t overridden_by_class[5];                     /* edges with a non-zero entry, per tsgo_graph.e_type */
+    int32_t active, reserved;                           /* 1 when any edge has a non-zero entry */
+    double  ms_total;
+} tsgo_edge_robust_stats;
+int tsgo_set_edge_robust(tsgo_optimizer* opt, int32_t n_entries, const tsgo_edge_robust_entry* entries,
+                         const uint8_t* entry_of_edge /* 1 per edge of the tsgo_graph, input order */, int64_t n_mask,
+                         tsgo_edge_robust_stats* stats /* may be NULL */);
+int tsgo_get_edge_robust(tsgo_optimizer* opt, int32_t* n_entries_out, tsgo_edge_robust_entry* entries_out /* room for TSGO_EDGE_ROBUST_MAX */,
+                         uint8_t* entry_of_edge_out, int64_t cap_edges);
 
 /* Powell's dogleg trust-region loop, tsgo_config.rules = 3 (no reference counterpart).  The model is that of rules = 2 with lambda = 0:
  * chi^2(x + d) ~ chi^2 - 2 b^T d + d^T H d, with H, b and chi^2 from the linearisation of rules = 2 (b zeroed at fixed vertices, the gauge

@@ -130,6 +130,15 @@ public:
         std::cout << "Summary() error = " << stats.chi2[last] << std::endl;
     }
     const tsgo_stats& Stats() const { return stats; }
+    // Optimises the graph the handle HOLDS (SetGraph) without handing it over again, so that what was set on it since — SetEdgeRobust,
+    // SetEdgeInformation, InitEstimates — stays in force; `graph` (the one given to SetGraph) receives the positions.  Throws on an error.
+    void OptimizeHeld(Graph* graph) {
+        if (tsgo_optimize(handle, (int)iterations, &stats)) throw std::runtime_error(tsgo_last_error());
+        if (!graph) return;
+        std::vector<double> out(graph->VertexCount() * 3);
+        if (tsgo_get_vertices(handle, out.data())) throw std::runtime_error(tsgo_last_error());
+        graph->SetPositions(out);
+    }
     // rules = 2 (Levenberg-Marquardt, tsgo_config.rules): what the last Optimize did trial by trial — Stats().lm_lambda / lm_gain / lm_pred /
     // lm_chi2_trial, entries 0 .. Stats().trace_len - 1 — and how many of its steps were rolled back
     int StepsRejected() const { return stats.steps_rejected; }
@@ -180,6 +189,27 @@ public:
         tsgo_robust r;
         if (tsgo_get_robust(handle, &r)) throw std::runtime_error(tsgo_last_error());
         return r;
+    }
+
+    // Robust kernels per EDGE of the graph the handle holds (tsgo_set_edge_robust): a palette of at most TSGO_EDGE_ROBUST_MAX entries and
+    // one byte per edge in input order — 0: the edge keeps its class's kernel (SetRobust), k >= 1: palette[k - 1] whatever the class; an
+    // entry with TSGO_ROBUST_NONE exempts its edges (the odometry chain, a surveyed beacon).  An empty palette with an empty mask clears.
+    // The setting goes with the next SetGraph / Optimize(&graph).  Throws on an error (a mask of the wrong length, a value above the
+    // palette's size, an unknown kernel, precision 32).
+    void SetEdgeRobust(const std::vector<tsgo_edge_robust_entry>& palette, const std::vector<uint8_t>& entry_of_edge, tsgo_edge_robust_stats* stats = nullptr) {
+        if (tsgo_set_edge_robust(handle, (int32_t)palette.size(), palette.empty() ? nullptr : palette.data(), entry_of_edge.empty() ? nullptr : entry_of_edge.data(),
+                                 (int64_t)entry_of_edge.size(), stats))
+            throw std::runtime_error(tsgo_last_error());
+    }
+    // ... read back: the palette, and (if asked for) the byte of every one of the graph's n_edges edges
+    std::vector<tsgo_edge_robust_entry> EdgeRobust(size_t n_edges, std::vector<uint8_t>* entry_of_edge = nullptr) const {
+        std::vector<tsgo_edge_robust_entry> palette(TSGO_EDGE_ROBUST_MAX);
+        std::vector<uint8_t> mask(n_edges);
+        int32_t n = 0;
+        if (tsgo_get_edge_robust(handle, &n, palette.data(), mask.data(), (int64_t)n_edges)) throw std::runtime_error(tsgo_last_error());
+        palette.resize((size_t)n);
+        if (entry_of_edge) entry_of_edge->swap(mask);
+        return palette;
     }
 
     // Marginal covariances at the estimates of the last Optimize (tsgo_marginals): 9 doubles per id, row-major; a landmark's 2x2 block

@@ -37,6 +37,18 @@ class tsgo_robust(C.Structure):
     _fields_ = [("kernel", C.c_int32 * 5), ("reserved", C.c_int32), ("delta", C.c_double * 5)]
 
 
+TSGO_EDGE_ROBUST_MAX = 15
+
+
+class tsgo_edge_robust_entry(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("reserved", C.c_int32), ("delta", C.c_double)]
+
+
+class tsgo_edge_robust_stats(C.Structure):
+    _fields_ = [("edges_by_entry", C.c_int64 * (TSGO_EDGE_ROBUST_MAX + 1)), ("overridden_by_class", C.c_int64 * 5), ("active", C.c_int32),
+                ("reserved", C.c_int32), ("ms_total", C.c_double)]
+
+
 class tsgo_dogleg_params(C.Structure):
     _fields_ = [("radius0", C.c_double), ("radius_min", C.c_double), ("radius_max", C.c_double), ("chi2_rel_tol", C.c_double)]
 
@@ -144,7 +156,8 @@ HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_default_gnc"
 DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_graph", "tsgo_reset_history", "tsgo_optimize", "tsgo_get_vertices",
                   "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
                   "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust", "tsgo_edge_report", "tsgo_gate_edges", "tsgo_init_estimates",
-                  "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc", "tsgo_sample_marginals", "tsgo_set_dogleg", "tsgo_get_dogleg", "tsgo_get_dogleg_trace"]
+                  "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc", "tsgo_sample_marginals", "tsgo_set_dogleg", "tsgo_get_dogleg", "tsgo_get_dogleg_trace",
+                  "tsgo_set_edge_robust", "tsgo_get_edge_robust"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply",
                    "tsgo_testing_sym_scan", "tsgo_testing_sym_product", "tsgo_testing_schur_pattern"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
@@ -199,6 +212,8 @@ def _declare_device(L):
     L.tsgo_sample_marginals.argtypes = [vp, C.c_int32, C.c_uint64, C.c_double, vp, C.c_int64, vp, C.c_int64, C.POINTER(tsgo_sample_stats)]
     L.tsgo_set_robust.argtypes = [vp, C.POINTER(tsgo_robust)]
     L.tsgo_get_robust.argtypes = [vp, C.POINTER(tsgo_robust)]
+    L.tsgo_set_edge_robust.argtypes = [vp, C.c_int32, vp, vp, C.c_int64, C.POINTER(tsgo_edge_robust_stats)]
+    L.tsgo_get_edge_robust.argtypes = [vp, C.POINTER(C.c_int32), vp, vp, C.c_int64]
     L.tsgo_set_dogleg.argtypes = [vp, C.POINTER(tsgo_dogleg_params)]
     L.tsgo_get_dogleg.argtypes = [vp, C.POINTER(tsgo_dogleg_params)]
     L.tsgo_get_dogleg_trace.argtypes = [vp, C.POINTER(tsgo_dogleg_trace)]

@@ -44,10 +44,10 @@
         if constexpr (kDoglegKernels) launch_ghg_f64(out);
     }
     void launch_ghg_f64(T* out) {
-        if (report_lm_priors()) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(rk(), [&](auto rk) {
+        if (report_lm_priors()) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick_rk([&](auto rk) {
             launch(k_dl_ghg_lm_prior<T, g, rk>, nbL, tl, (const T*)lmrec, (const uint32_t*)maps.rep_pl_edge, (const T*)dl_gl, out + nbP, lm_prior_args(), robust_args());
         }); });
-        pick_edge_walk([&](auto g, auto general, auto pri) { pick<0, 1>(rk(), [&](auto rk) {
+        pick_edge_walk([&](auto g, auto general, auto pri) { pick_rk([&](auto rk) {
             launch(k_dl_ghg<T, g, general, pri, rk>, nbP, tp, to, (const T*)ps, (const T*)lmrec, maps.edge_maps(), (const T*)dl_gp, (const T*)dl_gl, out, general ? odom_analytic_flag() : 0,
                    pri ? pose_prior_args() : no_priors(), robust_args());
         }); });

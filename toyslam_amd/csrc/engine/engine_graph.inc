@@ -209,6 +209,7 @@
 
     int refill(const tsgo_graph& g) {
         const auto t0 = std::chrono::steady_clock::now();
+        drop_edge_robust();      // a per-edge robust setting goes with the values it was made for, as an edge-information edit does
         const int rc = refill_values(g);
         // any failure leaves tables, lever arms and solver state half-updated: the handle then holds no graph and the next
         // tsgo_set_graph rebuilds from scratch
@@ -254,6 +255,7 @@
         if (last_set_reused) return refill(g);
         if (int rc = carry_out()) return rc;
         release();
+        drop_edge_robust();
         drop_structure_maps();      // the index described the old tables, and its device maps lived in the slabs just released
         BuildOptions bo; bo.rank = cfg.rank; bo.world = cfg.world; bo.lanes_per_pose = cfg.lanes_per_pose; bo.lanes_per_lm = cfg.lanes_per_lm;
         bo.fill_planes = false;

@@ -62,7 +62,9 @@
     static GateArgs<T> no_gate() { return GateArgs<T>{nullptr, nullptr, nullptr, 0, T(0), nullptr, 0}; }
     // Robust kernels per edge class (tsgo_set_robust): belongs to the HANDLE (it survives tsgo_set_graph; tsgo_hip.hip lists the lifetimes), read by every launch that
     // robustifies.  A setting equal to the default takes the RK = 0 instantiations — the compile-time Huber, exactly what was launched
-    // before the setting existed; anything else the RK = 1 ones, which read kind and width from the by-value argument below.
+    // before the setting existed; anything else the RK = 1 ones, which read kind and width from the by-value argument below.  While a
+    // per-edge setting is active (tsgo_set_edge_robust, engine_edge_robust.inc; f64 handles only) the RK = 2 ones, which also read a byte per
+    // slot, record or edge and the palette behind the pointers at the argument's end.
     tsgo_robust robust = default_robust();
     static tsgo_robust default_robust() { tsgo_robust r; tsgo_default_robust(&r); return r; }
     static bool same_robust(const tsgo_robust& a, const tsgo_robust& b) {
@@ -70,10 +72,16 @@
             if (a.kernel[k] != b.kernel[k] || (a.kernel[k] != TSGO_ROBUST_NONE && a.delta[k] != b.delta[k])) return false;      // NONE ignores its width
         return true;
     }
-    int rk() const { return same_robust(robust, default_robust()) ? 0 : 1; }
+    int rk() const { return er.active ? 2 : (same_robust(robust, default_robust()) ? 0 : 1); }
+    // pick_rk(f): f(RK) for this handle; the RK = 2 kernels are instantiated for double alone
+    template <typename F> void pick_rk(F&& f) {
+        if constexpr (sizeof(T) == 8) pick<0, 1, 2>(rk(), std::forward<F>(f));
+        else pick<0, 1>(rk(), std::forward<F>(f));
+    }
     RobustArgs<T> robust_args() const {
         RobustArgs<T> a{};
         for (int k = 0; k < kEdgeClasses; ++k) { a.kind[k] = robust.kernel[k]; a.delta[k] = (T)robust.delta[k]; }
+        if (er.active) { a.pal = maps.er_pal; a.by_lm = maps.er_lm; a.by_pose = maps.er_pose; a.odom = maps.er_od; a.pose_prior = maps.er_pp; a.lm_prior = maps.er_pl; a.edge = maps.er_edge; }
         return a;
     }
     int set_robust(const tsgo_robust& r) override {
@@ -91,13 +99,13 @@
     void launch_lin_lm() {              // (tsgo_time_kernel too)
         const int zf = (py_rules() || trial_rules()) ? 1 : 0;
         if (tl.n_slices == 0) return;
-        pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick<0, 1>(rk(), [&](auto rk) {
+        pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick_rk([&](auto rk) {
             launch_table(k_lin_lm<T, g, pri, rk>, nbL, tl, zf, lmrec, (const T*)ps, (const T*)gauge_l, ninv, tl, (T)lambda, pri ? lm_prior_args() : no_priors(), robust_args());
         }); }); });
     }
     void launch_lin_pose_only() {       // (tsgo_time_kernel too)
         const int zf = (py_rules() || trial_rules()) ? 1 : 0;
-        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick<0, 1>(rk(), [&](auto rk) {
+        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick_rk([&](auto rk) {
             launch_table(k_lin_pose<T, g, general, pri, rk>, nbP, tp, zf, (const T*)ps, (const T*)lmrec, to.row_off, (const T*)gauge_p, tp, to, pr.pose_first, pr.pose_last, part,
                          part + (size_t)pr.P * 18, (T)lambda, general ? odom_analytic_flag() : 0, pri ? pose_prior_args() : no_priors(), robust_args());
         }); }); }); });
@@ -105,10 +113,10 @@
     // rules = 2: robustified chi^2 at the current estimates, nbP partials into `out` (tsgo_lm_kernels.h; tsgo_time_kernel 7 too).  One launch,
     // and one more in front of it on a graph with priors (the landmark priors' partials, which k_chi2<.., 1> folds as k_lin_pose<.., 1> does)
     void launch_chi2(T* out) {
-        if (pr.has_priors && tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(rk(), [&](auto rk) {
+        if (pr.has_priors && tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick_rk([&](auto rk) {
             launch(k_chi2_lm_prior<T, g, rk>, nbL, tl, (const T*)lmrec, lm_prior_args(), robust_args());
         }); });
-        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick<0, 1>(rk(), [&](auto rk) {
+        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(oj(), [&](auto general) { pick<0, 1>(pr.has_priors, [&](auto pri) { pick_rk([&](auto rk) {
             launch(k_chi2<T, g, general, pri, rk>, nbP, tp, to, (const T*)ps, (const T*)lmrec, out, pri ? pose_prior_args() : no_priors(), robust_args());
         }); }); }); });
     }

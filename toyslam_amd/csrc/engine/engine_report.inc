@@ -29,10 +29,10 @@
     }
     // the pass (tsgo_time_kernel 8 too).  rec = nullptr: summary only
     void launch_edge_report(T* rec) {
-        if (report_lm_priors()) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<0, 1>(rk(), [&](auto rk) {
+        if (report_lm_priors()) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick_rk([&](auto rk) {
             launch(k_edge_report_lm_prior<T, g, rk>, nbL, tl, (const T*)lmrec, (const uint32_t*)maps.rep_pl_edge, rec, maps.rep_part + (size_t)nbP * kEdgeClasses, lm_prior_args(), robust_args());
         }); });
-        pick_edge_walk([&](auto g, auto general, auto pri) { pick<0, 1>(rk(), [&](auto rk) {
+        pick_edge_walk([&](auto g, auto general, auto pri) { pick_rk([&](auto rk) {
             launch(k_edge_report<T, g, general, pri, rk>, nbP, tp, to, (const T*)ps, (const T*)lmrec, maps.edge_maps(), rec, maps.rep_part, pri ? pose_prior_args() : no_priors(), robust_args());
         }); });
     }

@@ -33,15 +33,15 @@
     template <int NV> void launch_sample_rhs(MbBuf& B, T* u, uint64_t seed, int k0, int nc) {
         constexpr int CH = NV == 1 ? 1 : 4;
         const SampleBatch sb{SampleSeed{(uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32)}, k0, nc, NV};
-        if (tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
-            launch(k_smp_rhs_lm<T, g, CH>, nbL, tl, (const T*)ps, (const T*)lmrec, (const uint32_t*)maps.smp_lm_edge, (const uint32_t*)maps.rep_pl_edge,
+        if (tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) { pick<2, 1>(rk(), [&](auto rk) {      // (RK 1 serves the default setting too; listed last: what pick falls back to)
+            launch(k_smp_rhs_lm<T, g, CH, rk>, nbL, tl, (const T*)ps, (const T*)lmrec, (const uint32_t*)maps.smp_lm_edge, (const uint32_t*)maps.rep_pl_edge,
                    (const int*)maps.smp_lm_vertex, (const T*)gauge_l, pr.has_priors ? lm_prior_args() : no_priors(), robust_args(), sb, u);
-        });
-        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) {
-            launch(k_smp_rhs_pose<T, g, CH>, nbP, tp, to, (const T*)ps, (const T*)lmrec, (const uint32_t*)maps.rep_lm_edge, (const uint32_t*)maps.rep_od_edge,
+        }); });
+        pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<2, 1>(rk(), [&](auto rk) {
+            launch(k_smp_rhs_pose<T, g, CH, rk>, nbP, tp, to, (const T*)ps, (const T*)lmrec, (const uint32_t*)maps.rep_lm_edge, (const uint32_t*)maps.rep_od_edge,
                    (const uint32_t*)maps.rep_pp_edge, (const int*)maps.smp_pose_vertex, (const T*)gauge_p, (const T*)u,
                    pr.has_priors ? pose_prior_args() : no_priors(), robust_args(), odom_analytic_flag(), sb, B.r);
-        });
+        }); });
     }
 
     template <int NV> int sample_run(int K, uint64_t seed, double tol, double* cov, double* samples, tsgo_sample_stats& ss) {

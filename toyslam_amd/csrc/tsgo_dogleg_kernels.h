@@ -54,7 +54,7 @@ __global__ __launch_bounds__(kBlock) void k_dl_gradient(int P, int L, const T* _
 
 // What the lane that visits an edge adds to g'Hg: v = A g_1 + B g_2 with the Jacobians the linearisation uses for the edge's class, then
 // sum_k a_k v_k^2 with a = robust weight * information, from the same edge function call (and robust_class<RK> selection) the report and
-// the linearisation make.  g1: the gradient of the walking lane's own pose, loaded once; a neighbour's (gp[j], gl[l]) is gathered BEHIND
+// the linearisation make (RK = 2: the byte of the visited edge, robust_at on ra.edge).  g1: the gradient of the walking lane's own pose, loaded once; a neighbour's (gp[j], gl[l]) is gathered BEHIND
 // the slot's coalesced plane loads (the walk's VGPR note).  The walk hands over neither the landmark's nor the neighbour's number: the
 // first is the slot's index word again (the walk has it in a register already: the same address, no store in between), the second
 // follows from the record pointer.  The visitor writes nothing, so "skipped before loaded" asks nothing of it.
@@ -72,22 +72,22 @@ template <typename T, int OJ, int RK> struct GhgVisitor {
     const Kernel rk_lm = robust_class<RK>(ra, kClassLm), rk_odom = robust_class<RK>(ra, kClassOdom);
     T acc = 0;
     // A = [-R^T | (ppy, -ppx)], B = R^T
-    __device__ __forceinline__ void lm(uint32_t, size_t k, const PoseAt<T>& p, T lx, T ly) {
+    __device__ __forceinline__ void lm(uint32_t e, size_t k, const PoseAt<T>& p, T lx, T ly) {
         const LmMeas<T> z = lm_meas<T>(tb, k);
         const uint32_t l = tb.idx[k];
-        const LmLin<T> o = lm_linearize<T>(p.x, p.y, p.c, p.s, lx, ly, z.zx, z.zy, z.w0, z.w1, rk_lm);
+        const LmLin<T> o = lm_linearize<T>(p.x, p.y, p.c, p.s, lx, ly, z.zx, z.zy, z.w0, z.w1, robust_at<RK>(ra, rk_lm, ra.edge, e));
         const auto g2 = ld2<T>(gl + (size_t)l * 2);
         const T d0 = g2.x - g1x, d1 = g2.y - g1y;
         const T v0 = p.c * d0 + p.s * d1 + o.ppy * g1t, v1 = p.c * d1 - p.s * d0 - o.ppx * g1t;
         acc += o.a0 * v0 * v0 + o.a1 * v1 * v1;
     }
     // constants: A = -I, B = +I; analytic (tsgo_math.h): A = [[-M, q], [0 0 -kappa]], B = [[M, 0], [0 0 kappa]]
-    __device__ __forceinline__ void odom(uint32_t, size_t k, const PoseAt<T>& p, const T* qj) {
+    __device__ __forceinline__ void odom(uint32_t e, size_t k, const PoseAt<T>& p, const T* qj) {
         const OdomMeas<T> z = odom_meas<T>(od, k);
         const PoseAt<T> pj = pose_at<T>(qj);
         const T* g2 = gp + (size_t)((qj - ps) >> 2) * 3;
         const T t0 = g2[0] - g1x, t1 = g2[1] - g1y, tt = g2[2] - g1t;
-        const OdomLin<T> o = odom_linearize<T>(p.x, p.y, p.c, p.s, pj.x, pj.y, pj.c, pj.s, z.mi, z.w, rk_odom);
+        const OdomLin<T> o = odom_linearize<T>(p.x, p.y, p.c, p.s, pj.x, pj.y, pj.c, pj.s, z.mi, z.w, robust_at<RK>(ra, rk_odom, ra.edge, e));
         T v0 = t0, v1 = t1, vt = tt;
         if (OJ && analytic) {
             const OdomJac<T> j = odom_jacobians<T>(p.x, p.y, p.c, p.s, pj.x, pj.y, pj.c, pj.s, z.mi);
@@ -96,19 +96,21 @@ template <typename T, int OJ, int RK> struct GhgVisitor {
         acc += o.a[0] * v0 * v0 + o.a[1] * v1 * v1 + o.a[2] * vt * vt;
     }
     // e = T1 p1 - T2 p2: A = [I | u], B = -[I | v] (vlm_linearize: u, v)
-    __device__ __forceinline__ void vlm(uint32_t, size_t k, const PoseAt<T>& p, const T* qj) {
+    __device__ __forceinline__ void vlm(uint32_t e, size_t k, const PoseAt<T>& p, const T* qj) {
         const OdomMeas<T> z = odom_meas<T>(od, k);
         const PoseAt<T> pj = pose_at<T>(qj);
         const T* g2 = gp + (size_t)((qj - ps) >> 2) * 3;
         const T g2x = g2[0], g2y = g2[1], g2t = g2[2];
-        const VlmLin<T> o = vlm_linearize<T>(p.x, p.y, p.c, p.s, pj.x, pj.y, pj.c, pj.s, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1], robust_class<RK>(ra, kClassVlm));
+        const VlmLin<T> o = vlm_linearize<T>(p.x, p.y, p.c, p.s, pj.x, pj.y, pj.c, pj.s, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1],
+                                                   robust_at<RK>(ra, robust_class<RK>(ra, kClassVlm), ra.edge, e));
         const T v0 = (g1x + o.u0 * g1t) - (g2x + o.v0 * g2t), v1 = (g1y + o.u1 * g1t) - (g2y + o.v1 * g2t);
         acc += o.om0 * v0 * v0 + o.om1 * v1 * v1;
     }
     // J = blockdiag(R_m^T, 1)
-    __device__ __forceinline__ void pose_prior(uint32_t, const T* q, const PoseAt<T>& p) {
+    __device__ __forceinline__ void pose_prior(uint32_t e, const T* q, const PoseAt<T>& p) {
         const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C), w01 = ld2<T>(q + PRI_W0);
-        const PosePriorLin<T> o = pose_prior_linearize<T>(m01.x, m01.y, cs.x, cs.y, w01.x, w01.y, q[PRI_W2], p.x, p.y, p.c, p.s, robust_class<RK>(ra, kClassPosePrior));
+        const PosePriorLin<T> o = pose_prior_linearize<T>(m01.x, m01.y, cs.x, cs.y, w01.x, w01.y, q[PRI_W2], p.x, p.y, p.c, p.s,
+                                                                    robust_at<RK>(ra, robust_class<RK>(ra, kClassPosePrior), ra.edge, e));
         const T v0 = cs.x * g1x + cs.y * g1y, v1 = cs.x * g1y - cs.y * g1x;
         acc += o.a0 * v0 * v0 + o.a1 * v1 * v1 + o.a2 * g1t * g1t;
     }
@@ -119,9 +121,9 @@ template <typename T, int RK> struct GhgLmPriorVisitor {
     const RobustArgs<T>& ra;
     const T gx, gy;
     T acc = 0;
-    __device__ __forceinline__ void lm_prior(uint32_t, const T* q, T lx, T ly) {
+    __device__ __forceinline__ void lm_prior(uint32_t e, const T* q, T lx, T ly) {
         const auto m = ld2<T>(q + PRL_MX), w = ld2<T>(q + PRL_W0);
-        const LmPriorLin<T> o = lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly, robust_class<RK>(ra, kClassLmPrior));
+        const LmPriorLin<T> o = lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly, robust_at<RK>(ra, robust_class<RK>(ra, kClassLmPrior), ra.edge, e));
         acc += o.a0 * gx * gx + o.a1 * gy * gy;
     }
 };

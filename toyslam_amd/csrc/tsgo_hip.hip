@@ -25,6 +25,7 @@
 //   engine/engine_gate.inc         tsgo_gate_edges: candidate edges against the joint marginal of their vertices (Mahalanobis gate)
 //   engine/engine_init.inc         tsgo_init_estimates: estimates from an odometry spanning tree (pointer jumping), landmarks from their observations
 //   engine/engine_edit.inc         tsgo_set_edge_information / tsgo_get_edge_information: the information diagonal of listed edges, in place
+//   engine/engine_edge_robust.inc  tsgo_set_edge_robust / tsgo_get_edge_robust: a palette of robust kernels and one byte per input edge; the per-slot byte arrays of the RK = 2 kernels
 //   engine/engine_gnc.inc          tsgo_gnc: graduated non-convexity (truncated least squares), one reweighting pass over the tables per round
 //   engine/engine_dogleg.inc       rules = 3, Powell's dogleg trust-region loop: one linearisation and one solve per ACCEPTED step, trials from the snapshot; tsgo_set_dogleg,
 //                                  tsgo_get_dogleg_trace.  Kernels: tsgo_dogleg_kernels.h (f64 only) — the gradient as dense vectors, g'Hg by the once-per-edge walk
@@ -184,6 +185,8 @@ struct IEngine {
     virtual int init_estimates(int what, const uint8_t* mask, int64_t n_mask, tsgo_init_stats* st) = 0;
     virtual int set_edge_information(int64_t n, const int64_t* edge_idx, const double* e_inf, tsgo_edge_info_stats* st) = 0;
     virtual int get_edge_information(double* e_inf_out, int64_t cap_edges) = 0;
+    virtual int set_edge_robust(int32_t n_entries, const tsgo_edge_robust_entry* entries, const uint8_t* of_edge, int64_t n_mask, tsgo_edge_robust_stats* st) = 0;
+    virtual int get_edge_robust(int32_t* n_out, tsgo_edge_robust_entry* entries_out, uint8_t* of_edge_out, int64_t cap_edges) = 0;
     virtual int gnc(const tsgo_gnc_params& p, const uint8_t* subject, int64_t n_mask, double* w_out, int64_t cap_edges, tsgo_gnc_stats* st) = 0;
 #ifdef TSGO_TESTING
     virtual int testing_apply(int which, const double* in, double* out, int n_cols) = 0;
@@ -309,6 +312,8 @@ template <typename T> struct Engine : IEngine {
     // ---- What the solver learns while it runs has one of three lifetimes; a new member goes into one of the three groups.
     // 1. Forgotten at EVERY tsgo_set_graph, refill or new structure (a refilled handle does, bit for bit, what a fresh one does): reset_solver_state()
     //    assigns fresh_memory(); refill_values() and carry_in() then put the warm-start history back under warm_requests.
+    //    (Not solver memory, but of this lifetime too: the per-edge robust setting `er`, engine_edge_robust.inc — dropped by refill() and set_graph
+    //    themselves, not by reset_solver_state(), which tsgo_init_estimates also runs and which must keep it.)
     static constexpr int kAgeSlots = 16;
     struct SolverMemory {
         bool have_prev = false;            // warm start: hist[0] holds the pose delta of the previous solve
@@ -353,6 +358,11 @@ template <typename T> struct Engine : IEngine {
         uint32_t* smp_lm_edge = nullptr;
         int *smp_pose_vertex = nullptr, *smp_lm_vertex = nullptr;
         bool smp_ready = false;
+        // tsgo_set_edge_robust (engine_edge_robust.inc): a byte per slot of by_lm, by_pose and odom, per record of the two prior lists and per
+        // input edge, and the palette (RobustArgs, tsgo_kernels.h)
+        uint8_t *er_lm = nullptr, *er_pose = nullptr, *er_od = nullptr, *er_pp = nullptr, *er_pl = nullptr, *er_edge = nullptr;
+        RobustEntry<T>* er_pal = nullptr;
+        bool er_ready = false;
     } maps;
     void drop_structure_maps() { sindex.clear(); maps = StructureMaps(); }
     const VertexIndex& vertices() { return sindex.vertices(structure.v_id, pr); }
@@ -567,6 +577,7 @@ template <typename T> struct Engine : IEngine {
 #include "engine/engine_sample.inc"
 #include "engine/engine_init.inc"
 #include "engine/engine_edit.inc"
+#include "engine/engine_edge_robust.inc"
 #include "engine/engine_gnc.inc"
 #include "engine/engine_dogleg.inc"
 #ifdef TSGO_TESTING
@@ -744,6 +755,15 @@ int tsgo_get_robust(tsgo_optimizer* o, tsgo_robust* out) {
     if (!o || !out) return tsgo::set_error(-1, "tsgo_get_robust: null argument");
     o->eng->get_robust(out);
     return 0;
+}
+int tsgo_set_edge_robust(tsgo_optimizer* o, int32_t n_entries, const tsgo_edge_robust_entry* entries, const uint8_t* entry_of_edge, int64_t n_mask,
+                         tsgo_edge_robust_stats* stats) {
+    if (!o) return tsgo::set_error(-1, "tsgo_set_edge_robust: null handle");
+    return o->eng->set_edge_robust(n_entries, entries, entry_of_edge, n_mask, stats);
+}
+int tsgo_get_edge_robust(tsgo_optimizer* o, int32_t* n_entries_out, tsgo_edge_robust_entry* entries_out, uint8_t* entry_of_edge_out, int64_t cap_edges) {
+    if (!o) return tsgo::set_error(-1, "tsgo_get_edge_robust: null handle");
+    return o->eng->get_edge_robust(n_entries_out, entries_out, entry_of_edge_out, cap_edges);
 }
 int tsgo_set_dogleg(tsgo_optimizer* o, const tsgo_dogleg_params* p) {
     if (!o || !p) return tsgo::set_error(-1, "tsgo_set_dogleg: null argument");

@@ -209,10 +209,35 @@ template <typename T> struct PriorArgs { const uint32_t* off; const T* rec; T* l
 // setting existed; RK = 1 reads kind and width of the class whose table is being walked from this by-value kernel argument (kernarg
 // memory, scalar loads).  The class is known where the edge function is called (the LM rows, ODOM against virtual landmark by kVlmMask,
 // the prior records) and the kind is the same for every lane: the selection in robust_eval is a scalar branch.
-template <typename T> struct RobustArgs { int kind[kEdgeClasses]; int pad; T delta[kEdgeClasses]; };
+//
+// RK = 2: robust kernels per EDGE (tsgo_set_edge_robust, include/tsgo.h; engine/engine_edge_robust.inc).  An edge carries one byte: 0 leaves
+// it to its class (kind and width from this argument, as under RK = 1, so a later tsgo_set_robust applies), k >= 1 gives it entry k - 1 of
+// the handle's palette, a device table of at most kEdgeRobustMax (width, kind) records of 16 B in f64 — one pair load, and the whole
+// table sits in a handful of cache lines.  The kernels that walk a table read the byte of the SLOT (one array per table, in slot order:
+// contiguous in lane order like the slot's own planes, 0 on padding) or of the prior RECORD; the visitors of the once-per-edge walk and
+// the sampling kernels, which hold the input edge index anyway, read the byte of the EDGE.  The kernel object is then per lane and
+// robust_eval a per-lane switch: divergent only in rows that mix kernels.  f64 only.  The pointers sit behind the class fields and are
+// null (never read) under RK = 0 and 1.
+constexpr int kEdgeRobustMax = 15;
+template <typename T> struct RobustEntry { T delta; int kind; int pad; };
+template <typename T> struct RobustArgs {
+    int kind[kEdgeClasses]; int pad; T delta[kEdgeClasses];
+    const RobustEntry<T>* pal;                                  // RK = 2 from here on: the palette
+    const uint8_t *by_lm, *by_pose, *odom;                      // ... a byte per slot of the lm-major LM, pose-major LM and pose-pose tables
+    const uint8_t *pose_prior, *lm_prior;                       // ... a byte per prior record
+    const uint8_t* edge;                                        // ... a byte per input edge
+};
 template <int RK, typename T> __device__ __forceinline__ auto robust_class(const RobustArgs<T>& ra, int cls) {
     if constexpr (RK == 0) return HuberDefault{};
     else return Robust<T>{ra.kind[cls], ra.delta[cls]};
+}
+// The kernel of ONE slot, record or edge: the class's (cls_kernel = robust_class<RK>) unless RK = 2 and bytes[k] names a palette entry.
+template <int RK, typename T, typename K> __device__ __forceinline__ K robust_at(const RobustArgs<T>& ra, const K& cls_kernel, const uint8_t* __restrict__ bytes, size_t k) {
+    if constexpr (RK == 2) {
+        const uint32_t b = bytes[k];
+        if (b != 0u) { const RobustEntry<T> e = ra.pal[b - 1u]; return Robust<T>{e.kind, e.delta}; }
+    }
+    return cls_kernel;
 }
 
 // Pose prior (type 3): e_t = R_m^T (t - t_m), e_th = wrap(th - m_th); J = blockdiag(R_m^T, 1).  With a = robust weight * (w0, w1, w2):
@@ -233,7 +258,7 @@ template <typename T, typename K> __device__ __forceinline__ T pose_prior_fold(c
 //   writes: slot planes a0 a1 ppx ppy (lm-major copy), lmrec[l][2..6] = Dl^-1, u
 // PRI = 1: the landmark priors (type 4: D_l += Omega_w, b_l -= Omega_w (l - m)) before the inverse, and one chi^2 partial of them per
 // workgroup into pa.lm_chi (every wave reaches the workgroup sum: none leaves early)
-// RK = 1: the robust kernels of classes LM and landmark prior from ra (RobustArgs above)
+// RK = 1: the robust kernels of classes LM and landmark prior from ra (RobustArgs above); RK = 2: per slot / per record (ra.by_lm, ra.lm_prior)
 template <typename T, int G, int PRI = 0, int RK = 0>
 __global__ __launch_bounds__(kBlock) void k_lin_lm(const uint32_t* __restrict__ row_off, int n_slices, int n_vertices, int xcd8, int zero_fixed,
                                                    T* __restrict__ lmrec, const T* __restrict__ ps, const T* __restrict__ gauge_l,
@@ -257,7 +282,7 @@ __global__ __launch_bounds__(kBlock) void k_lin_lm(const uint32_t* __restrict__ 
         const T* q = ps + (size_t)i * 4;
         const auto q01 = ld2<T>(q), q23 = ld2<T>(q + 2);
         const T x = q01.x, y = q01.y, c = q23.x, s = q23.y;
-        const LmLin<T> o = lm_linearize<T>(x, y, c, s, lx, ly, z.zx, z.zy, z.w0, z.w1, rk_lm);
+        const LmLin<T> o = lm_linearize<T>(x, y, c, s, lx, ly, z.zx, z.zy, z.w0, z.w1, robust_at<RK>(ra, rk_lm, ra.by_lm, k));
         lm_slot_store<T>(tb, k, o);
         dxx += o.a0 * c * c + o.a1 * s * s; dxy += (o.a0 - o.a1) * c * s; dyy += o.a0 * s * s + o.a1 * c * c;
         const T f0 = o.a0 * o.e0, f1 = o.a1 * o.e1;
@@ -272,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void k_lin_lm(const uint32_t* __restrict__ 
             for (uint32_t k = pa.off[l]; k < pa.off[l + 1]; ++k) {
                 const T* q = pa.rec + (size_t)k * PRI_LM_REC;
                 const auto m = ld2<T>(q + PRL_MX), w = ld2<T>(q + PRL_W0);
-                const LmPriorLin<T> o = lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly, robust_class<RK>(ra, kClassLmPrior));
+                const LmPriorLin<T> o = lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly, robust_at<RK>(ra, robust_class<RK>(ra, kClassLmPrior), ra.lm_prior, k));
                 dxx += o.a0; dyy += o.a1; g0 -= o.a0 * o.e0; g1 -= o.a1 * o.e1;
                 chi += o.rho;
             }
@@ -303,7 +328,8 @@ __global__ __launch_bounds__(kBlock) void k_lin_lm(const uint32_t* __restrict__ 
 // ODOM edges under the reference's constant Jacobians are written in that form too when the graph holds the other kind.
 // PRI = 1: the pose priors (type 3, pose_prior_fold) of the pose in the epilogue, before a fixed pose's gradient is zeroed, and the landmark
 // priors' chi^2 partials (pa.lm_chi, left by k_lin_lm<.., 1>) in workgroup 0's partial.  The host lists only the priors of owned poses.
-// RK = 1: the robust kernels of classes LM, ODOM, virtual landmark and pose prior from ra (RobustArgs above)
+// RK = 1: the robust kernels of classes LM, ODOM, virtual landmark and pose prior from ra (RobustArgs above); RK = 2: per slot / per record
+// (ra.by_pose, ra.odom — both slots of a pose-pose edge carry its byte — and ra.pose_prior)
 template <typename T, int G, int OJ = 0, int PRI = 0, int RK = 0>
 __global__ __launch_bounds__(kBlock) void k_lin_pose(const uint32_t* __restrict__ row_off, int n_slices, int n_vertices, int xcd8, int zero_fixed,
                                                      const T* __restrict__ ps, const T* __restrict__ lmrec,
@@ -332,7 +358,7 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(const uint32_t* __restrict_
                 const T* lr = lmrec + (size_t)l * kLmRec;
                 const auto l01 = ld2<T>(lr), l23 = ld2<T>(lr + 2), l45 = ld2<T>(lr + 4);
                 const T lx = l01.x, ly = l01.y, nxx = l23.x, nxy = l23.y, nyy = l45.x, ux = l45.y, uy = lr[6];
-                const LmLin<T> o = lm_linearize<T>(x0, y0, c, s, lx, ly, z.zx, z.zy, z.w0, z.w1, rk_lm);
+                const LmLin<T> o = lm_linearize<T>(x0, y0, c, s, lx, ly, z.zx, z.zy, z.w0, z.w1, robust_at<RK>(ra, rk_lm, ra.by_pose, k));
                 lm_slot_store<T>(tb, k, o);
                 chi += o.rho;
                 const T v0 = o.ppy, v1 = -o.ppx;
@@ -364,7 +390,8 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(const uint32_t* __restrict_
                 const T* oq = ps + (size_t)j * 4;
                 const T xj = oq[0], yj = oq[1], cj = oq[2], sj = oq[3];
                 if (OJ && (raw & kVlmMask)) {      // virtual landmark measurement: mi = (pox, poy, pnx, pny, ., .), w = (w0, w1, .)
-                    const VlmLin<T> v = vlm_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1], robust_class<RK>(ra, kClassVlm));
+                    const VlmLin<T> v = vlm_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1],
+                                                               robust_at<RK>(ra, robust_class<RK>(ra, kClassVlm), ra.odom, k));
                     T h[PP_PLANES];
                     vlm_slot<T>(v, h);
 #pragma unroll
@@ -374,8 +401,9 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(const uint32_t* __restrict_
                     if (!second) chi += v.rho;
                     continue;
                 }
-                const OdomLin<T> o = second ? odom_linearize<T>(xj, yj, cj, sj, x0, y0, c, s, z.mi, z.w, rk_odom)
-                                            : odom_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi, z.w, rk_odom);
+                const auto rk_slot = robust_at<RK>(ra, rk_odom, ra.odom, k);
+                const OdomLin<T> o = second ? odom_linearize<T>(xj, yj, cj, sj, x0, y0, c, s, z.mi, z.w, rk_slot)
+                                            : odom_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi, z.w, rk_slot);
                 if (OJ && odom_analytic) {
                     const OdomBlocks<T> ob = second ? odom_blocks<T>(o, xj, yj, cj, sj, x0, y0, c, s, z.mi) : odom_blocks<T>(o, x0, y0, c, s, xj, yj, cj, sj, z.mi);
                     // H_12 = [[-K, 0], [g^T, -w]] at the first endpoint, its transpose at the second
@@ -418,7 +446,8 @@ __global__ __launch_bounds__(kBlock) void k_lin_pose(const uint32_t* __restrict_
             if constexpr (PRI != 0) {
                 T h00 = 0, h01 = 0, h11 = 0, h22 = 0, b0 = 0, b1 = 0, b2 = 0;
                 for (uint32_t k = pa.off[i]; k < pa.off[i + 1]; ++k)
-                    chi += pose_prior_fold<T>(pa.rec + (size_t)k * PRI_POSE_REC, x0, y0, c, s, h00, h01, h11, h22, b0, b1, b2, robust_class<RK>(ra, kClassPosePrior));
+                    chi += pose_prior_fold<T>(pa.rec + (size_t)k * PRI_POSE_REC, x0, y0, c, s, h00, h01, h11, h22, b0, b1, b2,
+                                                  robust_at<RK>(ra, robust_class<RK>(ra, kClassPosePrior), ra.pose_prior, k));
                 o[0] += h00; o[1] += h01; o[3] += h11; o[5] += h22; o[6] += b0; o[7] += b1; o[8] += b2;
             }
             if (fixed_here) { o[6] = 0; o[7] = 0; o[8] = 0; }

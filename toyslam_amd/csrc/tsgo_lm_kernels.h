@@ -22,7 +22,7 @@ __global__ __launch_bounds__(kBlock) void k_chi2_lm_prior(Table<T> tb, const T* 
         for (uint32_t k = pa.off[l]; k < pa.off[l + 1]; ++k) {
             const T* q = pa.rec + (size_t)k * PRI_LM_REC;
             const auto m = ld2<T>(q + PRL_MX), w = ld2<T>(q + PRL_W0);
-            chi += lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly, robust_class<RK>(ra, kClassLmPrior)).rho;
+            chi += lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly, robust_at<RK>(ra, robust_class<RK>(ra, kClassLmPrior), ra.lm_prior, k)).rho;
         }
     }
     const T total = block_sum<T>(chi, red);
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(kBlock) void k_chi2_lm_prior(Table<T> tb, const T* 
 // slot (listed at both endpoints) counted at the edge's first, a vertex's priors folded by its head lane after its rows, the landmark
 // priors' partials added by workgroup 0.  OJ = 1: virtual landmark slots (kVlmMask); the ODOM residual is the same under either Jacobians.
 // RK (RobustArgs, tsgo_kernels.h): the same class -> kernel selection as k_lin_lm / k_lin_pose, through the same edge functions, so the rule
-// above holds under every robust kernel the handle is given.
+// above holds under every robust kernel the handle is given; RK = 2 reads the same per-slot and per-record bytes as k_lin_pose (robust_at).
 template <typename T, int G, int OJ = 0, int PRI = 0, int RK = 0>
 __global__ __launch_bounds__(kBlock) void k_chi2(Table<T> tb, Table<T> od, const T* __restrict__ ps, const T* __restrict__ lmrec,
                                                  T* __restrict__ chi_part, const PriorArgs<T> pa, const RobustArgs<T> ra) {
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void k_chi2(Table<T> tb, Table<T> od, const
             const uint32_t l = tb.idx[k];
             const LmMeas<T> z = lm_meas<T>(tb, k);
             const auto l01 = ld2<T>(lmrec + (size_t)l * kLmRec);
-            chi += lm_linearize<T>(x0, y0, c, s, l01.x, l01.y, z.zx, z.zy, z.w0, z.w1, rk_lm).rho;
+            chi += lm_linearize<T>(x0, y0, c, s, l01.x, l01.y, z.zx, z.zy, z.w0, z.w1, robust_at<RK>(ra, rk_lm, ra.by_pose, k)).rho;
         }
         for (uint32_t row = od.row_off[slice], r1 = od.row_off[slice + 1]; row < r1; ++row) {
             const size_t k = (size_t)row * 64 + lane;
@@ -66,15 +66,15 @@ __global__ __launch_bounds__(kBlock) void k_chi2(Table<T> tb, Table<T> od, const
             const uint32_t j = raw & kPoseIdxMask;
             const OdomMeas<T> z = odom_meas<T>(od, k);
             const auto j01 = ld2<T>(ps + (size_t)j * 4), j23 = ld2<T>(ps + (size_t)j * 4 + 2);
-            if (OJ && (raw & kVlmMask)) chi += vlm_linearize<T>(x0, y0, c, s, j01.x, j01.y, j23.x, j23.y, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1], robust_class<RK>(ra, kClassVlm)).rho;
-            else chi += odom_linearize<T>(x0, y0, c, s, j01.x, j01.y, j23.x, j23.y, z.mi, z.w, rk_odom).rho;      // a padding slot has w = 0: rho = 0
+            if (OJ && (raw & kVlmMask)) chi += vlm_linearize<T>(x0, y0, c, s, j01.x, j01.y, j23.x, j23.y, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1], robust_at<RK>(ra, robust_class<RK>(ra, kClassVlm), ra.odom, k)).rho;
+            else chi += odom_linearize<T>(x0, y0, c, s, j01.x, j01.y, j23.x, j23.y, z.mi, z.w, robust_at<RK>(ra, rk_odom, ra.odom, k)).rho;      // a padding slot has w = 0: rho = 0
         }
         if constexpr (PRI != 0) {
             if (valid && wk.head)
                 for (uint32_t k = pa.off[i]; k < pa.off[i + 1]; ++k) {
                     const T* q = pa.rec + (size_t)k * PRI_POSE_REC;
                     const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C), w01 = ld2<T>(q + PRI_W0);
-                    chi += pose_prior_linearize<T>(m01.x, m01.y, cs.x, cs.y, w01.x, w01.y, q[PRI_W2], x0, y0, c, s, robust_class<RK>(ra, kClassPosePrior)).rho;
+                    chi += pose_prior_linearize<T>(m01.x, m01.y, cs.x, cs.y, w01.x, w01.y, q[PRI_W2], x0, y0, c, s, robust_at<RK>(ra, robust_class<RK>(ra, kClassPosePrior), ra.pose_prior, k)).rho;
                 }
         }
     }

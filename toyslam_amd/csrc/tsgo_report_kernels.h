@@ -3,7 +3,8 @@
 // One pass over the graph at the current estimates that keeps what every linearisation computes per edge and folds away: the residual e,
 // s = e^T Omega e with the RAW information, rho(s) and the robust scale w = rho'(s) of the edge's class.  Which lane meets which edge is
 // tsgo_edge_walk.h's (every input edge once, by one lane); what happens there is ReportVisitor's: the slot's measurement and weights
-// through lm_meas / odom_meas, the prior record's own, the edge functions of the linearisation with the same robust_class<RK> selection,
+// through lm_meas / odom_meas, the prior record's own, the edge functions of the linearisation with the same robust_class<RK> selection
+// (RK = 2, tsgo_set_edge_robust: the byte of the visited edge, robust_at on ra.edge; the class summaries stay indexed by the edge's type),
 // and edge_record (tsgo_math.h) for the record.  The residual arithmetic is not restated.
 //
 // Output.  The lane that visits edge e writes its six numbers to rec[6 * e] (three pair stores: 48 B in f64, 16-byte aligned): one
@@ -66,23 +67,25 @@ template <typename T, int RK> struct ReportVisitor {
     __device__ __forceinline__ void put(int cls, uint32_t e, const EdgeRecord<T>& r) { acc[cls].add(r, e); if (rec) record_store<T>(rec, e, r); }
     __device__ __forceinline__ void lm(uint32_t e, size_t k, const PoseAt<T>& p, T lx, T ly) {
         const LmMeas<T> z = lm_meas<T>(tb, k);
-        put(kClassLm, e, edge_record<T>(lm_linearize<T>(p.x, p.y, p.c, p.s, lx, ly, z.zx, z.zy, z.w0, z.w1, rk_lm), z.w0, z.w1, rk_lm));
+        const auto rk = robust_at<RK>(ra, rk_lm, ra.edge, e);
+        put(kClassLm, e, edge_record<T>(lm_linearize<T>(p.x, p.y, p.c, p.s, lx, ly, z.zx, z.zy, z.w0, z.w1, rk), z.w0, z.w1, rk));
     }
     __device__ __forceinline__ void odom(uint32_t e, size_t k, const PoseAt<T>& p, const T* qj) {
         const OdomMeas<T> z = odom_meas<T>(od, k);
         const PoseAt<T> pj = pose_at<T>(qj);
-        put(kClassOdom, e, edge_record<T>(odom_linearize<T>(p.x, p.y, p.c, p.s, pj.x, pj.y, pj.c, pj.s, z.mi, z.w, rk_odom), z.w, rk_odom));
+        const auto rk = robust_at<RK>(ra, rk_odom, ra.edge, e);
+        put(kClassOdom, e, edge_record<T>(odom_linearize<T>(p.x, p.y, p.c, p.s, pj.x, pj.y, pj.c, pj.s, z.mi, z.w, rk), z.w, rk));
     }
     __device__ __forceinline__ void vlm(uint32_t e, size_t k, const PoseAt<T>& p, const T* qj) {
         const OdomMeas<T> z = odom_meas<T>(od, k);
         const PoseAt<T> pj = pose_at<T>(qj);
-        const auto rk = robust_class<RK>(ra, kClassVlm);
+        const auto rk = robust_at<RK>(ra, robust_class<RK>(ra, kClassVlm), ra.edge, e);
         put(kClassVlm, e, edge_record<T>(vlm_linearize<T>(p.x, p.y, p.c, p.s, pj.x, pj.y, pj.c, pj.s, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1], rk), z.w[0], z.w[1], rk));
     }
     __device__ __forceinline__ void pose_prior(uint32_t e, const T* q, const PoseAt<T>& p) {
         const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C), w01 = ld2<T>(q + PRI_W0);
         const T w2 = q[PRI_W2];
-        const auto rk = robust_class<RK>(ra, kClassPosePrior);
+        const auto rk = robust_at<RK>(ra, robust_class<RK>(ra, kClassPosePrior), ra.edge, e);
         put(kClassPosePrior, e, edge_record<T>(pose_prior_linearize<T>(m01.x, m01.y, cs.x, cs.y, w01.x, w01.y, w2, p.x, p.y, p.c, p.s, rk), w01.x, w01.y, w2, rk));
     }
 };
@@ -94,7 +97,7 @@ template <typename T, int RK> struct ReportLmPriorVisitor {
     ReportAcc<T> acc;
     __device__ __forceinline__ void lm_prior(uint32_t e, const T* q, T lx, T ly) {
         const auto m = ld2<T>(q + PRL_MX), w = ld2<T>(q + PRL_W0);
-        const auto rk = robust_class<RK>(ra, kClassLmPrior);
+        const auto rk = robust_at<RK>(ra, robust_class<RK>(ra, kClassLmPrior), ra.edge, e);
         const EdgeRecord<T> r = edge_record<T>(lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly, rk), w.x, w.y, rk);
         acc.add(r, e);
         if (rec) record_store<T>(rec, e, r);

@@ -14,7 +14,8 @@
 // a = w_robust * inf come from the edge functions every linearisation runs (lm_linearize, odom_linearize + odom_jacobians, vlm_linearize,
 // the prior functions) with the handle's robust setting read at run time (Robust<T>; the default setting is Huber 1.5, the arithmetic of
 // the compile-time kernel bit for bit).  Everything is recomputed from the static planes, so the layout of the dynamic ones (three planes
-// or the general eight) does not enter and neither kernel has an OJ / PRI / RK axis.
+// or the general eight) does not enter and neither kernel has an OJ / PRI axis.  RK = 1 (the default: the class kernels) or 2
+// (tsgo_set_edge_robust: the byte of the slot's input edge, robust_at on ra.edge — the edge index is in a register for the noise anyway).
 //
 // Single writer, no atomics: a vertex's sums stay in its G lanes (group_sum, a fixed xor order), its head lane adds the priors and the
 // gauge term in input order and writes the vertex's entries of every column.  Columns are walked CH at a time with the accumulators in
@@ -30,7 +31,7 @@ struct SampleBatch { SampleSeed seed; int k0, nc, NV; };
 
 constexpr uint32_t kNoiseEdge = 0u, kNoiseGauge = 1u;      // noise() tags
 
-template <typename T, int G, int CH>
+template <typename T, int G, int CH, int RK = 1>
 __global__ __launch_bounds__(kBlock) void k_smp_rhs_lm(Table<T> tb, const T* __restrict__ ps, const T* __restrict__ lmrec, const uint32_t* __restrict__ lm_edge,
                                                        const uint32_t* __restrict__ pl_edge, const int* __restrict__ lm_vertex, const T* __restrict__ gauge_l,
                                                        const PriorArgs<T> pa, const RobustArgs<T> ra, const SampleBatch sb, T* __restrict__ u) {
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(kBlock) void k_smp_rhs_lm(Table<T> tb, const T* __r
                 const LmMeas<T> z = lm_meas<T>(tb, k);
                 const auto q01 = ld2<T>(ps + (size_t)i * 4), q23 = ld2<T>(ps + (size_t)i * 4 + 2);
                 const T c = q23.x, s = q23.y;
-                const LmLin<T> o = lm_linearize<T>(q01.x, q01.y, c, s, lx, ly, z.zx, z.zy, z.w0, z.w1, rk_lm);
+                const LmLin<T> o = lm_linearize<T>(q01.x, q01.y, c, s, lx, ly, z.zx, z.zy, z.w0, z.w1, robust_at<RK>(ra, rk_lm, ra.edge, e));
                 const T sa0 = sqrt(o.a0), sa1 = sqrt(o.a1);
 #pragma unroll
                 for (int j = 0; j < CH; ++j) {
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(kBlock) void k_smp_rhs_lm(Table<T> tb, const T* __r
                         for (uint32_t k = pa.off[l]; k < pa.off[l + 1]; ++k) {      // landmark priors: A = I
                             const T* q = pa.rec + (size_t)k * PRI_LM_REC;
                             const auto m = ld2<T>(q + PRL_MX), w = ld2<T>(q + PRL_W0);
-                            const LmPriorLin<T> o = lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly, rk_lp);
+                            const LmPriorLin<T> o = lm_prior_linearize<T>(m.x, m.y, w.x, w.y, lx, ly, robust_at<RK>(ra, rk_lp, ra.edge, pl_edge[k]));
                             double n0, n1;
                             sample_noise2(sb.seed, kNoiseEdge, pl_edge[k], ks, n0, n1);
                             b0 += sqrt(o.a0) * (T)n0; b1 += sqrt(o.a1) * (T)n1;
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(kBlock) void k_smp_rhs_lm(Table<T> tb, const T* __r
     }
 }
 
-template <typename T, int G, int CH>
+template <typename T, int G, int CH, int RK = 1>
 __global__ __launch_bounds__(kBlock) void k_smp_rhs_pose(Table<T> tb, Table<T> od, const T* __restrict__ ps, const T* __restrict__ lmrec,
                                                          const uint32_t* __restrict__ lm_edge, const uint32_t* __restrict__ od_edge,
                                                          const uint32_t* __restrict__ pp_edge, const int* __restrict__ pose_vertex,
@@ -131,7 +132,7 @@ __global__ __launch_bounds__(kBlock) void k_smp_rhs_pose(Table<T> tb, Table<T> o
                 const uint32_t l = tb.idx[k];
                 const LmMeas<T> z = lm_meas<T>(tb, k);
                 const auto l01 = ld2<T>(lmrec + (size_t)l * kLmRec);
-                const LmLin<T> o = lm_linearize<T>(x0, y0, c, s, l01.x, l01.y, z.zx, z.zy, z.w0, z.w1, rk_lm);
+                const LmLin<T> o = lm_linearize<T>(x0, y0, c, s, l01.x, l01.y, z.zx, z.zy, z.w0, z.w1, robust_at<RK>(ra, rk_lm, ra.edge, e));
                 const T sa0 = sqrt(o.a0), sa1 = sqrt(o.a1);
                 const T* ul = u + ((size_t)l * sb.NV + c0) * 2;
 #pragma unroll
@@ -157,7 +158,7 @@ __global__ __launch_bounds__(kBlock) void k_smp_rhs_pose(Table<T> tb, Table<T> o
                 const auto j01 = ld2<T>(ps + (size_t)jn * 4), j23 = ld2<T>(ps + (size_t)jn * 4 + 2);
                 const T xj = j01.x, yj = j01.y, cj = j23.x, sj = j23.y;
                 if (raw & kVlmMask) {      // e = T1 p1 - T2 p2: [I | u] at the first endpoint, -[I | u] at the second, u of the slot's own pose
-                    const VlmLin<T> v = vlm_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1], rk_vlm);
+                    const VlmLin<T> v = vlm_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi[0], z.mi[1], z.mi[2], z.mi[3], z.w[0], z.w[1], robust_at<RK>(ra, rk_vlm, ra.edge, e));
                     const T sg = second ? T(-1) : T(1), s0 = sg * sqrt(v.om0), s1 = sg * sqrt(v.om1);
 #pragma unroll
                     for (int j = 0; j < CH; ++j) {
@@ -170,8 +171,9 @@ __global__ __launch_bounds__(kBlock) void k_smp_rhs_pose(Table<T> tb, Table<T> o
                     }
                     continue;
                 }
-                const OdomLin<T> o = second ? odom_linearize<T>(xj, yj, cj, sj, x0, y0, c, s, z.mi, z.w, rk_odom)
-                                            : odom_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi, z.w, rk_odom);
+                const Robust<T> rk_slot = robust_at<RK>(ra, rk_odom, ra.edge, e);
+                const OdomLin<T> o = second ? odom_linearize<T>(xj, yj, cj, sj, x0, y0, c, s, z.mi, z.w, rk_slot)
+                                            : odom_linearize<T>(x0, y0, c, s, xj, yj, cj, sj, z.mi, z.w, rk_slot);
                 const T sa0 = sqrt(o.a[0]), sa1 = sqrt(o.a[1]), sa2 = sqrt(o.a[2]);
                 // A = [[-M, q], [0 0 -kappa]], B = [[M, 0], [0 0 kappa]] (odom_jacobians); the reference's constants are M = I, q = 0, kappa = 1
                 OdomJac<T> jac{T(1), T(0), T(0), T(1), T(0), T(0), T(1)};
@@ -203,7 +205,7 @@ __global__ __launch_bounds__(kBlock) void k_smp_rhs_pose(Table<T> tb, Table<T> o
                         for (uint32_t k = pa.off[i]; k < pa.off[i + 1]; ++k) {      // pose priors: A = blockdiag(R_m^T, 1)
                             const T* q = pa.rec + (size_t)k * PRI_POSE_REC;
                             const auto m01 = ld2<T>(q), cs = ld2<T>(q + PRI_C), w01 = ld2<T>(q + PRI_W0);
-                            const PosePriorLin<T> o = pose_prior_linearize<T>(m01.x, m01.y, cs.x, cs.y, w01.x, w01.y, q[PRI_W2], x0, y0, c, s, rk_pp);
+                            const PosePriorLin<T> o = pose_prior_linearize<T>(m01.x, m01.y, cs.x, cs.y, w01.x, w01.y, q[PRI_W2], x0, y0, c, s, robust_at<RK>(ra, rk_pp, ra.edge, pp_edge[k]));
                             double n0, n1, n2;
                             sample_noise3(sb.seed, kNoiseEdge, pp_edge[k], ks, n0, n1, n2);
                             const T h0 = sqrt(o.a0) * (T)n0, h1 = sqrt(o.a1) * (T)n1;

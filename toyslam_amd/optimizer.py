@@ -119,6 +119,53 @@ class HipOptimizer:
         names = {v: k for k, v in _lib.ROBUST_KERNELS.items()}
         return {c: "none" if r.kernel[k] == 0 else (names[r.kernel[k]], r.delta[k]) for k, c in enumerate(_lib.ROBUST_CLASSES)}
 
+    def set_edge_robust(self, kernels, entry_of_edge):
+        """Robust kernels per EDGE (tsgo_set_edge_robust): `kernels` a palette of at most 15 entries, each "none" or (name, delta) as in
+        set_robust; entry_of_edge one integer per edge of the graph given to set_graph, in its order: 0 leaves the edge to its class's
+        kernel (set_robust), k >= 1 gives it kernels[k - 1] whatever its class.  An all-zero entry_of_edge is the same as
+        clear_edge_robust().  Survives set_robust, set_edge_information, init_estimates, gnc and optimize; the next set_graph drops it.
+        Returns the call's stats: edges_by_entry, overridden_by_class ({class: count}), active, ms_total."""
+        kernels = list(kernels)
+        ent = (_lib.tsgo_edge_robust_entry * max(1, len(kernels)))()
+        for k, v in enumerate(kernels):
+            name, delta = (v, 0.0) if isinstance(v, str) else v
+            if name not in _lib.ROBUST_KERNELS or (isinstance(v, str) and name != "none"):
+                raise ValueError('a robust kernel is "none" or (name, delta) with name in %s' % sorted(_lib.ROBUST_KERNELS))
+            ent[k].kernel, ent[k].delta = _lib.ROBUST_KERNELS[name], float(delta)
+        of = np.asarray(entry_of_edge)
+        if of.size and (of.min() < 0 or of.max() > 255):
+            raise ValueError("entry_of_edge values must be within [0, 255]")
+        of = np.ascontiguousarray(of.reshape(-1), dtype=np.uint8)
+        return self._set_edge_robust(len(kernels), ent if kernels else None, of.ctypes.data if len(of) else None, len(of))
+
+    def _set_edge_robust(self, n_entries, entries, mask, n_mask):
+        st = _lib.tsgo_edge_robust_stats()
+        _lib.check(self.lib, self.lib.tsgo_set_edge_robust(self.h, n_entries, entries, mask, n_mask, C.byref(st)), "tsgo_set_edge_robust")
+        return dict(edges_by_entry=np.array(st.edges_by_entry[:], dtype=np.int64),
+                    overridden_by_class={c: st.overridden_by_class[k] for k, c in enumerate(_lib.ROBUST_CLASSES)}, active=bool(st.active), ms_total=st.ms_total)
+
+    def exempt_edges(self, edges):
+        """The listed edges (indices into the edge arrays, or a boolean mask over them) take no robust kernel at all — rho = s and w = 1
+        exactly, e.g. the odometry chain — and every other edge keeps its class's: set_edge_robust with one "none" entry."""
+        of = np.zeros(self.n_edges, dtype=np.uint8)
+        of[np.asarray(edges)] = 1
+        return self.set_edge_robust(["none"], of)
+
+    def clear_edge_robust(self):
+        """Back to the class kernels alone: the handle then runs exactly what it ran before set_edge_robust."""
+        return self._set_edge_robust(0, None, None, 0)
+
+    @property
+    def edge_robust(self):
+        """The per-edge setting read back (tsgo_get_edge_robust): (kernels, entry_of_edge) as set_edge_robust takes them; ([], zeros) when
+        none is active."""
+        n = C.c_int32()
+        ent = (_lib.tsgo_edge_robust_entry * _lib.TSGO_EDGE_ROBUST_MAX)()
+        of = np.zeros(self.n_edges, dtype=np.uint8)
+        _lib.check(self.lib, self.lib.tsgo_get_edge_robust(self.h, C.byref(n), ent, of.ctypes.data if self.n_edges else None, self.n_edges), "tsgo_get_edge_robust")
+        names = {v: k for k, v in _lib.ROBUST_KERNELS.items()}
+        return ["none" if ent[k].kernel == 0 else (names[ent[k].kernel], ent[k].delta) for k in range(n.value)], of
+
     def set_dogleg(self, radius0=None, radius_min=None, radius_max=None, chi2_rel_tol=None):
         """Parameters of the dogleg loop (tsgo_set_dogleg; read by rules="dogleg" only): an argument left out keeps what the handle has.
         They belong to the handle and survive set_graph; every optimize call starts at radius0."""
