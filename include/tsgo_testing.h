@@ -91,6 +91,14 @@ int tsgo_testing_schur_pattern(int32_t builder, int32_t P, int32_t L, const int3
                                const int32_t* obs_pose, const uint32_t* obs_slot, const int32_t* od_ptr, const int32_t* od_col, const uint32_t* od_slot,
                                int32_t max_pair_degree, tsgo_testing_schur_out* out);
 
+/* The lane sums of the kernels (toyslam_amd/csrc/tsgo_kernels.h: lane_xor, group_sum, wave_sum, block_sum2) on caller-given values, in ONE
+ * workgroup of 256 threads: tests/test_gpu_lane_sums.py.  No handle, no graph.  in32 / in64: 256 values, thread t holds in[t].
+ * out32 / out64: 10 rows of 256, row-major, entry t of a row = what thread t got:
+ *   rows 0 .. 6   group_sum<T, G>(in[t]) for G = 1, 2, 4, 8, 16, 32, 64 (masks ascending)
+ *   row 7         wave_sum<T>(in[t]) (masks descending)
+ *   rows 8, 9     block_sum2 of a = in[t] and b = in[255 - t]: the workgroup's sums of a and of b. */
+int tsgo_testing_lane_sums(const float* in32, const double* in64, float* out32, double* out64);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,7 +159,7 @@ DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_
                   "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc", "tsgo_sample_marginals", "tsgo_set_dogleg", "tsgo_get_dogleg", "tsgo_get_dogleg_trace",
                   "tsgo_set_edge_robust", "tsgo_get_edge_robust"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply",
-                   "tsgo_testing_sym_scan", "tsgo_testing_sym_product", "tsgo_testing_schur_pattern"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
+                   "tsgo_testing_sym_scan", "tsgo_testing_sym_product", "tsgo_testing_schur_pattern", "tsgo_testing_lane_sums"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
 
 def _declare_host(L):
@@ -234,6 +234,7 @@ def _declare_testing(L):
     L.tsgo_testing_sym_scan.argtypes = [C.c_int32, vp, vp]
     L.tsgo_testing_sym_product.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.POINTER(tsgo_testing_sym_out)]
     L.tsgo_testing_schur_pattern.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [vp] * 9 + [C.c_int32, C.POINTER(tsgo_testing_schur_out)]
+    L.tsgo_testing_lane_sums.argtypes = [vp, vp, vp, vp]
 
 
 _host = None

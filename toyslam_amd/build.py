@@ -63,9 +63,11 @@ def build_hip_testing(force=False):
 
 
 def build_hip_plain(force=False):
-    """The product library's sources WITHOUT kernarg preload: the B side of A/B measurements and of the bitwise comparison
-    (tests/test_gpu_kernarg_preload.py, tests/test_kernarg_heads.py).  Not a product binary: build_all does not build it."""
-    return _hip_library(HIP_PLAIN_SO, [], force)
+    """The product library's sources WITHOUT either latency measure — no kernarg preload, and TSGO_SHUFFLE_SUMS: lane sums through
+    __shfl_xor, k_cg_step's and the gates' sums one after the other (csrc/tsgo_kernels.h: lane_xor) — the B side of the bitwise
+    comparisons (tests/test_gpu_kernarg_preload.py, tests/test_gpu_lane_sums.py, tests/test_kernarg_heads.py).  Not a product binary:
+    build_all does not build it."""
+    return _hip_library(HIP_PLAIN_SO, ["-DTSGO_SHUFFLE_SUMS"], force)
 
 
 def build_server(force=False):

@@ -442,8 +442,9 @@
             hipLaunchKernelGGL((k_fold_partials<T>), dim3(kFoldOut, 2), dim3(kBlock), 0, stream, nbP, dots, rzs, fold_part);
             dots = fold_part; rzs = fold_part + kFoldOut; n_part = kFoldOut;
         }
-        PF(pr.P * (3 + 3 + 6 + 4 * 3 * 2) * (double)sizeof(T), "vector step + pre-smoothing L0", "k_cg_step", tname());
-        hipLaunchKernelGGL((k_cg_step<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, (const T*)sbuf, dots, rzs, n_part,
+        const bool ask_first = nbC <= kAskFirstAbove;      // one round of workgroups: every operand asked for before the first wait (tsgo_amg_kernels.h)
+        PF(pr.P * (3 + 3 + 6 + 4 * 3 * 2) * (double)sizeof(T), "vector step + pre-smoothing L0", ask_first ? "k_cg_step" : "k_cg_step_rounds", tname());
+        hipLaunchKernelGGL((ask_first ? k_cg_step<T> : k_cg_step_rounds<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, (const T*)sbuf, dots, rzs, n_part,
                            (const CgState<T>*)st[slot], st[slot ^ 1], r, p, q, x, zc, (const T*)minv, (const T*)omega_dev, tol2, cfg.pcg_max_iters, (const T*)gscale_dev, kAmgStallIter, (T)kAmgStallRatio,
                            npart, low_cycle && !explicit0 ? zc32 : (float*)nullptr);
     }

@@ -752,20 +752,77 @@ __global__ __launch_bounds__(kBlock) void k_fold_partials(int n, const T* __rest
     if (threadIdx.x == 0) out[blockIdx.y * kFoldOut + blockIdx.x] = total;
 }
 
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_cg_step(int P, const T* __restrict__ sz, const T* __restrict__ dot_part,
-                                                    const T* __restrict__ rz_part, int n_part, const CgState<T>* __restrict__ st_in,
-                                                    CgState<T>* __restrict__ st_out, T* __restrict__ r, T* __restrict__ p,
-                                                    T* __restrict__ q, T* __restrict__ x, T* __restrict__ zc,
-                                                    const T* __restrict__ minv, const T* __restrict__ omega_ptr, T tol2, int max_iters,
-                                                    const T* __restrict__ gamma0_scale, int stall_iter, T stall_ratio,
-                                                    T* __restrict__ rdr_part, float* __restrict__ zc32) {
-    __shared__ T red[kWavesPerBlock];
-    const CgState<T> s = *st_in;
+// ASK = 1 (k_cg_step: grids of at most kAskFirstAbove workgroups; Engine::launch_cg_step): every operand is requested before the first
+// wait, below.  A larger grid runs in several rounds of workgroups, whose prologues hide behind each other's vector traffic, and the 28
+// registers the requests hold cost it occupancy (8 -> 6 waves per SIMD): at a million poses the kernel took 62.6 instead of 59.6 us
+// that way (profiles/lane_sums_ab.txt), so there it keeps the order state, test, sums, vectors (ASK = 0: k_cg_step_rounds).  Same
+// arithmetic, same bits, same arguments.
+constexpr int kAskFirstAbove = kFoldAbove;
+template <typename T, int ASK>
+__device__ __forceinline__ void cg_step_body(int P, const T* __restrict__ sz, const T* __restrict__ dot_part,
+                                             const T* __restrict__ rz_part, int n_part, const CgState<T>* __restrict__ st_in,
+                                             CgState<T>* __restrict__ st_out, T* __restrict__ r, T* __restrict__ p,
+                                             T* __restrict__ q, T* __restrict__ x, T* __restrict__ zc,
+                                             const T* __restrict__ minv, const T* __restrict__ omega_ptr, T tol2, int max_iters,
+                                             const T* __restrict__ gamma0_scale, int stall_iter, T stall_ratio,
+                                             T* __restrict__ rdr_part, float* __restrict__ zc32) {
+    __shared__ T red[2 * kWavesPerBlock];
     const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
-    if (s.done) { if (writer) *st_out = s; return; }
-    const T delta = block_sum_array<T>(dot_part, n_part, red);
-    const T gamma = block_sum_array<T>(rz_part, n_part, red);
+    const int i0 = blockIdx.x * kBlock;
+    const int n_here = min(kBlock, P - i0);
+    const size_t e0 = (size_t)i0 * 3;
+    // This thread's operands: lane = element, three elements of the vectors and six of the diagonal inverses (the loads of a wavefront
+    // are contiguous; the residual and the inverses reach the per-pose part through LDS below).  A thread past the workgroup's last
+    // element asks for that last element instead (in bounds, never used): no branch around any request.
+    T vz[3], vp[3], vs[3], vq[3], vx[3], vr[3], vm[6];
+    auto request = [&]() {
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            const int le = max(min((int)threadIdx.x + m * kBlock, 3 * n_here - 1), 0);
+            const size_t j = e0 + le;
+            const int ip = le / 3, k = le - 3 * ip;
+            vz[m] = zc[(size_t)(i0 + ip) * kPoseRec + k]; vp[m] = p[j]; vs[m] = sz[j]; vq[m] = q[j]; vx[m] = x[j]; vr[m] = r[j];
+        }
+        const T* mi = minv + (size_t)i0 * 6;
+#pragma unroll
+        for (int m = 0; m < 6; ++m) vm[m] = mi[max(min((int)threadIdx.x + m * kBlock, 6 * n_here - 1), 0)];
+    };
+#ifdef TSGO_SHUFFLE_SUMS
+    constexpr bool ask_first = false;
+#else
+    constexpr bool ask_first = ASK != 0;
+#endif
+    const CgState<T> s = *st_in;
+    T delta = 0, gamma = 0;
+    if constexpr (!ask_first) {
+        if (s.done) { if (writer) *st_out = s; return; }
+        delta = block_sum_array<T>(dot_part, n_part, red);
+        gamma = block_sum_array<T>(rz_part, n_part, red);
+    } else {
+        // Everything the kernel reads depends on its arguments alone, so all of it is ASKED FOR before anything is waited for: the state,
+        // this thread's share of both partial arrays, its vector operands.  (The order state -> test -> partials of delta -> sum -> partials
+        // of gamma -> sum -> alpha, beta -> vectors was four dependent round trips and two barrier pairs in front of the first vector load,
+        // paid in full once per iteration: the grid is one wave of workgroups.)  The early exits below stay where they were; the loads in
+        // flight are dropped.  issue_before_exit keeps the compiler from sinking the requests below the exits.
+        // the first two partials of a thread (all there are up to 512 workgroups: 131 000 poses; k_fold_partials leaves 64) are requested
+        // without a wait between them, clamped like the vectors; a thread's sum keeps block_sum_array's order: 0 + a[t] + a[t + kBlock] + ...
+        const int k0 = (int)threadIdx.x, k1 = k0 + kBlock, kl = max(n_part - 1, 0);
+        const T da = dot_part[min(k0, kl)], ga = rz_part[min(k0, kl)], db = dot_part[min(k1, kl)], gb = rz_part[min(k1, kl)];
+        // (the partials' pointers are in the preloaded argument head, the vectors' are not: without the fence the scheduler puts the wait
+        // for the kernarg fetch in front of ALL the requests — tests/test_kernarg_heads.py)
+        __builtin_amdgcn_sched_barrier(0);
+        request();
+        if (k0 < n_part) { delta += da; gamma += ga; }
+        if (k1 < n_part) { delta += db; gamma += gb; }
+        for (int k = k1 + kBlock; k < n_part; k += kBlock) { delta += dot_part[k]; gamma += rz_part[k]; }
+        issue_before_exit(delta); issue_before_exit(gamma);
+#pragma unroll
+        for (int m = 0; m < 3; ++m) { issue_before_exit(vz[m]); issue_before_exit(vp[m]); issue_before_exit(vs[m]); issue_before_exit(vq[m]); issue_before_exit(vx[m]); issue_before_exit(vr[m]); }
+#pragma unroll
+        for (int m = 0; m < 6; ++m) issue_before_exit(vm[m]);
+        if (s.done) { if (writer) *st_out = s; return; }
+        block_sum2<T>(delta, gamma, red);      // per value: block_sum_array's order (threads striding by kBlock, lanes, then waves 0 .. 3)
+    }
     const T gamma0 = s.iters == 0 ? gamma * (*gamma0_scale) : s.gamma0;
     CgState<T> n = s; n.gamma0 = gamma0;
     // gamma = r^T M^-1 r < 0 (or NaN) means the preconditioner is not positive definite: breakdown, NOT convergence (the host then
@@ -785,28 +842,24 @@ __global__ __launch_bounds__(kBlock) void k_cg_step(int P, const T* __restrict__
     // made them 24-byte-strided triples), the residual and the diagonal inverses handed to the per-pose part through LDS.
     __shared__ T s_r[3 * kBlock];
     __shared__ T s_m[6 * kBlock];
-    const int i0 = blockIdx.x * kBlock;
-    const int n_here = min(kBlock, P - i0);
+    if constexpr (!ask_first) request();
     {
-        const size_t e0 = (size_t)i0 * 3;
 #pragma unroll
         for (int m = 0; m < 3; ++m) {
             const int le = (int)threadIdx.x + m * kBlock;
             if (le < 3 * n_here) {
                 const size_t j = e0 + le;
-                const int ip = le / 3, k = le - 3 * ip;
-                const T pk = zc[(size_t)(i0 + ip) * kPoseRec + k] + beta * p[j];
-                const T qk = sz[j] + beta * q[j];
-                p[j] = pk; q[j] = qk; x[j] += alpha * pk;
-                const T rk = r[j] - alpha * qk;
+                const T pk = vz[m] + beta * vp[m];
+                const T qk = vs[m] + beta * vq[m];
+                p[j] = pk; q[j] = qk; x[j] = vx[m] + alpha * pk;
+                const T rk = vr[m] - alpha * qk;
                 r[j] = rk; s_r[le] = rk;
             }
         }
-        const T* mi = minv + (size_t)i0 * 6;
 #pragma unroll
         for (int m = 0; m < 6; ++m) {
             const int le = (int)threadIdx.x + m * kBlock;
-            if (le < 6 * n_here) s_m[le] = mi[le];
+            if (le < 6 * n_here) s_m[le] = vm[m];
         }
     }
     __syncthreads();
@@ -828,6 +881,16 @@ __global__ __launch_bounds__(kBlock) void k_cg_step(int P, const T* __restrict__
     if (writer) { n.gamma_old = gamma; n.alpha_old = alpha; n.iters = s.iters + 1; *st_out = n; }
 }
 
+#define TSGO_CG_STEP_PARAMS int P, const T* __restrict__ sz, const T* __restrict__ dot_part, const T* __restrict__ rz_part, int n_part,                          \
+                            const CgState<T>* __restrict__ st_in, CgState<T>* __restrict__ st_out, T* __restrict__ r, T* __restrict__ p, T* __restrict__ q,        \
+                            T* __restrict__ x, T* __restrict__ zc, const T* __restrict__ minv, const T* __restrict__ omega_ptr, T tol2, int max_iters,           \
+                            const T* __restrict__ gamma0_scale, int stall_iter, T stall_ratio, T* __restrict__ rdr_part, float* __restrict__ zc32
+#define TSGO_CG_STEP_ARGS P, sz, dot_part, rz_part, n_part, st_in, st_out, r, p, q, x, zc, minv, omega_ptr, tol2, max_iters, gamma0_scale, stall_iter, stall_ratio, rdr_part, zc32
+template <typename T> __global__ __launch_bounds__(kBlock) void k_cg_step(TSGO_CG_STEP_PARAMS) { cg_step_body<T, 1>(TSGO_CG_STEP_ARGS); }
+template <typename T> __global__ __launch_bounds__(kBlock) void k_cg_step_rounds(TSGO_CG_STEP_PARAMS) { cg_step_body<T, 0>(TSGO_CG_STEP_ARGS); }
+#undef TSGO_CG_STEP_PARAMS
+#undef TSGO_CG_STEP_ARGS
+
 // First kernel of every multigrid-preconditioned PCG iteration, one workgroup: has the residual the last k_cg_step produced met the
 // stopping rule?  (Round 4: on the default path the test rides in workgroup 0 of the iteration's first product kernel instead —
 // iter_gate_body in tsgo_kernels.h, k_schur_lm's `gate` argument — and this kernel runs only where that product is not the first launch.)  Then this and every later kernel of the solve exits at once (they all read st->done).
@@ -837,7 +900,7 @@ __global__ __launch_bounds__(kBlock) void k_cg_step(int P, const T* __restrict__
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_iter_gate(CgState<T>* __restrict__ st, const T* __restrict__ rdr_part, const T* __restrict__ bpart, int n, T tol2,
                                                       int* __restrict__ host_flag, int seq) {
-    __shared__ T red[kWavesPerBlock];
+    __shared__ T red[2 * kWavesPerBlock];
     iter_gate_body<T>(GateArgs<T>{st, rdr_part, bpart, n, tol2, host_flag, seq}, red);
 }
 

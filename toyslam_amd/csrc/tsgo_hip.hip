@@ -32,6 +32,7 @@
 //                                  (a third visitor of tsgo_edge_walk.h), the step from the snapshot
 //   engine/engine_testing.inc      tsgo_testing_apply (TSGO_TESTING builds only): the operators PCG applies, read out column by column
 //   engine/sym_testing.inc         (file scope, TSGO_TESTING builds only) the pattern builders of tsgo_sym_kernels.h on caller-given arrays
+//   engine/lane_testing.inc        (file scope, TSGO_TESTING builds only) the lane sums of tsgo_kernels.h on caller-given values
 //
 // There is NO CPU fallback in this file: every entry point that computes needs a gfx950 device and
 // returns an error otherwise.
@@ -589,6 +590,7 @@ template <typename T> struct Engine : IEngine {
 
 #ifdef TSGO_TESTING
 #include "engine/sym_testing.inc"
+#include "engine/lane_testing.inc"
 #endif
 
 struct tsgo_optimizer {
@@ -688,6 +690,11 @@ int tsgo_testing_apply(tsgo_optimizer* o, int32_t which, const double* in, doubl
     return o->eng->testing_apply(which, in, out, n_cols);
 }
 int tsgo_testing_sym_scan(int32_t n, const int32_t* in, int32_t* out) { return sym_scan_run(n, in, out); }
+int tsgo_testing_lane_sums(const float* in32, const double* in64, float* out32, double* out64) {
+    if (!in32 || !in64 || !out32 || !out64) return tsgo::set_error(-1, "tsgo_testing_lane_sums: null argument");
+    if (int rc = lane_sums_run<float>(in32, out32)) return rc;
+    return lane_sums_run<double>(in64, out64);
+}
 int tsgo_testing_sym_product(int32_t builder, int32_t upper, int32_t n, const int32_t* xptr, const int32_t* xcol, const int32_t* x_alias, int32_t ny, int32_t nc,
                              const int32_t* yptr, const int32_t* ycol, tsgo_testing_sym_out* out) {
     return sym_product_run(builder, upper, n, xptr, xcol, x_alias, ny, nc, yptr, ycol, out);

@@ -145,16 +145,70 @@ template <typename T, int LOW> __device__ __forceinline__ PoseVec<T> pose_vec(co
     return {z01.x, z01.y, z23.x, z23.y, zr[4]};
 }
 
-template <typename T, int G> __device__ __forceinline__ T group_sum(T v) {
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m);
+// lane_xor<M>(v): the value lane (i ^ M) holds, M one of 1, 2, 4, 8, 16, 32 — the exchange every lane sum below is made of.  __shfl_xor
+// is a ds_bpermute_b32 per dword: a trip through the LDS crossbar (its latency that of an LDS read) in each of the up to six DEPENDENT
+// rounds of a sum, at the tail of every kernel's longest wave.  The same exchange without leaving the VALU:
+//   M = 1, 2   DPP quad_perm [1,0,3,2] / [2,3,0,1]                 (the compiler folds the move into the add that follows)
+//   M = 4      two DPP moves inside the row of 16: lanes of banks 0 and 2 read four lanes up (row_shl:4, bank mask 0x5), banks 1 and 3
+//              four lanes down (row_shr:4, bank mask 0xa)
+//   M = 8      DPP row_ror:8
+//   M = 16, 32 v_permlane16_swap / v_permlane32_swap of the value with itself: result 0 holds the partner's value in the odd rows
+//              (upper half), result 1 in the even rows (lower half)
+// 8-byte values move as two dwords.  A true xor exchange: every lane adds the same two operands as under __shfl_xor, the sums keep their
+// bits.  What differs between the forms is what a lane reads from a partner the EXEC mask has switched off, so the sums are called where
+// the wave's control flow has converged: every call site (this file, tsgo_amg_kernels.h, tsgo_block_row.h's users, the marginal, sample,
+// init, lm and dogleg kernels) is reached either by whole waves — wk.live, st->done, row bounds and kernel arguments are wave-uniform; the
+// clamp path of block_row keeps every lane of a surplus workgroup walking the last row — or BEHIND the lane-divergent walk (row_dot's
+// strided loop, the tables' padding `continue`, k_pair_gemm_wave's `if (live)` loop), never inside it: none had to be made uniform.
+// Blocks are one-dimensional and a multiple of 64 threads: threadIdx.x & 63 is the lane.  (The struct reductions of the edge-report and GNC
+// kernels and the integer sums of the pattern builders are not these sums and keep __shfl_xor.)
+// TSGO_SHUFFLE_SUMS (build.py: the plain library) keeps the __shfl_xor forms, and the two-sums-one-after-the-other shape of
+// block_sum2 and k_cg_step's prologue: the B side of the bitwise comparison.
+#ifndef TSGO_SHUFFLE_SUMS
+template <int M> __device__ __forceinline__ uint32_t lane_xor_dword(uint32_t u) {
+    static_assert(M == 1 || M == 2 || M == 4 || M == 8 || M == 16 || M == 32, "lane_xor: one bit of the lane number");
+    const int v = (int)u;
+    // __builtin_amdgcn_mov_dpp(src, dpp_ctrl, row_mask, bank_mask, bound_ctrl), __builtin_amdgcn_update_dpp(old, src, ...)
+    // (M = 1, 2, 8 read a lane of the row whatever the lane: no `old` value, bound_ctrl — the form the compiler folds into an f32 add)
+    if constexpr (M == 1) return (uint32_t)__builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, true);                 // quad_perm:[1,0,3,2]
+    else if constexpr (M == 2) return (uint32_t)__builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, true);            // quad_perm:[2,3,0,1]
+    else if constexpr (M == 4) {
+        const int up = __builtin_amdgcn_update_dpp(v, v, 0x104, 0xf, 0x5, false);                             // row_shl:4: lane i reads i + 4
+        return (uint32_t)__builtin_amdgcn_update_dpp(up, v, 0x114, 0xf, 0xa, false);                          // row_shr:4: lane i reads i - 4
+    }
+    else if constexpr (M == 8) return (uint32_t)__builtin_amdgcn_mov_dpp(v, 0x128, 0xf, 0xf, true);           // row_ror:8
+    else if constexpr (M == 16) { const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false); return (threadIdx.x & 16u) ? r[0] : r[1]; }
+    else { const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false); return (threadIdx.x & 32u) ? r[0] : r[1]; }
+}
+template <int M, typename T> __device__ __forceinline__ T lane_xor(T v) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "lane_xor: one or two dwords");
+    if constexpr (sizeof(T) == 4) {
+        uint32_t u;
+        __builtin_memcpy(&u, &v, 4);
+        u = lane_xor_dword<M>(u);
+        __builtin_memcpy(&v, &u, 4);
+    } else {
+        uint32_t u[2];
+        __builtin_memcpy(u, &v, 8);
+        u[0] = lane_xor_dword<M>(u[0]); u[1] = lane_xor_dword<M>(u[1]);
+        __builtin_memcpy(&v, u, 8);
+    }
     return v;
 }
+#else
+template <int M, typename T> __device__ __forceinline__ T lane_xor(T v) { return __shfl_xor(v, M); }
+#endif
 
-template <typename T> __device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
+// Sum over the G lanes of a group (masks ascending) and over the wave (masks descending): every lane gets the result.
+template <typename T, int G, int M = 1> __device__ __forceinline__ T group_sum(T v) {
+    if constexpr (M < G) { v += lane_xor<M>(v); return group_sum<T, G, 2 * M>(v); }
+    else return v;
+}
+
+template <typename T, int M = 32> __device__ __forceinline__ T wave_sum(T v) {
+    v += lane_xor<M>(v);
+    if constexpr (M > 1) return wave_sum<T, M / 2>(v);
+    else return v;
 }
 
 // Sum over the workgroup; every thread gets the result.  `red` = kWavesPerBlock T's of LDS.
@@ -170,6 +224,23 @@ template <typename T> __device__ __forceinline__ T block_sum(T v, T* red) {
     return s;
 }
 
+// Two workgroup sums through the same rounds: the lane exchanges of a and b interleave (two independent chains instead of one after the
+// other), ONE barrier pair, two rows of LDS.  Per value the order of the additions is block_sum's.  `red` = 2 * kWavesPerBlock T's.
+template <typename T> __device__ __forceinline__ void block_sum2(T& a, T& b, T* red) {
+#ifdef TSGO_SHUFFLE_SUMS
+    a = block_sum<T>(a, red); b = block_sum<T>(b, red);
+#else
+    a = wave_sum(a); b = wave_sum(b);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { red[w] = a; red[kWavesPerBlock + w] = b; }
+    __syncthreads();
+    a = red[0]; b = red[kWavesPerBlock];
+#pragma unroll
+    for (int k = 1; k < kWavesPerBlock; ++k) { a += red[k]; b += red[kWavesPerBlock + k]; }
+#endif
+}
+
 // Fixed-order sum of n partials by a whole workgroup (n is a few hundred).
 template <typename T> __device__ __forceinline__ T block_sum_array(const T* a, int n, T* red) {
     T v = 0;
@@ -182,15 +253,15 @@ template <typename T> __device__ __forceinline__ T block_sum_array(const T* a, i
 // b^T D^-1 b, sets st->done when the residual meets the tolerance, and — eager launches — tells the host thread in ONE aligned 8-byte
 // store that the seq-th launched iteration has started and what it saw (seq | done | fail | iterations completed; Engine::do_solve_paced).
 template <typename T> struct GateArgs { CgState<T>* st; const T* rdr_part; const T* bpart; int n; T tol2; int* host_flag; int seq; };
-template <typename T> __device__ __forceinline__ int iter_gate_body(const GateArgs<T> g, T* red) {      // thread 0 returns the verdict (done)
+template <typename T> __device__ __forceinline__ int iter_gate_body(const GateArgs<T> g, T* red) {      // thread 0 returns the verdict (done); red: 2 * kWavesPerBlock
     const int done = g.st->done, iters = g.st->iters, fail0 = g.st->fail;
     T a = 0, b = 0;                                  // the partials are on their way while the state is looked at
     for (int k = threadIdx.x; k < g.n; k += kBlock) { a += g.rdr_part[k]; b += g.bpart[k]; }
     issue_before_exit(a);
     int done_now = done, fail_now = fail0;
     if (!(done || iters == 0)) {                     // iteration 0: no step has been taken yet (a warm start is judged by k_warm_scale)
-        const T rdr = block_sum<T>(a, red);
-        const T bdb = block_sum<T>(b, red);
+        block_sum2<T>(a, b, red);
+        const T rdr = a, bdb = b;
         if (threadIdx.x == 0 && !(rdr > g.tol2 * bdb)) { fail_now = (rdr != rdr) ? 1 : 0; done_now = 1; g.st->done = 1; g.st->fail = fail_now; }      // NaN: breakdown
     }
     if (g.host_flag && threadIdx.x == 0)      // ONE aligned 8-byte store: the host never sees the fields of two gates mixed
@@ -525,7 +596,7 @@ __global__ __launch_bounds__(kBlock) void k_schur_lm(const uint32_t* __restrict_
                                                      const float* __restrict__ zc32 = nullptr, float* __restrict__ t32 = nullptr,
                                                      const GateArgs<T> gate = GateArgs<T>{nullptr, nullptr, nullptr, 0, T(0), nullptr, 0},
                                                      T lambda = T(0), T* __restrict__ pred_part = nullptr) {
-    __shared__ T red[kWavesPerBlock];
+    __shared__ T red[2 * kWavesPerBlock];
     __shared__ int verdict;
     // The iteration's stopping rule rides in workgroup 0 of its first product (gate_n > 0; the state it judges and sets is st, its
     // partials gate_rdr / gate_b, the rest of GateArgs in `gate`): one launch fewer per iteration.  st is neither const nor __restrict__:
@@ -632,7 +703,7 @@ __global__ __launch_bounds__(kBlock) void k_schur_pose(const uint32_t* __restric
                                                        const float* __restrict__ t32 = nullptr,
                                                        const T* __restrict__ post_minv = nullptr, const T* __restrict__ post_r = nullptr,
                                                        const T* __restrict__ post_omega = nullptr, T* __restrict__ zc_post = nullptr) {
-    __shared__ T red[kWavesPerBlock];
+    __shared__ T red[2 * kWavesPerBlock];
     // post_minv (the SECOND product inside a multigrid cycle, one shard, f32-copy operands): the level-0 post-smoothing
     // zc_i += omega Minv_i (r_i - (S z)_i) in this kernel's epilogue instead of a launch of its own (k_smooth0<1>).  The pass gathers
     // its operands from the f32 copies (zc32), so writing the f64 records it does not read is no race; the f32 copies are rewritten by
@@ -724,11 +795,12 @@ __global__ __launch_bounds__(kBlock) void k_schur_pose(const uint32_t* __restric
             }
         }
     }
-    const T total = block_sum<T>(dot, red);
-    if (threadIdx.x == 0) dot_part[blockIdx.x] = total;
-    if (rvec) {        // wave-uniform: a kernel argument
-        const T trz = block_sum<T>(rz, red);
-        if (threadIdx.x == 0) rz_part[blockIdx.x] = trz;
+    if (rvec) {        // wave-uniform: a kernel argument.  The PCG product: (S z, z) and (r, z) in one reduction
+        block_sum2<T>(dot, rz, red);
+        if (threadIdx.x == 0) { dot_part[blockIdx.x] = dot; rz_part[blockIdx.x] = rz; }
+    } else {
+        const T total = block_sum<T>(dot, red);
+        if (threadIdx.x == 0) dot_part[blockIdx.x] = total;
     }
 }
 
