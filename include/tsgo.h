@@ -82,7 +82,8 @@ typedef struct tsgo_config {
                                 blocks are all-reduced (rank 0 contributes the diagonal), everything below is computed redundantly. */
     int32_t xcd_map;         /* 1: workgroup -> slice map gives each XCD a contiguous eighth of the vertices; 0: round-robin */
     int32_t warm_start;      /* 0: PCG starts from zero.  m >= 1: from a prediction of this solve's pose delta made from the deltas of the last
-                                (up to m, at most 6) Gauss-Newton iterations: order 1 is (1 - step) * the previous delta (the un-taken
+                                (up to m, at most 5: a sixth delta is held only to measure order 5, and only measured orders are taken,
+                                so values above 5 act as 5) Gauss-Newton iterations: order 1 is (1 - step) * the previous delta (the un-taken
                                 remainder of the last step); order k continues the degree-(k-1) trend of delta_j / (1 - step)^j.  Below the
                                 cap the engine takes, solve by solve, the order that would have predicted the previous delta best.
                                 Default 6.  Same answer to pcg_rel_tol. */

@@ -34,6 +34,32 @@ int tsgo_comm_init_local(tsgo_optimizer* opt, tsgo_local_group* group);
  *            no column is stopped.  which <= 2 loop over the columns. */
 int tsgo_testing_apply(tsgo_optimizer* opt, int32_t which, const double* in, double* out, int32_t n_cols);
 
+/* The PCG warm start of `opt` (engine/engine_solve.inc: launch_warm; kernels k_pack_x, k_warm_residual, k_warm_scale, and k_save_x /
+ * k_save_update, which leave the history and the prediction errors): what it decides and writes, read out of the handle
+ * (tests/test_gpu_warm_start.py).  All vectors are 3 * P doubles in the order of the graph's POSE vertices, as in tsgo_testing_apply,
+ * widened from the handle's precision.  The call linearises at the current estimates (without damping) with a hierarchy built for that
+ * linearisation, runs launch_warm as do_solve does when `warmed`, and reads; like tsgo_testing_apply it restores every device byte of the
+ * handle afterwards, and the solver's host-side memory (the counters below, the rotation of the history buffers) as well: the next
+ * tsgo_optimize computes, bit for bit, what it would have without the call.
+ *   n_plant = 0: the history the handle holds.
+ *   n_plant = 1 .. 12: the history is forgotten first, then `plant` (n_plant deltas of 3 * P doubles, OLDEST first, each rounded to the
+ *     handle's precision) is recorded delta by delta through the code the Gauss-Newton loops record a solved delta with (record_delta):
+ *     fused = 0 by k_save_x, fused = 1 by k_save_update with step 0, which leaves the estimates alone.  Only the last 6 are kept.
+ * Refused: a handle without a graph, a sharded handle (world > 1), n_plant outside [0, 12], n_plant > 0 without `plant`, fused not 0 or 1. */
+typedef struct tsgo_testing_warm_out {
+    int32_t warmed;                 /* do_solve's own test: cfg.warm_start && have_prev && step_scale() < 1 */
+    int32_t n_prev, n_tested, n_max;/* as launch_warm computes them */
+    int32_t order;                  /* *warm_order_dev */
+    int32_t done;                   /* st[0]->done after k_warm_scale (multigrid); 0 for block-Jacobi */
+    int32_t carried;                /* mem.carried */
+    double err[6];                  /* row m of warm_err summed over the workgroups, m < n_tested; 0 beyond */
+    double scale, bdb, rdr;         /* *gscale_dev and the sums of the two partial arrays k_warm_scale read */
+    double *hist;                   /* n_prev x 3P, newest first; may be NULL */
+    double *b, *x0, *r0;            /* 3P each: r before launch_warm, x and r after it; each may be NULL */
+} tsgo_testing_warm_out;
+/* warmed = 0: the counters and b are returned, everything else is 0 / untouched. */
+int tsgo_testing_warm_start(tsgo_optimizer* opt, int32_t n_plant, const double* plant, int32_t fused, tsgo_testing_warm_out* out);
+
 /* ---- the device pattern builders (toyslam_amd/csrc/tsgo_sym_kernels.h) on caller-given integer arrays: tests/test_gpu_sym_patterns.py.
  * No handle, no graph, no linearisation: each call allocates its own device scratch, launches the kernels through the launch helpers the
  * engine itself uses (the same geometry) on the null stream, copies everything they wrote back and frees the scratch before it returns.

@@ -51,7 +51,7 @@ def test_shipped_binaries_contain_no_test_hook_or_research_variable():
     research set, in the server and in both product libraries; the testing twin of the library has them."""
     names = [b"TSGO_INJECT_AMG_FAILURE", b"TSGO_FORCE_HOST_SLOW", b"TSGO_FORCE_PACED", b"TSGO_SYM_DECLINE", b"TSGO_HOST_PRODUCTS", b"TSGO_HIER_MAX_AGE",
              b"TSGO_HIER_SLACK", b"TSGO_AGGC", b"TSGO_AGG_LIST", b"TSGO_AGG_MODE", b"TSGO_SWEEPS_LIST", b"TSGO_PACE_LEAD", b"TSGO_SORT_WINDOW_POSE", b"tsgo_local_group_create", b"tsgo_testing_apply",
-             b"tsgo_testing_sym_scan", b"tsgo_testing_sym_product", b"tsgo_testing_schur_pattern"]
+             b"tsgo_testing_sym_scan", b"tsgo_testing_sym_product", b"tsgo_testing_schur_pattern", b"tsgo_testing_warm_start"]
     for path in (build.HIP_SO, build.HOST_SO, build.SERVER):
         if not os.path.exists(path):
             pytest.skip("%s not built yet" % path)

@@ -150,6 +150,11 @@ class tsgo_testing_schur_out(C.Structure):
                [("nnz", C.c_int64), ("pairs", C.c_int64), ("od", C.c_int64), ("declined", C.c_int32), ("reserved", C.c_int32)]
 
 
+class tsgo_testing_warm_out(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("warmed", "n_prev", "n_tested", "n_max", "order", "done", "carried")] + \
+               [("err", C.c_double * 6), ("scale", C.c_double), ("bdb", C.c_double), ("rdr", C.c_double)] + [(n, C.c_void_p) for n in ("hist", "b", "x0", "r0")]
+
+
 HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_default_gnc", "tsgo_default_dogleg", "tsgo_last_error", "tsgo_wire_decode", "tsgo_wire_new", "tsgo_wire_decode_into", "tsgo_wire_view", "tsgo_wire_free",
                 "tsgo_wire_encode_response", "tsgo_wire_encode_request", "tsgo_synth_create", "tsgo_synth_view",
                 "tsgo_synth_truth", "tsgo_synth_free", "tsgo_layout_probe", "tsgo_amg_probe", "tsgo_amg_probe_shard", "tsgo_init_tree", "tsgo_sample_noise"]
@@ -159,7 +164,7 @@ DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_
                   "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc", "tsgo_sample_marginals", "tsgo_set_dogleg", "tsgo_get_dogleg", "tsgo_get_dogleg_trace",
                   "tsgo_set_edge_robust", "tsgo_get_edge_robust"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply",
-                   "tsgo_testing_sym_scan", "tsgo_testing_sym_product", "tsgo_testing_schur_pattern", "tsgo_testing_lane_sums"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
+                   "tsgo_testing_sym_scan", "tsgo_testing_sym_product", "tsgo_testing_schur_pattern", "tsgo_testing_lane_sums", "tsgo_testing_warm_start"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
 
 def _declare_host(L):
@@ -235,6 +240,7 @@ def _declare_testing(L):
     L.tsgo_testing_sym_product.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.POINTER(tsgo_testing_sym_out)]
     L.tsgo_testing_schur_pattern.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [vp] * 9 + [C.c_int32, C.POINTER(tsgo_testing_schur_out)]
     L.tsgo_testing_lane_sums.argtypes = [vp, vp, vp, vp]
+    L.tsgo_testing_warm_start.argtypes = [vp, C.c_int32, vp, C.c_int32, C.POINTER(tsgo_testing_warm_out)]
 
 
 _host = None

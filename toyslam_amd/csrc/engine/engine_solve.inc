@@ -77,6 +77,11 @@
     // Warm start (cfg.warm_start): the Gauss-Newton update takes kStepScale of the solved delta, so (1 - kStepScale) of it
     // is still to go at the next linearisation.  x0 = that remainder, r = b~ - S x0 (one extra product), and the stopping
     // rule keeps measuring against the right-hand side: gamma0 is scaled by (b^T D^-1 b) / (r0^T D^-1 r0).
+    // the highest order launch_warm allows, and how many orders have an error to choose by
+    void warm_orders(int& n_max, int& n_tested) const {
+        n_max = std::max(1, std::min({mem.n_prev, (int)cfg.warm_start, kMaxWarm}));
+        n_tested = std::min(mem.n_tested, n_max);
+    }
     int launch_warm() {
         // x0 = the un-taken remainder of the previous step, (1 - step) d1, at order 1; higher orders continue the trend of the last
         // deltas as well (order 2: (1 - step) (d1 + c1) with c1 = d1 - (1 - step) d2, what the last step added over ITS prediction).
@@ -86,8 +91,7 @@
         WarmTerms<T> w{};
         warm_coefficients(w);
         for (int j = 0; j < kMaxWarm; ++j) w.v[j] = hist[j];
-        w.n_max = std::max(1, std::min({mem.n_prev, (int)cfg.warm_start, kMaxWarm}));
-        w.n_tested = std::min(mem.n_tested, w.n_max);
+        warm_orders(w.n_max, w.n_tested);
         w.errpart = warm_err; w.nb_err = nbC;
         launch_pack_x(w, warm_order_dev);
         if (int rc = launch_matvec(0)) return rc;
@@ -310,6 +314,20 @@
         return 0;
     }
 
+    // The solved delta in x enters the warm start's history (k_save_x; fused: k_save_update, which also takes the step): the oldest buffer
+    // takes it, the orders that can be tested on it leave their prediction errors in warm_err, and the three counters move.  (Also what
+    // tsgo_testing_warm_start plants a history with, engine_testing.inc.)
+    void record_delta(bool fused, T step) {
+        std::rotate(hist, hist + kMaxWarm - 1, hist + kMaxWarm);      // the oldest buffer takes this delta; hist[1..] are the deltas before it
+        WarmTerms<T> w{};
+        warm_coefficients(w);
+        for (int j = 0; j + 1 < kMaxWarm; ++j) w.v[j] = hist[j + 1];
+        w.n_max = std::min({mem.n_prev, (int)cfg.warm_start, kMaxWarm - 1});      // orders that can be tested on this delta
+        if (fused) launch_save_update(w, hist[0], warm_err, step);
+        else launch_save_x(w, hist[0], warm_err);
+        mem.n_tested = w.n_max; mem.have_prev = true; mem.n_prev = std::min(mem.n_prev + 1, kMaxWarm);
+    }
+
     // landmarks: dl = u - Dl^-1 W^T x (+ optional update); poses: update.  Returns ||delta_p||^2 (identical on every
     // rank: pose vectors are replicated) and THIS rank's ||delta_l||^2 (landmark deltas are shard-local).
     // Step reports (one-shard handles): a step that is taken runs k_save_x and k_pose_update as ONE launch in front of the landmark pass (which
@@ -318,14 +336,7 @@
         const int P = pr.P;
         const bool report = reports(), fused = report && step != T(0);
         if (step != T(0)) {
-            std::rotate(hist, hist + kMaxWarm - 1, hist + kMaxWarm);      // the oldest buffer takes this delta; hist[1..] are the deltas before it
-            WarmTerms<T> w{};
-            warm_coefficients(w);
-            for (int j = 0; j + 1 < kMaxWarm; ++j) w.v[j] = hist[j + 1];
-            w.n_max = std::min({mem.n_prev, (int)cfg.warm_start, kMaxWarm - 1});      // orders that can be tested on this delta
-            if (fused) launch_save_update(w, hist[0], warm_err, step);
-            else launch_save_x(w, hist[0], warm_err);
-            mem.n_tested = w.n_max; mem.have_prev = true; mem.n_prev = std::min(mem.n_prev + 1, kMaxWarm);
+            record_delta(fused, step);
         } else {      // a probe (step 0) leaves nothing to carry over
             launch_pack_x(WarmTerms<T>{}, (int*)nullptr);
             mem.have_prev = false; mem.n_prev = 0; mem.n_tested = 0;

@@ -30,7 +30,7 @@
 //   engine/engine_dogleg.inc       rules = 3, Powell's dogleg trust-region loop: one linearisation and one solve per ACCEPTED step, trials from the snapshot; tsgo_set_dogleg,
 //                                  tsgo_get_dogleg_trace.  Kernels: tsgo_dogleg_kernels.h (f64 only) — the gradient as dense vectors, g'Hg by the once-per-edge walk
 //                                  (a third visitor of tsgo_edge_walk.h), the step from the snapshot
-//   engine/engine_testing.inc      tsgo_testing_apply (TSGO_TESTING builds only): the operators PCG applies, read out column by column
+//   engine/engine_testing.inc      tsgo_testing_apply, tsgo_testing_warm_start (TSGO_TESTING builds only): the operators PCG applies, read out column by column; the warm start's outputs
 //   engine/sym_testing.inc         (file scope, TSGO_TESTING builds only) the pattern builders of tsgo_sym_kernels.h on caller-given arrays
 //   engine/lane_testing.inc        (file scope, TSGO_TESTING builds only) the lane sums of tsgo_kernels.h on caller-given values
 //
@@ -191,6 +191,7 @@ struct IEngine {
     virtual int gnc(const tsgo_gnc_params& p, const uint8_t* subject, int64_t n_mask, double* w_out, int64_t cap_edges, tsgo_gnc_stats* st) = 0;
 #ifdef TSGO_TESTING
     virtual int testing_apply(int which, const double* in, double* out, int n_cols) = 0;
+    virtual int testing_warm_start(int n_plant, const double* plant, int fused, tsgo_testing_warm_out* out) = 0;
 #endif
     ncclComm_t comm = nullptr;
     tsgo_local_group* lgroup = nullptr;      // in-process stand-in for the communicator (tests on a one-GPU box; always null outside TSGO_TESTING builds)
@@ -688,6 +689,10 @@ int tsgo_comm_init_local(tsgo_optimizer* o, tsgo_local_group* g) {
 int tsgo_testing_apply(tsgo_optimizer* o, int32_t which, const double* in, double* out, int32_t n_cols) {
     if (!o) return tsgo::set_error(-1, "tsgo_testing_apply: null handle");
     return o->eng->testing_apply(which, in, out, n_cols);
+}
+int tsgo_testing_warm_start(tsgo_optimizer* o, int32_t n_plant, const double* plant, int32_t fused, tsgo_testing_warm_out* out) {
+    if (!o) return tsgo::set_error(-1, "tsgo_testing_warm_start: null handle");
+    return o->eng->testing_warm_start(n_plant, plant, fused, out);
 }
 int tsgo_testing_sym_scan(int32_t n, const int32_t* in, int32_t* out) { return sym_scan_run(n, in, out); }
 int tsgo_testing_lane_sums(const float* in32, const double* in64, float* out32, double* out64) {

@@ -444,6 +444,22 @@ iters=st.iterations_run, stop=STOP[st.stop_reason], chi2=np.array(st.chi2[:n]), 
         _lib.check(self.lib, self.lib.tsgo_testing_apply(self.h, int(which), cols.ctypes.data, out.ctypes.data, cols.shape[0]), "tsgo_testing_apply")
         return np.ascontiguousarray(out.T).reshape(x.shape)
 
+    def testing_warm_start(self, plant=None, fused=0):
+        """tsgo_testing_warm_start (testing=True handles): what the PCG warm start decides and writes, as a dict of the fields of
+        tsgo_testing_warm_out; vectors (3 P,) in the order of the graph's pose vertices, hist (n_prev, 3 P) newest first.  plant: None
+        (the history the handle holds) or (n, 3 P) deltas, oldest first, recorded through k_save_x (fused=0) or k_save_update (fused=1)
+        after the history is forgotten.  The handle is left as it was."""
+        P = int((self._ids_types[1] == 0).sum()) if self._ids_types is not None else 0
+        n = 0 if plant is None else len(plant)
+        pl = None if plant is None else np.ascontiguousarray(np.asarray(plant, np.float64).reshape(n, 3 * P))
+        hist = np.zeros((6, 3 * P)); b = np.zeros(3 * P); x0 = np.zeros(3 * P); r0 = np.zeros(3 * P)
+        out = _lib.tsgo_testing_warm_out()
+        out.hist, out.b, out.x0, out.r0 = hist.ctypes.data, b.ctypes.data, x0.ctypes.data, r0.ctypes.data
+        _lib.check(self.lib, self.lib.tsgo_testing_warm_start(self.h, n, pl.ctypes.data if n else None, int(fused), C.byref(out)), "tsgo_testing_warm_start")
+        res = {f: getattr(out, f) for f in ("warmed", "n_prev", "n_tested", "n_max", "order", "done", "carried", "scale", "bdb", "rdr")}
+        res.update(err=np.array(out.err[:]), hist=hist[:out.n_prev].copy(), b=b, x0=x0, r0=r0)
+        return res
+
     def comm_init_local(self, group):
         """group: a handle from local_group(world) shared by the handles of this process (one thread each)."""
         _lib.check(self.lib, self.lib.tsgo_comm_init_local(self.h, group), "tsgo_comm_init_local")
