@@ -587,6 +587,45 @@ int tsgo_set_edge_information(tsgo_optimizer* opt, int64_t n, const int64_t* edg
                               tsgo_edge_info_stats* stats /* may be NULL */);
 int tsgo_get_edge_information(tsgo_optimizer* opt, double* e_inf_out, int64_t cap_edges);
 
+/* Edit vertices in place on the device (g2o's setFixed and setEstimate on a live optimizer): which vertices are fixed,
+ * and the estimates of listed vertices, without a tsgo_set_graph — which would rebuild the layout for another fixed list and, as a refill,
+ * drop every weight edit, the per-edge robust setting and the solver's history for other estimates.  Typical: move the anchor to the
+ * current pose, so that tsgo_marginals and tsgo_gate_edges give uncertainty relative to the robot; freeze the old part of a map; release a
+ * surveyed landmark; try a relocalisation hypothesis under tsgo_edge_report.
+ * tsgo_set_fixed: count[i] is the multiplicity of ids[i] in the fixed list (NULL: 1 each); 0 releases the vertex, k >= 1 stands for k
+ * occurrences (the gauge term is 1e6 per occurrence).  Unlisted vertices keep theirs.  The call writes (T)(1e6 * k) into the handle's two
+ * gauge arrays and nothing else on the device: the estimates keep their bits.
+ *   The canonical list: afterwards the handle's fixed list is the vertices with count > 0 in tsgo_graph vertex order, each repeated count
+ *   times, and every reader sees it — the linearisation, tsgo_init_estimates (its breadth-first sources and the landmarks it leaves alone),
+ *   and the "is H regular" check of tsgo_marginals, tsgo_joint_marginals, tsgo_gate_edges and tsgo_sample_marginals.  Every later call
+ *   behaves, bit for bit where the same kernels see the same inputs, as a fresh handle given the same graph with that list.  Releasing
+ *   every fixed vertex is legal: the result is what tsgo_set_graph makes of n_fixed = 0, and tsgo_marginals then refuses as it does there.
+ *   Solver state: the rule of tsgo_set_edge_information.  The next linearisation builds a fresh multigrid hierarchy; the warm start's
+ *   history, weight edits, the per-edge robust setting and the robust setting stay.  n == 0 returns 0 and changes nothing.
+ *   Lifetime: that of an edit.  The next tsgo_set_graph installs the list it carries; whether it may reuse the structure is still decided
+ *   against the list of the previous tsgo_set_graph, not against the edit.
+ * tsgo_get_fixed: the multiplicities the handle holds now, one per vertex in tsgo_graph order (after a plain tsgo_set_graph: the
+ * occurrences in its list).
+ * tsgo_set_estimates: the listed vertices receive (x, y, theta) — 3 doubles per listed vertex, a landmark's third is ignored — exactly as
+ * tsgo_set_graph writes them: a pose's record ((T)x, (T)y, (T)cos theta, (T)sin theta) and (T)theta with cos / sin taken on the host in
+ * f64, a landmark's (T)x, (T)y.  ids == NULL: every vertex in order (n must equal n_vertices).  Every other estimate keeps its bits; fixed
+ * vertices may be listed.  The call ends as tsgo_init_estimates does: the solver restarts as after a refill and the warm start's history
+ * is dropped even under warm_requests.  Weight edits, robust settings and a tsgo_set_fixed stay.
+ * Errors (< 0, text in tsgo_last_error; everything is validated before anything is staged or launched, the handle is exactly as before):
+ * a NULL handle; no graph set; n < 0; ids == NULL with n > 0 (set_fixed) or with n != n_vertices (set_estimates); v_pos == NULL with n > 0;
+ * an unknown id; an id listed twice; a count outside [0, 65535]; an estimate that is not finite on an axis the vertex uses; cap_vertices <
+ * n_vertices or count_out == NULL with vertices to return (get); an edge-sharded handle (world > 1), for all three. */
+typedef struct tsgo_vertex_edit_stats {
+    int64_t listed, poses, landmarks;     /* vertices listed; of them Se2 / Point2 */
+    int64_t fixed_now, released;          /* vertices of the graph with count > 0 after the call; set_fixed: listed vertices that went from > 0 to 0 */
+    double ms_total, ms_host, ms_device;  /* whole call; validation + staging; hipEvent time of the kernel */
+} tsgo_vertex_edit_stats;
+int tsgo_set_fixed(tsgo_optimizer* opt, int64_t n, const uint32_t* ids, const int32_t* count /* may be NULL: 1 each */,
+                   tsgo_vertex_edit_stats* stats /* may be NULL */);
+int tsgo_get_fixed(tsgo_optimizer* opt, int32_t* count_out /* 1 per vertex, tsgo_graph order */, int64_t cap_vertices);
+int tsgo_set_estimates(tsgo_optimizer* opt, int64_t n, const uint32_t* ids /* NULL: all vertices in order, n == n_vertices */,
+                       const double* v_pos /* 3 per listed vertex */, tsgo_vertex_edit_stats* stats /* may be NULL */);
+
 /* Graduated non-convexity with the truncated-least-squares surrogate (Yang, Antonante, Tzoumas, Carlone 2020; GTSAM's GncOptimizer with
  * known inliers): the outer loop for a graph whose start cannot be trusted, where an M-estimator of tsgo_set_robust
  * only helps near the optimum.  Every round re-evaluates every edge on the device, turns its squared residual into a weight in [0, 1] and

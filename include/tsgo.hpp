@@ -131,7 +131,7 @@ public:
     }
     const tsgo_stats& Stats() const { return stats; }
     // Optimises the graph the handle HOLDS (SetGraph) without handing it over again, so that what was set on it since — SetEdgeRobust,
-    // SetEdgeInformation, InitEstimates — stays in force; `graph` (the one given to SetGraph) receives the positions.  Throws on an error.
+    // SetEdgeInformation, InitEstimates, SetFixed, SetEstimates — stays in force; `graph` (the one given to SetGraph) receives the positions.  Throws on an error.
     void OptimizeHeld(Graph* graph) {
         if (tsgo_optimize(handle, (int)iterations, &stats)) throw std::runtime_error(tsgo_last_error());
         if (!graph) return;
@@ -309,6 +309,29 @@ public:
         std::vector<double> inf((size_t)n * 3);
         if (tsgo_get_edge_information(handle, inf.empty() ? nullptr : inf.data(), n)) throw std::runtime_error(tsgo_last_error());
         return inf;
+    }
+    // Edit vertices in place (tsgo_set_fixed, tsgo_set_estimates) on the graph last handed to Optimize or SetGraph.  SetFixed: `counts` is the
+    // multiplicity of each listed id in the fixed list (empty: 1 each; 0 releases), unlisted vertices keep theirs; Release: count 0 for the
+    // listed ids; FixedCounts: what the handle holds now, one per vertex in the graph's vertex order.  SetEstimates: three doubles (x, y,
+    // theta) per listed id, a landmark's third is ignored; an empty `ids` with 3 * VertexCount values is "every vertex in order".  The other
+    // estimates, weight edits and robust settings stay; run OptimizeHeld afterwards — Optimize(graph) or SetGraph installs the list and the
+    // positions the graph carries.  All throw on an error (no graph yet, an unknown id or one listed twice, a count outside [0, 65535], a
+    // non-finite estimate, an edge-sharded handle).
+    void SetFixed(const std::vector<uint32_t>& ids, const std::vector<int32_t>& counts = std::vector<int32_t>(), tsgo_vertex_edit_stats* stats = nullptr) {
+        if (!counts.empty() && counts.size() != ids.size()) throw std::runtime_error("SetFixed: one count per listed id");
+        if (tsgo_set_fixed(handle, (int64_t)ids.size(), ids.empty() ? nullptr : ids.data(), counts.empty() ? nullptr : counts.data(), stats))
+            throw std::runtime_error(tsgo_last_error());
+    }
+    void Release(const std::vector<uint32_t>& ids, tsgo_vertex_edit_stats* stats = nullptr) { SetFixed(ids, std::vector<int32_t>(ids.size(), 0), stats); }
+    std::vector<int32_t> FixedCounts(size_t n_vertices) const {
+        std::vector<int32_t> counts(n_vertices);
+        if (tsgo_get_fixed(handle, counts.empty() ? nullptr : counts.data(), (int64_t)n_vertices)) throw std::runtime_error(tsgo_last_error());
+        return counts;
+    }
+    void SetEstimates(const std::vector<uint32_t>& ids, const std::vector<double>& xyt, tsgo_vertex_edit_stats* stats = nullptr) {
+        if (!ids.empty() && xyt.size() != ids.size() * 3) throw std::runtime_error("SetEstimates: three values per listed id");
+        if (tsgo_set_estimates(handle, (int64_t)(xyt.size() / 3), ids.empty() ? nullptr : ids.data(), xyt.empty() ? nullptr : xyt.data(), stats))
+            throw std::runtime_error(tsgo_last_error());
     }
     // Graduated non-convexity, truncated least squares (tsgo_gnc), on the graph last handed to Optimize or SetGraph: rounds of on-device
     // reweighting and Optimize-style inner runs under the handle's own rules and robust setting (textbook GNC: SetRobust NONE on every

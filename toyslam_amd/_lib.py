@@ -90,6 +90,10 @@ class tsgo_edge_info_stats(C.Structure):
                 ("ms_total", C.c_double), ("ms_host", C.c_double), ("ms_device", C.c_double)]
 
 
+class tsgo_vertex_edit_stats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("listed", "poses", "landmarks", "fixed_now", "released")] + [(n, C.c_double) for n in ("ms_total", "ms_host", "ms_device")]
+
+
 TSGO_GNC_MAX_ROUNDS = 128
 GNC_STOP = {0: "all_inliers", 1: "binary", 2: "rounds", 3: "solver_failed"}      # TSGO_GNC_*
 
@@ -162,7 +166,7 @@ DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_
                   "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
                   "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust", "tsgo_edge_report", "tsgo_gate_edges", "tsgo_init_estimates",
                   "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc", "tsgo_sample_marginals", "tsgo_set_dogleg", "tsgo_get_dogleg", "tsgo_get_dogleg_trace",
-                  "tsgo_set_edge_robust", "tsgo_get_edge_robust"]
+                  "tsgo_set_edge_robust", "tsgo_get_edge_robust", "tsgo_set_fixed", "tsgo_get_fixed", "tsgo_set_estimates"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply",
                    "tsgo_testing_sym_scan", "tsgo_testing_sym_product", "tsgo_testing_schur_pattern", "tsgo_testing_lane_sums", "tsgo_testing_warm_start"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
@@ -228,6 +232,9 @@ def _declare_device(L):
     L.tsgo_set_edge_information.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(tsgo_edge_info_stats)]
     L.tsgo_get_edge_information.argtypes = [vp, vp, C.c_int64]
     L.tsgo_gnc.argtypes = [vp, C.POINTER(tsgo_gnc_params), vp, C.c_int64, vp, C.c_int64, C.POINTER(tsgo_gnc_stats)]
+    L.tsgo_set_fixed.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(tsgo_vertex_edit_stats)]
+    L.tsgo_get_fixed.argtypes = [vp, vp, C.c_int64]
+    L.tsgo_set_estimates.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(tsgo_vertex_edit_stats)]
 
 
 def _declare_testing(L):

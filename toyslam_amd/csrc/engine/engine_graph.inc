@@ -220,6 +220,7 @@
         return 0;
     }
     int refill_values(const tsgo_graph& g) {
+        if (int rc = restore_fixed()) return rc;      // a tsgo_set_fixed ends here: the request repeats the list the tables were built with (engine_edit.inc)
         if (int rc = stage_values(g, true)) return rc;
         if (int rc = stage_priors(g)) return rc;
         keep_prior_weights(g);
@@ -257,6 +258,7 @@
         release();
         drop_edge_robust();
         drop_structure_maps();      // the index described the old tables, and its device maps lived in the slabs just released
+        fixed_edited = false; fixed_edit.clear();      // a tsgo_set_fixed goes with the tables it edited: build_problem installs this request's list
         BuildOptions bo; bo.rank = cfg.rank; bo.world = cfg.world; bo.lanes_per_pose = cfg.lanes_per_pose; bo.lanes_per_lm = cfg.lanes_per_lm;
         bo.fill_planes = false;
         const std::string err = build_problem(g, bo, pr);

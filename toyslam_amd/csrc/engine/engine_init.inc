@@ -26,8 +26,9 @@
             InitTree tree;
             const VertexIndex& vi = vertices();
             {
+                const std::vector<uint32_t>& fixed = fixed_list();      // the request's list, or the canonical one of a tsgo_set_fixed (engine_edit.inc)
                 const tsgo_graph view{(int32_t)structure.v_id.size(), structure.v_id.data(), structure.v_type.data(), nullptr, (int32_t)E, structure.e_type.data(),
-                                      structure.e_ids.data(), nullptr, nullptr, (int32_t)structure.fixed.size(), structure.fixed.data()};
+                                      structure.e_ids.data(), nullptr, nullptr, (int32_t)fixed.size(), fixed.data()};
                 const std::string err = build_init_tree(view, mask, n_mask, tree, &vi.ids);
                 if (!err.empty()) return set_error(-2, "tsgo_init_estimates: " + err);
             }

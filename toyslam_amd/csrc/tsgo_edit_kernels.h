@@ -1,5 +1,6 @@
 // tsgo_edit_kernels.h — tsgo_set_edge_information / tsgo_get_edge_information on the device (engine/engine_edit.inc):
-// the information diagonal of listed edges written into, or read back from, every place the handle keeps it.
+// the information diagonal of listed edges written into, or read back from, every place the handle keeps it.  At the end of the file the
+// two scatters over listed VERTICES, tsgo_set_fixed and tsgo_set_estimates.
 //
 // A weight on the device is a plain copy of tsgo_graph.e_inf in the handle's scalar type (engine_graph.inc: stage_values, stage_priors),
 // so an edit is a scatter of (T)value and nothing else.  Where an input edge lives is the edge -> slot map: two 32-bit words per edge,
@@ -82,6 +83,45 @@ __global__ __launch_bounds__(kBlock) void k_get_edge_inf(int n_edges, const uint
     default: break;
     }
     out[3 * (size_t)e] = w0; out[3 * (size_t)e + 1] = w1; out[3 * (size_t)e + 2] = w2;
+}
+
+// ---- tsgo_set_fixed / tsgo_set_estimates (engine/engine_edit.inc): values of listed VERTICES ------------------------
+// A listed vertex arrives as two 32-bit words the host resolved through the structure index (VertexIndex): its kind (0 pose, 1 landmark)
+// and its number in the internal numbering, checked there against P and L.  The host's duplicate check gives every address ONE writer.
+constexpr uint32_t kEditPose = 0, kEditLm = 1;
+
+// One thread per listed vertex: (T)val[i], the gauge term 1e6 * multiplicity, into gauge_p / gauge_l.  Nothing else is written.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_set_gauge(int n, const uint2* __restrict__ ref, const double* __restrict__ val, T* __restrict__ gauge_p, int n_pose,
+                                                      T* __restrict__ gauge_l, int n_lm) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint2 at = ref[i];
+    const T g = (T)val[i];
+    if (at.x == kEditPose) { if (at.y < (uint32_t)n_pose) gauge_p[at.y] = g; }
+    else if (at.y < (uint32_t)n_lm) gauge_l[at.y] = g;
+}
+
+// One thread per listed vertex: val[5 i ..] = (x, y, cos theta, sin theta, theta), taken on the host in f64, written as stage_values writes
+// them (engine_graph.inc) — a pose's record and its theta, or the first two entries of a landmark's record (the others are what a
+// linearisation derives).  ref null: the dense form, every vertex in the internal numbering: thread i < n_pose is pose i, the others
+// landmark i - n_pose.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_set_estimates(int n, const uint2* __restrict__ ref, const double* __restrict__ val, T* __restrict__ ps, T* __restrict__ theta,
+                                                          int n_pose, T* __restrict__ lmrec, int n_lm) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint2 at = ref ? ref[i] : (i < n_pose ? make_uint2(kEditPose, (uint32_t)i) : make_uint2(kEditLm, (uint32_t)(i - n_pose)));
+    const double* v = val + 5 * (size_t)i;
+    if (at.x == kEditPose) {
+        if (at.y >= (uint32_t)n_pose) return;
+        T* q = ps + 4 * (size_t)at.y;
+        q[0] = (T)v[0]; q[1] = (T)v[1]; q[2] = (T)v[2]; q[3] = (T)v[3];
+        theta[at.y] = (T)v[4];
+    } else if (at.y < (uint32_t)n_lm) {
+        T* q = lmrec + (size_t)kLmRec * at.y;
+        q[0] = (T)v[0]; q[1] = (T)v[1];
+    }
 }
 
 }  // namespace tsgo

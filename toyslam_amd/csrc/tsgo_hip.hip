@@ -24,7 +24,8 @@
 //                                  they have no slot -> edge maps, count padding through its zero weight, and must agree with each other on chi^2 bit for bit
 //   engine/engine_gate.inc         tsgo_gate_edges: candidate edges against the joint marginal of their vertices (Mahalanobis gate)
 //   engine/engine_init.inc         tsgo_init_estimates: estimates from an odometry spanning tree (pointer jumping), landmarks from their observations
-//   engine/engine_edit.inc         tsgo_set_edge_information / tsgo_get_edge_information: the information diagonal of listed edges, in place
+//   engine/engine_edit.inc         tsgo_set_edge_information / tsgo_get_edge_information: the information diagonal of listed edges, in place;
+//                                  tsgo_set_fixed / tsgo_get_fixed / tsgo_set_estimates: the gauge terms and the estimates of listed vertices, in place
 //   engine/engine_edge_robust.inc  tsgo_set_edge_robust / tsgo_get_edge_robust: a palette of robust kernels and one byte per input edge; the per-slot byte arrays of the RK = 2 kernels
 //   engine/engine_gnc.inc          tsgo_gnc: graduated non-convexity (truncated least squares), one reweighting pass over the tables per round
 //   engine/engine_dogleg.inc       rules = 3, Powell's dogleg trust-region loop: one linearisation and one solve per ACCEPTED step, trials from the snapshot; tsgo_set_dogleg,
@@ -186,6 +187,9 @@ struct IEngine {
     virtual int init_estimates(int what, const uint8_t* mask, int64_t n_mask, tsgo_init_stats* st) = 0;
     virtual int set_edge_information(int64_t n, const int64_t* edge_idx, const double* e_inf, tsgo_edge_info_stats* st) = 0;
     virtual int get_edge_information(double* e_inf_out, int64_t cap_edges) = 0;
+    virtual int set_fixed(int64_t n, const uint32_t* ids, const int32_t* count, tsgo_vertex_edit_stats* st) = 0;
+    virtual int get_fixed(int32_t* count_out, int64_t cap_vertices) = 0;
+    virtual int set_estimates(int64_t n, const uint32_t* ids, const double* v_pos, tsgo_vertex_edit_stats* st) = 0;
     virtual int set_edge_robust(int32_t n_entries, const tsgo_edge_robust_entry* entries, const uint8_t* of_edge, int64_t n_mask, tsgo_edge_robust_stats* st) = 0;
     virtual int get_edge_robust(int32_t* n_out, tsgo_edge_robust_entry* entries_out, uint8_t* of_edge_out, int64_t cap_edges) = 0;
     virtual int gnc(const tsgo_gnc_params& p, const uint8_t* subject, int64_t n_mask, double* w_out, int64_t cap_edges, tsgo_gnc_stats* st) = 0;
@@ -355,6 +359,9 @@ template <typename T> struct Engine : IEngine {
         uint8_t* edit_cls = nullptr;               // [E]
         char* edit_buf = nullptr;                  // [32 E] bytes: (3 n doubles | n int64) of a set call; 3 E doubles of a get call
         bool edit_ready = false;
+        // tsgo_set_fixed / tsgo_set_estimates (engine_edit.inc): what a call sends, (values | kind and internal number) of its listed vertices
+        char* vedit_buf = nullptr;                 // [48 V] bytes
+        bool vedit_ready = false;
         // tsgo_sample_marginals (engine_sample.inc): slot -> input edge of by_lm (the other tables' are the report's), internal pose /
         // landmark -> position in the request's vertex arrays
         uint32_t* smp_lm_edge = nullptr;
@@ -744,6 +751,18 @@ int tsgo_set_edge_information(tsgo_optimizer* o, int64_t n, const int64_t* edge_
 int tsgo_get_edge_information(tsgo_optimizer* o, double* e_inf_out, int64_t cap_edges) {
     if (!o) return tsgo::set_error(-1, "tsgo_get_edge_information: null handle");
     return o->eng->get_edge_information(e_inf_out, cap_edges);
+}
+int tsgo_set_fixed(tsgo_optimizer* o, int64_t n, const uint32_t* ids, const int32_t* count, tsgo_vertex_edit_stats* stats) {
+    if (!o) return tsgo::set_error(-1, "tsgo_set_fixed: null handle");
+    return o->eng->set_fixed(n, ids, count, stats);
+}
+int tsgo_get_fixed(tsgo_optimizer* o, int32_t* count_out, int64_t cap_vertices) {
+    if (!o) return tsgo::set_error(-1, "tsgo_get_fixed: null handle");
+    return o->eng->get_fixed(count_out, cap_vertices);
+}
+int tsgo_set_estimates(tsgo_optimizer* o, int64_t n, const uint32_t* ids, const double* v_pos, tsgo_vertex_edit_stats* stats) {
+    if (!o) return tsgo::set_error(-1, "tsgo_set_estimates: null handle");
+    return o->eng->set_estimates(n, ids, v_pos, stats);
 }
 int tsgo_gnc(tsgo_optimizer* o, const tsgo_gnc_params* params, const uint8_t* subject, int64_t n_mask, double* w_out, int64_t cap_edges, tsgo_gnc_stats* stats) {
     if (!o || !params) return tsgo::set_error(-1, "tsgo_gnc: null handle or params");

@@ -370,6 +370,52 @@ iters=st.iterations_run, stop=STOP[st.stop_reason], chi2=np.array(st.chi2[:n]), 
         _lib.check(self.lib, self.lib.tsgo_get_edge_information(self.h, out.ctypes.data if self.n_edges else None, self.n_edges), "tsgo_get_edge_information")
         return out
 
+    def set_fixed(self, ids, count=1):
+        """Which vertices are fixed, edited in place on the device (tsgo_set_fixed).  ids: vertex ids of the graph the handle holds;
+        count: one integer, or one per id: the multiplicity of the id in the fixed list, 0 releases it.  Unlisted vertices keep theirs.
+        The estimates, every weight edit, the robust settings and the solver's history stay; the next set_graph installs the list it
+        carries.  Moving the anchor: release(old) and set_fixed(new) — or one call, set_fixed([old, new], [0, 1]).  Returns
+        tsgo_vertex_edit_stats as a dict."""
+        ids = np.ascontiguousarray(np.asarray(ids).reshape(-1).astype(np.uint32))
+        cnt = np.full(len(ids), int(count), dtype=np.int64) if np.ndim(count) == 0 else np.asarray(count, dtype=np.int64).reshape(-1)
+        if len(cnt) != len(ids):
+            raise ValueError("set_fixed: %d ids listed but count has %d entries" % (len(ids), len(cnt)))
+        if len(cnt) and (cnt.min() < -2**31 or cnt.max() >= 2**31):
+            raise ValueError("set_fixed: a count does not fit 32 bits")
+        cnt = np.ascontiguousarray(cnt.astype(np.int32))
+        st = _lib.tsgo_vertex_edit_stats()
+        n = len(ids)
+        _lib.check(self.lib, self.lib.tsgo_set_fixed(self.h, n, ids.ctypes.data if n else None, cnt.ctypes.data if n else None, C.byref(st)), "tsgo_set_fixed")
+        return {f: getattr(st, f) for f, _t in st._fields_}
+
+    def release(self, ids):
+        """The listed vertices are fixed no longer (set_fixed with count 0)."""
+        return self.set_fixed(ids, 0)
+
+    def fixed_counts(self):
+        """How often each vertex occurs in the fixed list the handle holds now (tsgo_get_fixed): (n_vertices,) int32 in the vertex order
+        of the graph given to set_graph."""
+        out = np.zeros(self.n_vertices, dtype=np.int32)
+        _lib.check(self.lib, self.lib.tsgo_get_fixed(self.h, out.ctypes.data if self.n_vertices else None, self.n_vertices), "tsgo_get_fixed")
+        return out
+
+    def set_vertices(self, pos, ids=None):
+        """Replace the estimates of vertices of the graph the handle holds, in place on the device (tsgo_set_estimates).  pos (n, 3):
+        (x, y, theta) per listed id, a landmark's third entry is ignored; ids=None: pos is (n_vertices, 3), every vertex in order.  The
+        other estimates keep their bits.  Weight edits, the robust settings and a set_fixed stay; the solver restarts as after
+        init_estimates.  Returns tsgo_vertex_edit_stats as a dict."""
+        pos = np.ascontiguousarray(np.asarray(pos, dtype=np.float64).reshape(-1, 3))
+        n = len(pos)
+        idp = None
+        if ids is not None:
+            idp = np.ascontiguousarray(np.asarray(ids).reshape(-1).astype(np.uint32))
+            if len(idp) != n:
+                raise ValueError("set_vertices: %d ids listed but pos has %d rows" % (len(idp), n))
+        st = _lib.tsgo_vertex_edit_stats()
+        _lib.check(self.lib, self.lib.tsgo_set_estimates(self.h, n, idp.ctypes.data if idp is not None else None, pos.ctypes.data if n else None,
+                                                          C.byref(st)), "tsgo_set_estimates")
+        return {f: getattr(st, f) for f, _t in st._fields_}
+
     def gnc(self, barc2=None, subject=None, mu_step=None, rounds_max=None, inner_iterations=None, keep_weights=True, weights=True):
         """Graduated non-convexity with the truncated-least-squares surrogate (tsgo_gnc): rounds of on-device reweighting, each followed
         by optimize(inner_iterations) under the handle's own rules and robust setting (textbook GNC: set_robust(all="none") first).
