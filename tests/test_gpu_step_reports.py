@@ -1,18 +1,20 @@
 """Step reports and the fused k_save_update against the path they replace (TSGO_STEP_DRAINS=1: copy + synchronise, k_save_x and
 k_pose_update as two launches), on fresh handles.  Neither touches a number or moves a decision, so everything a caller can see must be
 BITWISE equal: the chi^2 trace, the PCG iteration counts, the stop reason, the iterations run, the last delta norm and the vertices (under
-rules = 2 the per-trial traces as well).  The reference side also sets TSGO_PACE_SPLIT=0, whole-iteration pacing: split pacing of the paced
-solve was built, measured and taken out again (profiles/r12_step_chain.txt), so today that is the only pacing and nothing reads the variable."""
+rules = 2 and 3 the per-trial traces as well, under rules = 3 the dogleg trace).  Only the device times (ms_*) may differ between the two.
+The reference side also sets TSGO_PACE_SPLIT=0, whole-iteration pacing: split pacing of the paced solve was built, measured and taken out
+again (profiles/r12_step_chain.txt), so today that is the only pacing and nothing reads the variable."""
 import numpy as np
 import pytest
 
-from tests import edge_cases
+from tests import dogleg, edge_cases, lm_rules
 from toyslam_amd import synth
 from toyslam_amd.optimizer import HipOptimizer
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ("chi2", "cg_iters", "stop", "iters", "delta_norm", "rejected", "lm_lambda", "lm_gain", "lm_pred", "lm_chi2_trial")
+KEYS = ("chi2", "cg_iters", "stop", "iters", "delta_norm", "rejected", "lm_lambda", "lm_gain", "lm_pred", "lm_chi2_trial",
+        "dl_kind", "dl_solved", "dl_radius", "dl_step_norm", "dl_gg", "dl_gHg", "dl_gd", "dl_dd", "solves", "dl_radius_last")
 
 
 def _run(monkeypatch, old_way, graphs, calls, paced=False, **kw):
@@ -46,10 +48,10 @@ def _same(new, old):
         np.testing.assert_array_equal(a[-1], b[-1])
 
 
-def _both(monkeypatch, graphs, calls, **kw):
+def _both(monkeypatch, graphs, calls, both_ways=False, **kw):
     new, old = _run(monkeypatch, False, graphs, calls, **kw), _run(monkeypatch, True, graphs, calls, **kw)
     _same(new, old)
-    return new
+    return (new, old) if both_ways else new
 
 
 @pytest.fixture(scope="module")
@@ -76,6 +78,37 @@ def test_rules_1_and_2_four_iterations(monkeypatch, g2000, rules, paced):
     kw = dict(odom_jacobian="analytic") if rules == "lm" else {}
     r = _both(monkeypatch, [g2000], (4,), paced=paced, use_graphs=0, rules=rules, **kw)
     assert r[0][0]["iters"] == 4
+
+
+@pytest.mark.parametrize("paced", [False, True])
+def test_rules_2_with_a_rejection(monkeypatch, paced):
+    """c1 from a badly perturbed start: tests/test_lm_rules_cpu.py qualifies the case as rejecting at least one trial on the reference, so the
+    restore and the relinearisation at the restored point run both ways."""
+    p = lm_rules.C1_PERTURBED
+    r = _both(monkeypatch, [lm_rules.c1_perturbed()], (p["iterations"],), paced=paced, use_graphs=0, rules="lm", odom_jacobian="analytic", lm_lambda0=p["lambda0"])
+    assert r[0][0]["rejected"] >= 1
+
+
+@pytest.mark.parametrize("paced", [False, True])
+@pytest.mark.parametrize("case", ["B", "C", "D_priors"])
+def test_rules_3_trials(monkeypatch, case, paced):
+    """The dogleg loop both ways (the cases are qualified on the reference alone in tests/test_dogleg_cpu.py): B, boundary and dogleg steps;
+    C, one solve serving three rejected trials (the timing of a trial that reused a solve, the trial's report with the closing event behind
+    it); D_priors, the landmark priors' partials behind the g'Hg partials.  The device times are not compared between the two ways: each
+    way's must be finite, and positive wherever a phase ran."""
+    make, params, trials, jac = dogleg.CASES[case]
+    new, old = _both(monkeypatch, [make()], (trials,), both_ways=True, paced=paced, use_graphs=0, rules="dogleg", odom_jacobian=jac,
+                     **{"dl_" + k: v for k, v in params.items()})
+    r = new[0][0]
+    assert r["iters"] >= 1 and r["solves"] >= 1
+    if case == "C":
+        assert r["rejected"] == 3 and r["solves"] == 1 and list(r["dl_solved"]) == [1, 0, 0]
+    if case in ("B", "C"):
+        for way in (new, old):
+            ms = [way[0][0][k] for k in ("ms_linearize", "ms_solve", "ms_update")]
+            print(case, "paced" if paced else "burst", "report" if way is new else "drain", "ms_linearize %.4f ms_solve %.4f ms_update %.4f" % tuple(ms))
+            assert all(np.isfinite(m) and m >= 0 for m in ms), ms
+            assert ms[0] > 0 and ms[1] > 0 and ms[2] > 0, ms
 
 
 @pytest.mark.parametrize("paced", [False, True])

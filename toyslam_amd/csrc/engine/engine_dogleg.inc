@@ -4,7 +4,8 @@
 // One linearisation (lambda = 0, b zeroed at fixed vertices) and one solve give the Gauss-Newton step; every trial until a step is
 // accepted is a combination c1 g + c2 d_gn of it and the gradient, applied from the snapshot of rules = 2 (k_lm_state) and judged by the
 // chi^2-only pass (k_chi2).  A rejection shrinks the radius and costs one step kernel and one chi^2 pass: no linearisation, no hierarchy
-// work, no solve.  Kernels: tsgo_dogleg_kernels.h.
+// work, no solve.  Kernels: tsgo_dogleg_kernels.h.  The host steps around the launches are the ones rules 0 to 2 take (engine_solve.inc:
+// fetch_partials, sum_partials, begin_trial, note_linearisation / note_trial / accepted, end_step_timing; engine_launch.inc: launch_backsub).
     // ---- what belongs to the HANDLE (tsgo_hip.hip lists the lifetimes): the parameters survive tsgo_set_graph; the trace is the last tsgo_optimize's
     tsgo_dogleg_params dogleg = default_dogleg();
     tsgo_dogleg_trace dl_trace{};
@@ -22,20 +23,6 @@
         if (int rc = dalloc(&dl_gp, (size_t)pr.P * 3)) return rc;
         if (int rc = dalloc(&dl_gl, (size_t)std::max(pr.L, 1) * 2)) return rc;
         return dalloc(&dl_red, dl_red_size());
-    }
-    // n partials at src to the host: a step report, or copy + synchronise (the two ways of do_lm_step)
-    int dl_fetch(const T* src, size_t n, const T** h, hipEvent_t after = nullptr) {
-        if (reports()) {
-            const uint64_t rseq = launch_report(src, n);
-            if (after) HIP_OK(hipEventRecord(after, stream));
-            if (int rc = wait_report(rseq)) return rc;
-            *h = rep_data();
-        } else {
-            HIP_OK(hipMemcpyAsync(h_lm, src, sizeof(T) * n, hipMemcpyDeviceToHost, stream));
-            HIP_OK(hipStreamSynchronize(stream));
-            *h = h_lm;
-        }
-        return 0;
     }
     // g'Hg by the once-per-edge walk (tsgo_time_kernel 9 too): nbP partials at `out`, the landmark priors' nbL behind them
     // (f64 instantiations only: tsgo_create refuses rules = 3 with precision = 32, and the f32 engine launches none of the three)
@@ -67,21 +54,15 @@
     // gradient vectors and the four scalars.  Nothing enters the warm start's history.
     struct DoglegScalars { double gg = 0, gd = 0, dd = 0, ghg = 0; };
     int dl_after_solve(DoglegScalars* out) {
-        const int P = pr.P, L = pr.L;
-        launch(k_lm_state<T, 0>, grid_for(std::max(P, L)), P, L, ps, theta, lmrec, snap_ps, snap_theta, snap_lm);
-        launch_pack_x(WarmTerms<T>{}, (int*)nullptr);
-        mem.have_prev = false; mem.n_prev = 0; mem.n_tested = 0;
-        if (tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
-            launch_table(k_schur_lm<T, g, 1, 0>, nbL, tl, 0, st[0], (const T*)ninv, (const T*)nullptr, (const T*)nullptr, tl, (const T*)zc, lmrec, tvec, T(0), dl, npart + nbC, (const float*)nullptr, (float*)nullptr, no_gate(), T(0), (T*)nullptr);
-        });
+        begin_trial();
+        launch_backsub<1>(T(0), npart + nbC, T(0), nullptr);
         launch_dl_gradient();
         launch_ghg(dl_red + (size_t)3 * dl_nb());
         const int nb = dl_nb(), nlp = report_lm_priors() ? nbL : 0;
         const T* h = nullptr;
-        if (int rc = dl_fetch(dl_red, (size_t)3 * nb + nbP + nlp, &h)) return rc;
-        auto sum = [&](size_t from, int count) { double v = 0; for (int k = 0; k < count; ++k) v += (double)h[from + k]; return v; };
-        out->gg = sum(0, nb); out->gd = sum((size_t)nb, nb); out->dd = sum((size_t)2 * nb, nb);
-        out->ghg = sum((size_t)3 * nb, nbP) + sum((size_t)3 * nb + nbP, nlp);
+        if (int rc = fetch_partials(dl_red, (size_t)3 * nb + nbP + nlp, &h)) return rc;
+        out->gg = sum_partials(h, 0, nb); out->gd = sum_partials(h, (size_t)nb, nb); out->dd = sum_partials(h, (size_t)2 * nb, nb);
+        out->ghg = sum_partials(h, (size_t)3 * nb, nbP) + sum_partials(h, (size_t)3 * nb + nbP, nlp);
         return 0;
     }
     // the trial step from the snapshot and chi^2 there, one report
@@ -89,44 +70,14 @@
         if constexpr (kDoglegKernels) launch(k_dl_step<T>, dl_nb(), pr.P, pr.L, (T)c1, (T)c2, (const T*)dl_gp, (const T*)x, (const T*)dl_gl, (const T*)dl, (const T*)snap_ps, (const T*)snap_lm, ps, theta, lmrec);
         launch_chi2(lm_red);
         const T* h = nullptr;
-        if (int rc = dl_fetch(lm_red, (size_t)nbP, &h, after)) return rc;
-        double v = 0;
-        for (int k = 0; k < nbP; ++k) v += (double)h[k];
-        *chi2_trial = v;
+        if (int rc = fetch_partials(lm_red, (size_t)nbP, &h, after)) return rc;
+        *chi2_trial = sum_partials(h, 0, nbP);
         return 0;
-    }
-    // Step timing as end_step_timing / flush_step_timing keep it, with one difference: a trial that reused a solve recorded evc[2] and
-    // evc[3] alone and adds to ms_update alone.
-    bool dl_pending_solved = false;
-    int dl_add_times(hipEvent_t* e, bool solved, tsgo_stats& s) {
-        float ms = 0;
-        if (solved) {
-            HIP_OK(hipEventElapsedTime(&ms, e[0], e[1])); s.ms_linearize += ms;
-            HIP_OK(hipEventElapsedTime(&ms, e[1], e[2])); s.ms_solve += ms;
-        }
-        HIP_OK(hipEventElapsedTime(&ms, e[2], e[3])); s.ms_update += ms;
-        return 0;
-    }
-    int dl_end_timing(bool solved, tsgo_stats& s) {
-        if (!reports()) {
-            HIP_OK(hipEventRecord(evc[3], stream));
-            HIP_OK(hipEventSynchronize(evc[3]));
-            return dl_add_times(evc, solved, s);
-        }
-        if (ev_pending) { if (int rc = dl_add_times(ev_pending, dl_pending_solved, s)) return rc; }
-        ev_pending = evc; dl_pending_solved = solved; evc = evc == ev ? ev_b : ev;
-        return 0;
-    }
-    int dl_flush_timing(tsgo_stats& s) {
-        hipEvent_t* e = ev_pending;
-        ev_pending = nullptr; evc = ev;
-        if (!e) return 0;
-        HIP_OK(hipEventSynchronize(e[3]));      // (it stands right behind a report that has arrived)
-        return dl_add_times(e, dl_pending_solved, s);
     }
 
     // The loop.  need_solve: at the start and after every accepted step; a rejected trial leaves the linearisation, d_gn and the scalars
-    // in place for the next one.
+    // in place for the next one.  Step timing (end_step_timing): a trial that reused a solve recorded evc[2] and evc[3] alone and adds to
+    // ms_update alone.
     int dogleg_loop(int iterations, tsgo_stats& s) {
         if (int rc = report_prepare()) return rc;      // the slot -> edge maps of the once-per-edge walk
         tsgo_dogleg_trace& tr = dl_trace;
@@ -146,8 +97,8 @@
                 if (int rc = do_solve(&cg, &fail)) return rc;
                 s.pcg_iters_total += cg;
                 if (fail != 0) {
-                    if (traced) { s.chi2[it] = err; s.pcg_iters[it] = cg; tr.solved[it] = 1; tr.radius[it] = radius; }
-                    s.chi2_last = err; s.iterations_run = it + 1; s.trace_len = std::min(it + 1, TSGO_MAX_TRACE);
+                    note_linearisation(s, it, err);
+                    if (traced) { s.pcg_iters[it] = cg; tr.solved[it] = 1; tr.radius[it] = radius; }
                     tr.trials = it + 1; ++tr.solves;
                     s.stop_reason = TSGO_STOP_SOLVER;
                     break;
@@ -157,17 +108,17 @@
                 need_solve = false;
             }
             HIP_OK(hipEventRecord(evc[2], stream));
-            s.chi2_last = err; s.iterations_run = it + 1; s.trace_len = std::min(it + 1, TSGO_MAX_TRACE);
+            note_linearisation(s, it, err);
             tr.trials = it + 1;
             if (traced) {
-                s.chi2[it] = err; s.pcg_iters[it] = cg;
+                s.pcg_iters[it] = cg;
                 tr.solved[it] = solved ? 1 : 0; tr.radius[it] = radius; tr.gg[it] = q.gg; tr.gHg[it] = q.ghg; tr.gd[it] = q.gd; tr.dd[it] = q.dd;
             }
             if (q.gg == 0) {      // a stationary point: no step (kind 0, zero step, pred and gain)
                 if (traced) s.lm_chi2_trial[it] = err;
                 s.last_delta_norm = 0;
                 if (reports()) HIP_OK(hipEventRecord(evc[3], stream));      // (no trial closes this set)
-                if (int rc = dl_end_timing(solved, s)) return rc;
+                if (int rc = end_step_timing(s, solved)) return rc;
                 s.stop_reason = TSGO_STOP_CONVERGED;
                 break;
             }
@@ -186,15 +137,14 @@
             const double step_norm = std::sqrt(c1 * c1 * q.gg + 2 * c1 * c2 * q.gd + c2 * c2 * q.dd);
             double trial = 0;
             if (int rc = dl_trial(c1, c2, &trial, step_end_event())) return rc;
-            if (int rc = dl_end_timing(solved, s)) return rc;
-            const double gain = pred != 0 ? (err - trial) / pred : 0.0;
+            if (int rc = end_step_timing(s, solved)) return rc;
+            const double gain = note_trial(s, it, err, pred, trial);
             s.last_delta_norm = step_norm;
-            if (traced) { s.lm_pred[it] = pred; s.lm_chi2_trial[it] = trial; s.lm_gain[it] = gain; tr.kind[it] = kind; tr.step_norm[it] = step_norm; }
-            const bool accepted = gain > 0 && pred > 0;      // (a NaN anywhere fails both tests: rejected)
+            if (traced) { tr.kind[it] = kind; tr.step_norm[it] = step_norm; }
             if (!(gain >= 0.25)) radius = 0.25 * step_norm;
             else if (gain > 0.75 && kind != 0) radius = std::min(2 * radius, dogleg.radius_max);
             tr.radius_last = radius;
-            if (accepted) {
+            if (accepted(gain, pred)) {
                 if (step_norm < kDeltaTol || err - trial <= dogleg.chi2_rel_tol * err) { s.stop_reason = TSGO_STOP_CONVERGED; break; }
                 need_solve = true;
             } else {
@@ -203,5 +153,5 @@
                 if (!(radius >= dogleg.radius_min)) { s.stop_reason = TSGO_STOP_RADIUS; break; }
             }
         }
-        return dl_flush_timing(s);
+        return flush_step_timing(s);
     }

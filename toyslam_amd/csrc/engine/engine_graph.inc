@@ -330,15 +330,14 @@
         HIP_OK(hipHostMalloc((void**)&h_state, sizeof(CgState<T>)));
         HIP_OK(hipHostMalloc((void**)&h_flag, 16 * sizeof(int), hipHostMallocCoherent));
         std::memset(h_flag, 0, 16 * sizeof(int));
-        HIP_OK(hipHostMalloc((void**)&h_scratch, sizeof(T) * (size_t)(std::max(nbP, 2 * nbC) + nbL + 8)));
-        if (int rc = rep_reserve(std::max({(size_t)nbP, (size_t)nbC + nbL, trial_rules() ? lm_red_size() : (size_t)0, dogleg_rules() ? dl_red_size() : (size_t)0}))) return rc;
+        HIP_OK(hipHostMalloc((void**)&h_scratch, sizeof(T) * partials_max()));
+        if (int rc = rep_reserve(partials_max())) return rc;
         snap_ps = snap_theta = snap_lm = lm_red = nullptr;
         if (trial_rules()) {
             if (int rc = dalloc(&snap_ps, (size_t)P * 4)) return rc;
             if (int rc = dalloc(&snap_theta, (size_t)P)) return rc;
             if (int rc = dalloc(&snap_lm, (size_t)std::max(L, 1) * 2)) return rc;
             if (int rc = dalloc(&lm_red, lm_red_size())) return rc;
-            HIP_OK(hipHostMalloc((void**)&h_lm, sizeof(T) * std::max(lm_red_size(), dogleg_rules() ? dl_red_size() : (size_t)0)));
         }
         dl_gp = dl_gl = dl_red = nullptr;
         if (dogleg_rules()) { if (int rc = dl_alloc()) return rc; }

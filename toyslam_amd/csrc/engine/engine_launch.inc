@@ -145,6 +145,14 @@
                                               T(0), dl, npart, lo ? (const float*)zc32 : nullptr, lo ? tvec32 : nullptr, ga, T(0), (T*)nullptr);
         }); });
     }
+    // The landmark pass as the back-substitution: dl = u - Dl^-1 W^T x, the update by `step`, |dl|^2 partials at norm_out (MODE 1: do_backsub_update,
+    // dl_after_solve); MODE 2 (do_lm_step) also leaves the landmarks' predicted decrease under lam at pred_out
+    template <int MODE> void launch_backsub(T step, T* norm_out, T lam, T* pred_out) {
+        if (tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
+            launch_table(k_schur_lm<T, g, MODE, 0>, nbL, tl, 0, st[0], (const T*)ninv, (const T*)nullptr, (const T*)nullptr, tl, (const T*)zc, lmrec, tvec, step, dl, norm_out, (const float*)nullptr, (float*)nullptr, no_gate(), lam,
+                         pred_out);
+        });
+    }
     void launch_schur_pose(int slot, bool low, const T* rvec, T* rz_part, bool post_smooth, bool as_residual, const char* wh) {
         pick<1, 2, 4, 8>(pr.by_pose.G, [&](auto g) { pick<0, 1>(low, [&](auto lo) { pick<0, 1>(oj(), [&](auto general) {
             PF(bytes_schur_pose(lo) + (post_smooth ? pr.P * (6 + 3 + 3 + 3) * (double)sizeof(T) : 0.0), post_smooth ? "in-cycle product + post-smoothing L0" : wh, "k_schur_pose", tname(), g, lo, general);

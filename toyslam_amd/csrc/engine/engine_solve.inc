@@ -24,6 +24,25 @@
         }
         return 0;
     }
+    // The most partials one fetch brings back: the report buffer and the copy path's pinned destination (h_scratch) are both sized by it.
+    size_t partials_max() const { return std::max({(size_t)nbP, (size_t)nbC + nbL, trial_rules() ? lm_red_size() : (size_t)0, dogleg_rules() ? dl_red_size() : (size_t)0}); }
+    // n partials at src to the host, *h.  Step reports: the report is launched here, unless the caller `sent` it earlier in the chain
+    // (do_linearize), and `after`, a step's closing event, is recorded right behind it.  Otherwise copy + synchronise into h_scratch.
+    int fetch_partials(const T* src, size_t n, const T** h, hipEvent_t after = nullptr, uint64_t sent = 0) {
+        if (reports()) {
+            const uint64_t rseq = sent ? sent : launch_report(src, n);
+            if (after) HIP_OK(hipEventRecord(after, stream));
+            if (int rc = wait_report(rseq)) return rc;
+            *h = rep_data();
+        } else {
+            HIP_OK(hipMemcpyAsync(h_scratch, src, sizeof(T) * n, hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipStreamSynchronize(stream));
+            *h = h_scratch;
+        }
+        return 0;
+    }
+    // ... and their sum: in double, ascending from `from`
+    static double sum_partials(const T* h, size_t from, int count) { double v = 0; for (int k = 0; k < count; ++k) v += (double)h[from + k]; return v; }
     // one linearisation; chi2 on the host
     int do_linearize(double* chi2) {
         launch_lin();
@@ -33,9 +52,8 @@
         // and the solve's first launches queue up behind them.  Ahead of a burst or a replay it leaves at the end of the chain, so that the
         // host goes on when the stream is empty, as it does after a copy + synchronise: those paths time their solves by the wall clock
         // (do_solve_once: dev_us_per_iter) and must keep seeing the solve alone.
-        const bool report = reports(), early = report && paced();
-        uint64_t rseq = 0;
-        if (early) rseq = launch_report(part + (size_t)pr.P * 18, (size_t)nbP);
+        const T* chi_part = part + (size_t)pr.P * 18;
+        const uint64_t early = reports() && paced() ? launch_report(chi_part, (size_t)nbP) : 0;
         launch_finalize();
         if (amg_on) {
             // The Galerkin hierarchy is a preconditioner, not the operator: level 0 (the Schur products, its diagonal
@@ -56,18 +74,9 @@
                 }
             }
         }
-        const T* h = h_scratch;
-        if (report) {
-            if (!early) rseq = launch_report(part + (size_t)pr.P * 18, (size_t)nbP);
-            if (int rc = wait_report(rseq)) return rc;
-            h = rep_data();
-        } else {
-            HIP_OK(hipMemcpyAsync(h_scratch, part + (size_t)pr.P * 18, sizeof(T) * nbP, hipMemcpyDeviceToHost, stream));
-            HIP_OK(hipStreamSynchronize(stream));
-        }
-        double s = 0;
-        for (int k = 0; k < nbP; ++k) s += (double)h[k];
-        *chi2 = s;
+        const T* h = nullptr;
+        if (int rc = fetch_partials(chi_part, (size_t)nbP, &h, nullptr, early)) return rc;
+        *chi2 = sum_partials(h, 0, nbP);
         return 0;
     }
 
@@ -327,39 +336,26 @@
         else launch_save_x(w, hist[0], warm_err);
         mem.n_tested = w.n_max; mem.have_prev = true; mem.n_prev = std::min(mem.n_prev + 1, kMaxWarm);
     }
+    // ... or the solved delta enters nothing (a probe, a trial's full step): k_pack_x without a history, and the history is forgotten
+    void forget_warm_history() {
+        launch_pack_x(WarmTerms<T>{}, (int*)nullptr);
+        mem.have_prev = false; mem.n_prev = 0; mem.n_tested = 0;
+    }
 
     // landmarks: dl = u - Dl^-1 W^T x (+ optional update); poses: update.  Returns ||delta_p||^2 (identical on every
     // rank: pose vectors are replicated) and THIS rank's ||delta_l||^2 (landmark deltas are shard-local).
     // Step reports (one-shard handles): a step that is taken runs k_save_x and k_pose_update as ONE launch in front of the landmark pass (which
     // reads zc and lmrec, neither ps nor theta), the partials come back through k_report, and `after` (the step's closing event) is recorded behind it.
     int do_backsub_update(T step, double* np2_out, double* nl2_local_out, hipEvent_t after = nullptr) {
-        const int P = pr.P;
-        const bool report = reports(), fused = report && step != T(0);
-        if (step != T(0)) {
-            record_delta(fused, step);
-        } else {      // a probe (step 0) leaves nothing to carry over
-            launch_pack_x(WarmTerms<T>{}, (int*)nullptr);
-            mem.have_prev = false; mem.n_prev = 0; mem.n_tested = 0;
-        }
-        if (tl.n_slices > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
-            launch_table(k_schur_lm<T, g, 1, 0>, nbL, tl, 0, st[0], (const T*)ninv, (const T*)nullptr, (const T*)nullptr, tl, (const T*)zc, lmrec, tvec, step, dl, npart + nbC, (const float*)nullptr, (float*)nullptr, no_gate(), T(0), (T*)nullptr);
-        });
-        if (!fused) hipLaunchKernelGGL((k_pose_update<T>), dim3(nbC), dim3(kBlock), 0, stream, P, x, ps, theta, step, npart);
-        const int nl = tl.n_slices > 0 ? nbL : 0;
-        const T* h = h_scratch;
-        if (report) {
-            const uint64_t rseq = launch_report(npart, (size_t)(nbC + nl));
-            if (after) HIP_OK(hipEventRecord(after, stream));
-            if (int rc = wait_report(rseq)) return rc;
-            h = rep_data();
-        } else {
-            HIP_OK(hipMemcpyAsync(h_scratch, npart, sizeof(T) * (size_t)(nbC + nl), hipMemcpyDeviceToHost, stream));
-            HIP_OK(hipStreamSynchronize(stream));
-        }
-        double np2 = 0, nl2 = 0;
-        for (int k = 0; k < nbC; ++k) np2 += (double)h[k];
-        for (int k = 0; k < nl; ++k) nl2 += (double)h[nbC + k];
-        *np2_out = np2; *nl2_local_out = nl2;
+        const bool fused = reports() && step != T(0);
+        if (step != T(0)) record_delta(fused, step);
+        else forget_warm_history();      // a probe (step 0) leaves nothing to carry over
+        launch_backsub<1>(step, npart + nbC, T(0), nullptr);
+        if (!fused) hipLaunchKernelGGL((k_pose_update<T>), dim3(nbC), dim3(kBlock), 0, stream, pr.P, x, ps, theta, step, npart);
+        const int nl = lm_nl();
+        const T* h = nullptr;
+        if (int rc = fetch_partials(npart, (size_t)(nbC + nl), &h, after)) return rc;
+        *np2_out = sum_partials(h, 0, nbC); *nl2_local_out = sum_partials(h, (size_t)nbC, nl);
         return 0;
     }
     // Sum of the ranks' landmark-delta norms.  The stop rule ||delta|| < 1e-3 (OptimizerCpu.h:173) can only fire when the
@@ -381,62 +377,68 @@
     static constexpr double kLmLambdaMin = 1e-9, kLmLambdaMax = 1e9;
     int lm_nl() const { return tl.n_slices > 0 ? nbL : 0; }
     size_t lm_red_size() const { return (size_t)2 * (nbC + std::max(nbL, 1)) + nbP; }
-    // The tentative full step of a trial and everything the decision needs, in one chain of launches and ONE copy back: snapshot of the
+    // The tentative full step of a trial and everything the decision needs, in one chain of launches and ONE fetch: snapshot of the
     // estimates, back-substitution + update with step 1 (the landmarks' predicted decrease in the same pass, k_schur_lm<.., 2>; the poses'
     // in k_pose_update_lm), chi^2 at the trial point (k_chi2).  Nothing of the step enters the warm start's history: a full step leaves
     // no remainder to start from, and a rejected one must leave nothing at all.
     int do_lm_step(double lam, double* np2, double* nl2, double* pred, double* chi2_trial, hipEvent_t after = nullptr) {
-        const int P = pr.P, L = pr.L, nl = lm_nl();
+        const int nl = lm_nl();
         T* norm_p = lm_red; T* norm_l = lm_red + nbC; T* pred_p = norm_l + nl; T* pred_l = pred_p + nbC; T* chi = pred_l + nl;
-        launch(k_lm_state<T, 0>, grid_for(std::max(P, L)), P, L, ps, theta, lmrec, snap_ps, snap_theta, snap_lm);
-        launch_pack_x(WarmTerms<T>{}, (int*)nullptr);
-        mem.have_prev = false; mem.n_prev = 0; mem.n_tested = 0;
-        if (nl > 0) pick<1, 2, 4, 8>(pr.by_lm.G, [&](auto g) {
-            launch_table(k_schur_lm<T, g, 2, 0>, nbL, tl, 0, st[0], (const T*)ninv, (const T*)nullptr, (const T*)nullptr, tl, (const T*)zc, lmrec, tvec, T(1), dl, norm_l, (const float*)nullptr, (float*)nullptr, no_gate(), (T)lam, pred_l);
-        });
-        launch(k_pose_update_lm<T>, nbC, P, (const T*)x, ps, theta, (const T*)part, (T)lam, norm_p, pred_p);
+        begin_trial();      // (under step reports too the trial keeps its own kernels: k_pack_x takes no history and k_pose_update_lm reads the gradient as well)
+        launch_backsub<2>(T(1), norm_l, (T)lam, pred_l);
+        launch(k_pose_update_lm<T>, nbC, pr.P, (const T*)x, ps, theta, (const T*)part, (T)lam, norm_p, pred_p);
         launch_chi2(chi);
-        const size_t n = (size_t)2 * (nbC + nl) + nbP;
-        const T* h = h_lm;
-        if (reports()) {      // (the trial keeps its own kernels: k_pack_x takes no history and k_pose_update_lm reads the gradient as well)
-            const uint64_t rseq = launch_report(lm_red, n);
-            if (after) HIP_OK(hipEventRecord(after, stream));
-            if (int rc = wait_report(rseq)) return rc;
-            h = rep_data();
-        } else {
-            HIP_OK(hipMemcpyAsync(h_lm, lm_red, sizeof(T) * n, hipMemcpyDeviceToHost, stream));
-            HIP_OK(hipStreamSynchronize(stream));
-        }
-        auto sum = [&](size_t from, int count) { double v = 0; for (int k = 0; k < count; ++k) v += (double)h[from + k]; return v; };
-        *np2 = sum(0, nbC); *nl2 = sum(nbC, nl);
-        *pred = sum((size_t)nbC + nl, nbC) + sum((size_t)2 * nbC + nl, nl);
-        *chi2_trial = sum((size_t)2 * (nbC + nl), nbP);
+        const T* h = nullptr;
+        if (int rc = fetch_partials(lm_red, (size_t)2 * (nbC + nl) + nbP, &h, after)) return rc;
+        *np2 = sum_partials(h, 0, nbC); *nl2 = sum_partials(h, (size_t)nbC, nl);
+        *pred = sum_partials(h, (size_t)nbC + nl, nbC) + sum_partials(h, (size_t)2 * nbC + nl, nl);
+        *chi2_trial = sum_partials(h, (size_t)2 * (nbC + nl), nbP);
         return 0;
+    }
+    // A trial (rules 2 and 3) starts from a snapshot of the estimates, which lm_restore puts back, and leaves nothing in the warm start's history
+    void begin_trial() {
+        launch(k_lm_state<T, 0>, grid_for(std::max(pr.P, pr.L)), pr.P, pr.L, ps, theta, lmrec, snap_ps, snap_theta, snap_lm);
+        forget_warm_history();
     }
     int lm_restore() {
         launch(k_lm_state<T, 1>, grid_for(std::max(pr.P, pr.L)), pr.P, pr.L, ps, theta, lmrec, snap_ps, snap_theta, snap_lm);
         return 0;
     }
-    int add_step_times(hipEvent_t* e, tsgo_stats& s) {
+    // What every loop files per linearisation and per trial (the trial's gain ratio is returned), and the acceptance test of rules 2 and 3
+    static void note_linearisation(tsgo_stats& s, int it, double err) {
+        if (it < TSGO_MAX_TRACE) s.chi2[it] = err;
+        s.chi2_last = err;
+        s.iterations_run = it + 1; s.trace_len = std::min(it + 1, TSGO_MAX_TRACE);
+    }
+    static double note_trial(tsgo_stats& s, int it, double err, double pred, double trial) {
+        const double gain = pred != 0 ? (err - trial) / pred : 0.0;
+        if (it < TSGO_MAX_TRACE) { s.lm_pred[it] = pred; s.lm_chi2_trial[it] = trial; s.lm_gain[it] = gain; }
+        return gain;
+    }
+    static bool accepted(double gain, double pred) { return gain > 0 && pred > 0; }      // (a NaN anywhere fails both tests: rejected)
+    // A step that ran no linearisation and no solve (solved = false: a dogleg trial that reused a solve) recorded e[2] and e[3] alone
+    int add_step_times(hipEvent_t* e, bool solved, tsgo_stats& s) {
         float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, e[0], e[1])); s.ms_linearize += ms;
-        HIP_OK(hipEventElapsedTime(&ms, e[1], e[2])); s.ms_solve += ms;
+        if (solved) {
+            HIP_OK(hipEventElapsedTime(&ms, e[0], e[1])); s.ms_linearize += ms;
+            HIP_OK(hipEventElapsedTime(&ms, e[1], e[2])); s.ms_solve += ms;
+        }
         HIP_OK(hipEventElapsedTime(&ms, e[2], e[3])); s.ms_update += ms;
         return 0;
     }
     // evc[0..2] stand before a step's linearisation, solve and update.  Copy + synchronise: closes the update, waits, adds the device times.
-    // Step reports: evc[3] already stands behind the report the host has seen (do_backsub_update / do_lm_step), and no second wait is
+    // Step reports: evc[3] already stands behind the report the host has seen (fetch_partials: `after`), and no second wait is
     // spent on it: the set is read at the end of the NEXT step, when its events lie a whole step back in the stream, while that step
     // records the other set; the last step's set is read by flush_step_timing, once per tsgo_optimize.
     hipEvent_t step_end_event() const { return reports() ? evc[3] : (hipEvent_t) nullptr; }
-    int end_step_timing(tsgo_stats& s) {
+    int end_step_timing(tsgo_stats& s, bool solved = true) {
         if (!reports()) {
             HIP_OK(hipEventRecord(evc[3], stream));
             HIP_OK(hipEventSynchronize(evc[3]));
-            return add_step_times(evc, s);
+            return add_step_times(evc, solved, s);
         }
-        if (ev_pending) { if (int rc = add_step_times(ev_pending, s)) return rc; }
-        ev_pending = evc; evc = evc == ev ? ev_b : ev;
+        if (ev_pending) { if (int rc = add_step_times(ev_pending, pending_solved, s)) return rc; }
+        ev_pending = evc; pending_solved = solved; evc = evc == ev ? ev_b : ev;
         return 0;
     }
     int flush_step_timing(tsgo_stats& s) {
@@ -444,7 +446,7 @@
         ev_pending = nullptr; evc = ev;
         if (!e) return 0;
         HIP_OK(hipEventSynchronize(e[3]));      // (it stands right behind a report that has arrived)
-        return add_step_times(e, s);
+        return add_step_times(e, pending_solved, s);
     }
     // The loop.  One trial = linearise (H + lambda I, b zeroed at fixed vertices), solve, tentative full step, decide; a rejected trial is
     // followed by a fresh linearisation at the restored point: lambda is baked into the landmark inverses and the pose diagonals.
@@ -457,9 +459,9 @@
             if (int rc = do_linearize(&err)) return rc;
             HIP_OK(hipEventRecord(evc[1], stream));
             const bool traced = it < TSGO_MAX_TRACE;
-            if (traced) { s.chi2[it] = err; s.lm_lambda[it] = lam; }
-            s.chi2_last = err; s.lambda_last = lam;
-            s.iterations_run = it + 1; s.trace_len = std::min(it + 1, TSGO_MAX_TRACE);
+            note_linearisation(s, it, err);
+            if (traced) s.lm_lambda[it] = lam;
+            s.lambda_last = lam;
             int cg = 0, fail = 0;
             if (int rc = do_solve(&cg, &fail)) return rc;
             HIP_OK(hipEventRecord(evc[2], stream));
@@ -470,9 +472,8 @@
             if (int rc = do_lm_step(lam, &np2, &nl2, &pred, &trial, step_end_event())) return rc;
             if (int rc = end_step_timing(s)) return rc;
             s.last_delta_norm = std::sqrt(np2 + nl2);
-            const double gain = pred != 0 ? (err - trial) / pred : 0.0;
-            if (traced) { s.lm_pred[it] = pred; s.lm_chi2_trial[it] = trial; s.lm_gain[it] = gain; }
-            if (gain > 0 && pred > 0) {      // (a NaN anywhere fails both tests: rejected)
+            const double gain = note_trial(s, it, err, pred, trial);
+            if (accepted(gain, pred)) {
                 const double t = 2 * gain - 1;
                 lam = std::min(std::max(lam * std::max(1.0 / 3.0, 1 - t * t * t), kLmLambdaMin), kLmLambdaMax); nu = 2;
                 if (s.last_delta_norm < kDeltaTol || err - trial <= cfg.lm_chi2_rel_tol * err) { s.stop_reason = TSGO_STOP_CONVERGED; break; }
@@ -510,9 +511,7 @@
                 if (int rc = do_linearize(&err)) return rc;
             }
             HIP_OK(hipEventRecord(evc[1], stream));
-            if (it < TSGO_MAX_TRACE) s.chi2[it] = err;
-            s.chi2_last = err;
-            s.iterations_run = it + 1; s.trace_len = std::min(it + 1, TSGO_MAX_TRACE);
+            note_linearisation(s, it, err);
             if (!py_rules()) {
                 if (prevErr > 0 && err > prevErr) {                          // OptimizerCpu.h:140-153
                     if (++penalty > 2) { s.stop_reason = TSGO_STOP_WORSE; break; }

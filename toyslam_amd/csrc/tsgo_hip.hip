@@ -295,16 +295,16 @@ template <typename T> struct Engine : IEngine {
     CgState<T>* st[2] = {nullptr, nullptr};
     CgState<T>* h_state = nullptr;     // pinned
     int* h_flag = nullptr;             // pinned, coherent: what the gate of the last launched iteration saw (k_iter_gate, do_solve_paced)
-    T* h_scratch = nullptr;            // pinned, partial sums
+    T* h_scratch = nullptr;            // pinned, partials_max() of them: where fetch_partials copies to when there are no step reports
     // Step reports (one-shard handles; k_report, engine_solve.inc: wait_report): the device stores chi^2 / ||delta|| partials into h_rep
     // and then a sequence number into its first word; the host thread polls that word instead of draining the stream.  Pinned, coherent;
     // one cache line for the word, the partials behind it.  Sized by the largest graph the handle has seen, freed with the handle.
     uint64_t* h_rep = nullptr; size_t rep_cap = 0;
     static constexpr size_t kRepHead = 64 / sizeof(T);      // the word's cache line, in elements of T
     T* rep_data() const { return reinterpret_cast<T*>(h_rep) + kRepHead; }
-    // rules = 2 only (null otherwise): the estimates before a trial's step (k_lm_state), and the partials one trial brings back in one copy:
-    // lm_red = [ |d_p|^2 (nbC) | |d_l|^2 (nbL) | pred, poses (nbC) | pred, landmarks (nbL) | chi^2 at the trial point (nbP) ], h_lm its pinned twin
-    T *snap_ps = nullptr, *snap_theta = nullptr, *snap_lm = nullptr, *lm_red = nullptr, *h_lm = nullptr;
+    // rules = 2 and 3 only (null otherwise): the estimates before a trial's step (k_lm_state), and the partials one trial brings back in one fetch:
+    // lm_red = [ |d_p|^2 (nbC) | |d_l|^2 (nbL) | pred, poses (nbC) | pred, landmarks (nbL) | chi^2 at the trial point (nbP) ] (rules = 3: the last alone, in front)
+    T *snap_ps = nullptr, *snap_theta = nullptr, *snap_lm = nullptr, *lm_red = nullptr;
     int nbP = 0, nbL = 0, nbC = 0;
     bool fuse_post_smooth = true;      // the level-0 post-smoothing in the epilogue of the cycle's second product (research: TSGO_FUSE_POST=0 = k_smooth0)
     double hier_shift_cfg = 0;         // the hier_shift a graph starts with (0; research: TSGO_HIER_SHIFT)
@@ -313,6 +313,7 @@ template <typename T> struct Engine : IEngine {
     // step reports: a second set, so that a step's device times are read while the next step runs (end_step_timing); evc = the set being recorded
     hipEvent_t ev_b[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t* evc = ev; hipEvent_t* ev_pending = nullptr;
+    bool pending_solved = true;        // ... and whether the pending set's step linearised and solved (a dogleg trial that reused a solve did not)
     static constexpr int kDecideSolves = 3;
     bool replayed = false;             // the last tsgo_optimize replayed captured iterations (tsgo_stats.graph_replay)
     // ---- What the solver learns while it runs has one of three lifetimes; a new member goes into one of the three groups.
@@ -474,7 +475,6 @@ template <typename T> struct Engine : IEngine {
         if (h_state) { (void)hipHostFree(h_state); h_state = nullptr; }
         if (h_flag) { (void)hipHostFree(h_flag); h_flag = nullptr; }
         if (h_scratch) { (void)hipHostFree(h_scratch); h_scratch = nullptr; }
-        if (h_lm) { (void)hipHostFree(h_lm); h_lm = nullptr; }
         if (h_rho) { (void)hipHostFree(h_rho); h_rho = nullptr; }
         have_graph_data = false;
     }
