@@ -453,6 +453,41 @@ int tsgo_sample_marginals(tsgo_optimizer* opt, int32_t n_samples, uint64_t seed,
 void tsgo_sample_noise(uint64_t seed, uint32_t tag, uint32_t index, uint32_t sample,
                        uint32_t words_out[4] /* may be NULL */, double normals_out[4] /* may be NULL */);
 
+/* Leverage of EVERY edge in the graph from posterior samples: "how much does the map rest on each edge?".  With
+ * Sigma = H^-1, C_e = J_e Sigma J_e^T is the covariance of the predicted measurement of edge e and h_e = tr(Omega_a C_e), in [0, dof], its
+ * leverage; dof - h_e is its redundancy.  An edge with h near dof cannot be checked by any residual test: the estimate follows it.
+ * H, the Jacobians J_e = [A | B], the weights a = w inf (w the robust weight of the edge's effective kernel: its class's, tsgo_set_robust,
+ * or its own, tsgo_set_edge_robust) and the samples delta_k are those of tsgo_sample_marginals for the same (seed, k): a call with the
+ * same seed and n_samples sees bit for bit the delta_k that tsgo_sample_marginals stages in samples_out.  ODOM edges use the handle's
+ * odom_jacobian (under 0 that is -I / +I, the J that built H; with another J the trace identity below would fail).  Per sample and edge
+ * y = A delta_first + B delta_second (a prior edge: y = A delta), and the record of edge e, 8 doubles at rec_out[8 e] in the edge order of
+ * the tsgo_graph, is (c00, c01, c02, c11, c12, c22, h, dof_a):
+ *   C      = (1 / K) sum_k y y^T — the mean is 0, so no K - 1; for the dof-2 classes (LM, virtual landmark, landmark prior) c02 = c12 = c22 = 0 exactly
+ *   h      = sum_j a_j C_jj
+ *   dof_a  = the number of axes the class uses with a_j > 0.  An edge with zero information has h = 0 and dof_a = 0; its C is still reported.
+ * dof_a - h may be slightly negative: that is sampling noise and it is not clamped.  A diagonal entry of C has relative standard error
+ * sqrt(2 / K).  For a few edges exactly, hand them to tsgo_gate_edges as candidates with innov_out: it returns S = C + Omega^-1.
+ * stats (folded on the host in f64, in input edge order, from the records): per edge class the count, the sum of h and the sum of dof_a;
+ * h_gauge = sum over vertices of gamma_v tr(C_v), C_v = (1 / K) sum_k delta_v delta_v^T from the accumulators of the sampling path,
+ * gamma_v = 1e6 x occurrences in the fixed list; trace = h_sum[0 .. 4] added in class order, + h_gauge, whose expectation is the number of
+ * unknowns 3 P + 2 L (tr(H Sigma) = n; with the same samples it equals (1 / K) sum_k delta_k^T H delta_k up to rounding).
+ * State rule, determinism and refusals are those of tsgo_sample_marginals: nothing the next tsgo_optimize reads changes; the same call
+ * twice gives the same bits; precision = 64 and world == 1 only; a fixed vertex or a full pose prior is required; n_samples in [1, 65536];
+ * plus rec_out == NULL and cap_edges < n_edges.  Everything is validated before anything is launched and the handle stays usable. */
+typedef struct tsgo_leverage_stats {
+    int32_t samples, reserved;
+    int64_t edges[5];                       /* per tsgo_graph.e_type */
+    double  h_sum[5], dof_sum[5];           /* sum of h_e, sum of dof_a, per class */
+    double  h_gauge;                        /* sum over vertices of gamma_v tr(C_v) */
+    double  trace;                          /* h_sum[0 .. 4] folded in class order, + h_gauge; expectation = unknowns */
+    int64_t unknowns;                       /* 3 P + 2 L */
+    tsgo_marginal_stats solve;              /* as tsgo_sample_stats.solve */
+    double ms_total, ms_noise, ms_readout;  /* as tsgo_sample_stats; ms_readout includes the leverage kernels */
+} tsgo_leverage_stats;
+int tsgo_edge_leverage(tsgo_optimizer* opt, int32_t n_samples, uint64_t seed, double rel_tol,
+                       double* rec_out /* 8 per edge, input order */, int64_t cap_edges,
+                       tsgo_leverage_stats* stats /* may be NULL */);
+
 /* Per-edge residual report: which edges the robust kernels down-weighted, and by how much (what g2o's per-edge chi2() and Ceres' residual
  * evaluation answer).  Everything is evaluated at the handle's CURRENT estimates under its current tsgo_set_robust setting, by the edge
  * functions every linearisation runs; odom_jacobian, rules, damping and the fixed list do not enter.  rec_out receives six doubles per edge,
@@ -597,7 +632,7 @@ int tsgo_get_edge_information(tsgo_optimizer* opt, double* e_inf_out, int64_t ca
  * gauge arrays and nothing else on the device: the estimates keep their bits.
  *   The canonical list: afterwards the handle's fixed list is the vertices with count > 0 in tsgo_graph vertex order, each repeated count
  *   times, and every reader sees it — the linearisation, tsgo_init_estimates (its breadth-first sources and the landmarks it leaves alone),
- *   and the "is H regular" check of tsgo_marginals, tsgo_joint_marginals, tsgo_gate_edges and tsgo_sample_marginals.  Every later call
+ *   and the "is H regular" check of tsgo_marginals, tsgo_joint_marginals, tsgo_gate_edges, tsgo_sample_marginals and tsgo_edge_leverage.  Every later call
  *   behaves, bit for bit where the same kernels see the same inputs, as a fresh handle given the same graph with that list.  Releasing
  *   every fixed vertex is legal: the result is what tsgo_set_graph makes of n_fixed = 0, and tsgo_marginals then refuses as it does there.
  *   Solver state: the rule of tsgo_set_edge_information.  The next linearisation builds a fresh multigrid hierarchy; the warm start's

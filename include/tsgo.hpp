@@ -245,6 +245,18 @@ public:
         return cov;
     }
 
+    // Leverage of every edge from posterior samples (tsgo_edge_leverage): eight doubles per edge of the graph last handed to Optimize or
+    // SetGraph, in its edge order: (c00, c01, c02, c11, c12, c22, h, dof_a) — C = J Sigma J^T of the predicted measurement, h = tr(Omega_a C),
+    // the number of weighted axes; the redundancy is dof_a - h.  Estimated from n_samples samples (relative standard error
+    // sqrt(2 / n_samples) on a diagonal entry of C).  *stats (if given): the per-class sums and the trace.  Throws on an error (those of
+    // SampleMarginals).
+    std::vector<double> EdgeLeverage(size_t n_edges, int n_samples, uint64_t seed = 0, tsgo_leverage_stats* stats = nullptr) {
+        std::vector<double> rec(n_edges * 8);
+        double none[8];
+        if (tsgo_edge_leverage(handle, n_samples, seed, 0.0, rec.empty() ? none : rec.data(), (int64_t)n_edges, stats)) throw std::runtime_error(tsgo_last_error());
+        return rec;
+    }
+
     // Per-edge residual report at the current estimates (tsgo_edge_report): six doubles per edge of the graph last handed to Optimize, in
     // its edge order: (e0, e1, e2, s, rho, w); *stats (if given) receives the per-class summary.  EdgeSummary: the summary alone (no per-edge
     // buffer anywhere).  Both throw on an error (no graph yet, an edge-sharded handle).

@@ -77,6 +77,12 @@ class tsgo_sample_stats(C.Structure):
                 ("ms_total", C.c_double), ("ms_noise", C.c_double), ("ms_readout", C.c_double)]
 
 
+class tsgo_leverage_stats(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("reserved", C.c_int32), ("edges", C.c_int64 * 5), ("h_sum", C.c_double * 5), ("dof_sum", C.c_double * 5),
+                ("h_gauge", C.c_double), ("trace", C.c_double), ("unknowns", C.c_int64), ("solve", tsgo_marginal_stats),
+                ("ms_total", C.c_double), ("ms_noise", C.c_double), ("ms_readout", C.c_double)]
+
+
 class tsgo_init_stats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("poses_set", "landmarks_set", "roots_fixed", "roots_free", "edges_usable", "tree_edges", "landmarks_unobserved")] + \
                [("depth_max", C.c_int32), ("rounds", C.c_int32), ("ms_total", C.c_double), ("ms_tree", C.c_double), ("ms_device", C.c_double)]
@@ -166,7 +172,7 @@ DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_
                   "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
                   "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust", "tsgo_edge_report", "tsgo_gate_edges", "tsgo_init_estimates",
                   "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc", "tsgo_sample_marginals", "tsgo_set_dogleg", "tsgo_get_dogleg", "tsgo_get_dogleg_trace",
-                  "tsgo_set_edge_robust", "tsgo_get_edge_robust", "tsgo_set_fixed", "tsgo_get_fixed", "tsgo_set_estimates"]
+                  "tsgo_set_edge_robust", "tsgo_get_edge_robust", "tsgo_set_fixed", "tsgo_get_fixed", "tsgo_set_estimates", "tsgo_edge_leverage"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply",
                    "tsgo_testing_sym_scan", "tsgo_testing_sym_product", "tsgo_testing_schur_pattern", "tsgo_testing_lane_sums", "tsgo_testing_warm_start"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
@@ -219,6 +225,7 @@ def _declare_device(L):
     L.tsgo_marginals.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.POINTER(tsgo_marginal_stats)]
     L.tsgo_joint_marginals.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.c_int64, C.POINTER(C.c_int32), C.POINTER(tsgo_marginal_stats)]
     L.tsgo_sample_marginals.argtypes = [vp, C.c_int32, C.c_uint64, C.c_double, vp, C.c_int64, vp, C.c_int64, C.POINTER(tsgo_sample_stats)]
+    L.tsgo_edge_leverage.argtypes = [vp, C.c_int32, C.c_uint64, C.c_double, vp, C.c_int64, C.POINTER(tsgo_leverage_stats)]
     L.tsgo_set_robust.argtypes = [vp, C.POINTER(tsgo_robust)]
     L.tsgo_get_robust.argtypes = [vp, C.POINTER(tsgo_robust)]
     L.tsgo_set_edge_robust.argtypes = [vp, C.c_int32, vp, vp, C.c_int64, C.POINTER(tsgo_edge_robust_stats)]

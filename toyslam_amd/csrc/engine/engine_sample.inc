@@ -44,7 +44,10 @@
         }); });
     }
 
-    template <int NV> int sample_run(int K, uint64_t seed, double tol, double* cov, double* samples, tsgo_sample_stats& ss) {
+    // The batch driver of both sampling calls (right-hand side, solve, breakdown repeat, the vertex accumulators): tsgo_sample_marginals
+    // and tsgo_edge_leverage (engine_leverage.inc) differ in the read-out hook alone — more(B, u, nc) enqueues what a call adds behind
+    // the two accumulation kernels of a solved batch, inside the read-out's event pair.
+    template <int NV, typename More> int sample_run(int K, uint64_t seed, double tol, double* cov, double* samples, tsgo_sample_stats& ss, More&& more) {
         const int P = pr.P, L = pr.L;
         const size_t V = (size_t)pr.n_vertices;
         MbBuf B;
@@ -82,6 +85,7 @@
                 mb_lm<NV>(B.x, B.t, B.zero);      // t = Dl^-1 W^T X = Y^T X
                 launch(k_smp_acc_pose<T>, grid_for(P), P, NV, nc, (const T*)B.x, (const int*)maps.smp_pose_vertex, (int64_t)V, acc_p, stage);
                 if (L > 0) launch(k_smp_acc_lm<T>, grid_for(L), L, NV, nc, (const T*)u, (const T*)B.t, (const int*)maps.smp_lm_vertex, (int64_t)V, acc_l, stage);
+                more(B, (const T*)u, nc);
                 HIP_OK(hipGetLastError());
                 HIP_OK(hipEventRecord(er[1], stream));
                 pend_r = true;
@@ -113,16 +117,22 @@
         return 0;
     }
 
-    int sample_marginals(int n_samples, uint64_t seed, double rel_tol, double* cov, int64_t cap_vertices, double* samples, int64_t samples_cap,
-                         tsgo_sample_stats* st_out) override {
-        const auto wall0 = std::chrono::steady_clock::now();
-        const std::string nm("tsgo_sample_marginals");
-        tsgo_sample_stats ss; std::memset(&ss, 0, sizeof(ss));
+    // what both sampling calls refuse about the handle and n_samples
+    int sample_refusals(const std::string& nm, int n_samples) {
         if (sizeof(T) != 8) return set_error(-1, nm + ": needs precision = 64 (with the gauge, cond(H) is about 2e7: f32 samples would be noise)");
         if (cfg.world > 1 || collective()) return set_error(-1, nm + ": edge-sharded handles (world > 1) are not supported");
         if (!have_graph_data) return set_error(-3, nm + ": no graph set");
         if (!mb_anchored()) return set_error(-1, nm + ": sampling needs a fixed vertex or a full pose prior (without one H is singular)");
         if (n_samples < 1 || n_samples > kSampleMax) return set_error(-1, nm + ": n_samples = " + std::to_string(n_samples) + " is outside 1 .. " + std::to_string(kSampleMax));
+        return 0;
+    }
+
+    int sample_marginals(int n_samples, uint64_t seed, double rel_tol, double* cov, int64_t cap_vertices, double* samples, int64_t samples_cap,
+                         tsgo_sample_stats* st_out) override {
+        const auto wall0 = std::chrono::steady_clock::now();
+        const std::string nm("tsgo_sample_marginals");
+        tsgo_sample_stats ss; std::memset(&ss, 0, sizeof(ss));
+        if (int rc = sample_refusals(nm, n_samples)) return rc;
         const int64_t V = pr.n_vertices;
         if (!cov) return set_error(-1, nm + ": bad argument (cov_out is NULL)");
         if (cap_vertices < V) return set_error(-1, nm + ": cap_vertices " + std::to_string(cap_vertices) + " is below n_vertices = " + std::to_string(V));
@@ -132,7 +142,7 @@
             HIP_OK(hipSetDevice(cfg.device));
             if (int rc = sample_prepare()) return rc;
             const double tol = rel_tol > 0 ? rel_tol : cfg.pcg_rel_tol;
-            if (int rc = mb_compute([&](auto nv) { return sample_run<nv>(n_samples, seed, tol, cov, samples, ss); })) return rc;
+            if (int rc = mb_compute([&](auto nv) { return sample_run<nv>(n_samples, seed, tol, cov, samples, ss, [](MbBuf&, const T*, int) {}); })) return rc;
             ss.samples = n_samples;
             ss.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
             ss.solve.ms_total = ss.ms_total;

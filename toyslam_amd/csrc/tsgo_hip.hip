@@ -1,6 +1,6 @@
 // tsgo_hip.hip — device side of the C ABI in include/tsgo.h: buffers, launches, the Gauss-Newton
 // loop with the reference's stop rules (remote/optimizer/OptimizerCpu.h:80-180), hipGraph replay of
-// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_sample_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h, tsgo_gnc_kernels.h, tsgo_dogleg_kernels.h.
+// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_sample_kernels.h, tsgo_leverage_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h, tsgo_gnc_kernels.h, tsgo_dogleg_kernels.h.
 //
 // One translation unit; the engine class is laid out over this file and engine/*.inc (each included inside the class body):
 //   this file                      members (what the solver learns grouped by lifetime: SolverMemory; the structure index and its device maps), configuration / environment (host/knobs.h), device slabs, call-scoped device scratch (CallScratch, EventPair) and upload helpers; the C ABI at the end
@@ -17,8 +17,10 @@
 //   engine/engine_marginals.inc    tsgo_marginals, tsgo_joint_marginals: batched PCG for blocks of H^-1, one column-batch driver for every reader (mb_for_batches)
 //   host/batch_plan.h              (host only, no HIP) how the readers cut their columns into batches; the gate's per-batch lists
 //   engine/engine_sample.inc       tsgo_sample_marginals: posterior samples by perturb-and-MAP and every vertex's covariance from their second moments
+//   engine/engine_leverage.inc     tsgo_edge_leverage: C_e = J_e H^-1 J_e^T and the leverage of every input edge from the same samples (the sampling driver with one more read-out:
+//                                  k_lev_acc / k_lev_acc_lm_prior, tsgo_leverage_kernels.h, a fourth visitor of tsgo_edge_walk.h)
 //   engine/engine_report.inc       tsgo_edge_report: per-edge residual records and the per-class summary
-//   tsgo_edge_walk.h               (device only) the once-per-edge walk of the reader kernels, shared by the report, GNC and dogleg g'Hg passes: every input edge is visited by ONE lane
+//   tsgo_edge_walk.h               (device only) the once-per-edge walk of the reader kernels, shared by the report, GNC, dogleg g'Hg and leverage passes: every input edge is visited by ONE lane
 //                                  (pose-pose edges at their first endpoint, padding never), and a skipped slot is left before anything but its index and map words is
 //                                  read — why those passes write per edge with plain stores.  k_chi2 / k_lin_pose (and their landmark twins) intentionally do NOT use it:
 //                                  they have no slot -> edge maps, count padding through its zero weight, and must agree with each other on chi^2 bit for bit
@@ -73,6 +75,7 @@
 #include "tsgo_gnc_kernels.h"
 #include "tsgo_init_kernels.h"
 #include "tsgo_kernels.h"
+#include "tsgo_leverage_kernels.h"
 #include "tsgo_lm_kernels.h"
 #include "tsgo_marginal_kernels.h"
 #include "tsgo_report_kernels.h"
@@ -181,6 +184,7 @@ struct IEngine {
     virtual int joint_marginals(const uint32_t* ids, int n_ids, double rel_tol, double* cov, int64_t cov_cap, int* dim_out, tsgo_marginal_stats* st) = 0;
     virtual int sample_marginals(int n_samples, uint64_t seed, double rel_tol, double* cov, int64_t cap_vertices, double* samples, int64_t samples_cap,
                                  tsgo_sample_stats* st) = 0;
+    virtual int edge_leverage(int n_samples, uint64_t seed, double rel_tol, double* rec_out, int64_t cap_edges, tsgo_leverage_stats* st) = 0;
     virtual int edge_report(double* rec_out, int64_t cap_edges, tsgo_edge_report_stats* st) = 0;
     virtual int gate_edges(int n, const uint32_t* e_type, const uint32_t* e_ids, const double* e_meas, const double* e_inf, double rel_tol, double* rec_out,
                            double* innov_out, tsgo_gate_stats* st) = 0;
@@ -584,6 +588,7 @@ template <typename T> struct Engine : IEngine {
 #include "engine/engine_gate.inc"
 #include "engine/engine_report.inc"
 #include "engine/engine_sample.inc"
+#include "engine/engine_leverage.inc"
 #include "engine/engine_init.inc"
 #include "engine/engine_edit.inc"
 #include "engine/engine_edge_robust.inc"
@@ -730,6 +735,10 @@ int tsgo_sample_marginals(tsgo_optimizer* o, int32_t n_samples, uint64_t seed, d
                           int64_t samples_cap, tsgo_sample_stats* stats) {
     if (!o) return tsgo::set_error(-1, "tsgo_sample_marginals: null handle");
     return o->eng->sample_marginals(n_samples, seed, rel_tol, cov_out, cap_vertices, samples_out, samples_cap, stats);
+}
+int tsgo_edge_leverage(tsgo_optimizer* o, int32_t n_samples, uint64_t seed, double rel_tol, double* rec_out, int64_t cap_edges, tsgo_leverage_stats* stats) {
+    if (!o) return tsgo::set_error(-1, "tsgo_edge_leverage: null handle");
+    return o->eng->edge_leverage(n_samples, seed, rel_tol, rec_out, cap_edges, stats);
 }
 int tsgo_edge_report(tsgo_optimizer* o, double* rec_out, int64_t cap_edges, tsgo_edge_report_stats* stats) {
     if (!o) return tsgo::set_error(-1, "tsgo_edge_report: null handle");

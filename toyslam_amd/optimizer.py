@@ -280,6 +280,27 @@ iters=st.iterations_run, stop=STOP[st.stop_reason], chi2=np.array(st.chi2[:n]), 
         stats["solve"] = {f: getattr(st.solve, f) for f, _t in st.solve._fields_}
         return dict(cov=cov, samples=smp, stats=stats)
 
+    def edge_leverage(self, n_samples, seed=0, rel_tol=0.0):
+        """Leverage of every edge from posterior samples (tsgo_edge_leverage), in the edge order of the graph given to set_graph:
+        dict(cov (E, 3, 3) symmetric, C = J Sigma J^T of the predicted measurement (the dof-2 classes in cov[e, :2, :2]); h (E,) =
+        tr(Omega_a C); dof (E,) the number of weighted axes; redundancy = dof - h (not clamped: sampling noise may take it just below
+        0); all, the (E, 8) records (c00, c01, c02, c11, c12, c22, h, dof_a); stats).  The samples are those of sample_marginals for the
+        same (n_samples, seed); a diagonal entry of C has relative standard error sqrt(2 / K).  rel_tol <= 0: the handle's pcg_rel_tol."""
+        K, E = int(n_samples), self.n_edges
+        arr = np.zeros((max(E, 1), 8))
+        st = _lib.tsgo_leverage_stats()
+        _lib.check(self.lib, self.lib.tsgo_edge_leverage(self.h, K, int(seed) & 0xFFFFFFFFFFFFFFFF, float(rel_tol), arr.ctypes.data, E, C.byref(st)),
+                   "tsgo_edge_leverage")
+        arr = arr[:E]
+        cov = np.zeros((E, 3, 3))
+        for k, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+            cov[:, a, b] = arr[:, k]; cov[:, b, a] = arr[:, k]
+        stats = {f: getattr(st, f) for f, _t in st._fields_ if f not in ("solve", "reserved", "edges", "h_sum", "dof_sum")}
+        for f in ("edges", "h_sum", "dof_sum"):
+            stats[f] = np.array(getattr(st, f))
+        stats["solve"] = {f: getattr(st.solve, f) for f, _t in st.solve._fields_}
+        return dict(cov=cov, h=arr[:, 6], dof=arr[:, 7], redundancy=arr[:, 7] - arr[:, 6], all=arr, stats=stats)
+
     def edge_report(self, records=True):
         """Per-edge residual report at the current estimates under the handle's robust setting (tsgo_edge_report): (rec, summary).
         rec: dict of views over one (E, 6) array in the edge order of the graph given to set_graph — e (E, 3), s, rho, w (E,) — and the
