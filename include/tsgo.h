@@ -715,6 +715,80 @@ void tsgo_default_gnc(tsgo_gnc_params* p);                /* host-only too */
 int tsgo_gnc(tsgo_optimizer* opt, const tsgo_gnc_params* params, const uint8_t* subject /* may be NULL */, int64_t n_mask,
              double* w_out /* 1 per edge, may be NULL */, int64_t cap_edges, tsgo_gnc_stats* stats /* may be NULL */);
 
+/* Max-mixture edges (Olson and Agarwal 2013; g2o's max-mixture edge types, GTSAM's mixture factors): "this measurement
+ * is one of these alternatives" — a loop closure or its null hypothesis (the same mean, a very wide covariance), landmark A or landmark B,
+ * a direct fix or a known multipath offset.  Every pass evaluates every alternative on the device, selects the likeliest of each group and
+ * switches the others off in the tables (what tsgo_edge_report, host arithmetic per group and tsgo_set_edge_information would do in three
+ * calls and two transfers), then runs the handle's own tsgo_optimize.  A local method: it finds the selection that is consistent with the
+ * estimates it starts from (from an odometry-only start every closure looks false).
+ *   Components: a group is a list of edges that are already in the graph, each with its own measurement and information (positions in
+ *   the edge arrays of the tsgo_graph the handle was given, the numbering of tsgo_edge_report): group g is member_edge[group_off[g] ..
+ *   group_off[g + 1]).  Exactly one member of a group is switched on at a time; the others are held at information 0, where an edge
+ *   contributes exactly nothing (tsgo_set_edge_information).  An edge belongs to at most one group.  Edges in no group are never read for
+ *   their weights and never written.
+ *   Base information: what the handle holds when the call starts (tsgo_get_edge_information).  s_e = sum_k base_k e_k^2 of a member at the
+ *   current estimates, under the NONE kernel and written term for term as tsgo_edge_report writes it, never depends on what the tables hold
+ *   at that moment.
+ *   Cost of member m (edge e): c_m = s_e + k_m with k_m = -(ln b_0 + ln b_1 [+ ln b_2]) - 2 log_weight_m over the axes the edge's type uses,
+ *   in that order (k_m on the host in f64, c_m on the device in f64): -2 ln of the component's weighted Gaussian likelihood without its
+ *   (2 pi) term, which is the same for every member because the members of a group must have the same number of axes.  A cost that is not
+ *   finite counts as +infinity.
+ *   Selection: the member with the smallest cost; the comparison is strict, so a tie goes to the lowest position in the group, and a group
+ *   whose costs are all +infinity selects position 0.
+ *   The loop: nothing is selected at first.  Pass r = 0, 1, ... evaluates the costs at the current estimates and selects; n_changed[r] is the
+ *   number of groups whose selection differs from the previous pass's (in pass 0: every group), cost_sum[r] the sum of the winners' costs.
+ *     no group changed (r > 0)   the call stops with TSGO_MIX_STABLE: nothing is written, the tables hold this selection already;
+ *     otherwise                  the tables receive base for each winner and 0 for each loser on the axes the type uses, and the solver is
+ *                                invalidated as tsgo_set_edge_information does (the next linearisation builds a fresh multigrid hierarchy; the
+ *                                history and the robust settings stay);
+ *     r == rounds_max            the call stops with TSGO_MIX_ROUNDS: rounds_max rounds did not settle the selection (the tables hold the
+ *                                selection of this last pass, which no inner run has followed);
+ *     otherwise                  round r ends with tsgo_optimize(inner_iterations) under the handle's own rules, odom_jacobian and robust
+ *                                settings; an inner run that ends with TSGO_STOP_SOLVER stops the call with TSGO_MIX_SOLVER, an inner error
+ *                                code (< 0) ends the call with that code at once.
+ *   So passes = rounds + 1 unless the solver failed, and a call that settles reports TSGO_MIX_STABLE whatever rounds_max is.  With
+ *   inner_iterations = 0 a round selects and scatters only; inner_iterations = 1 is Olson and Agarwal's form (a selection per
+ *   linearisation).  selected_out (the position inside its group, one per group) and cost_out (one per member, as computed: a cost that
+ *   is not finite is returned as it is) are those of the last pass.
+ *   keep_selection = 1: on return the tables hold the last selection (a later tsgo_set_graph replaces it, as after an edit).
+ *   keep_selection = 0: the base information is restored bit for bit; the estimates stay where the loop left them.
+ * Deterministic: the same call from the same state gives the same bits.  n_groups == 0 returns 0 and does nothing.  precision 64 and
+ * world == 1 only.  Errors (< 0, text in tsgo_last_error; everything is validated before anything of the handle is written, the handle is
+ * exactly as before): a NULL handle or params; no graph set; n_groups < 0; group_off or member_edge NULL with groups to read; group_off[0]
+ * != 0; a group_off that does not increase (every group has at least 1 member); a group above TSGO_MIX_MAX_MEMBERS; an edge index outside
+ * the graph; an edge listed twice, in one group or in two; members of one group whose types differ in their number of axes (types 0 and 3
+ * have 3; types 1, 2 and 4 have 2); a base information on a used axis that is not finite and > 0; a log_weight that is not finite;
+ * rounds_max outside [1, TSGO_MIX_MAX_ROUNDS]; inner_iterations < 0; keep_selection not 0 or 1; cap_groups < n_groups with selected_out
+ * given, cap_members < group_off[n_groups] with cost_out given; precision = 32; an edge-sharded handle (world > 1). */
+#define TSGO_MIX_MAX_ROUNDS 128
+#define TSGO_MIX_MAX_MEMBERS 64
+enum { TSGO_MIX_STABLE = 0, TSGO_MIX_ROUNDS = 1, TSGO_MIX_SOLVER = 2 };
+typedef struct tsgo_mixture_params {
+    int32_t rounds_max;         /* 1 .. TSGO_MIX_MAX_ROUNDS; default 32 */
+    int32_t inner_iterations;   /* tsgo_optimize's `iterations` of every round; default 5.  0: select and scatter only */
+    int32_t keep_selection;     /* 1 (default) or 0 */
+    int32_t reserved;           /* 0 */
+} tsgo_mixture_params;
+typedef struct tsgo_mixture_stats {
+    int32_t rounds, passes;                                   /* rounds run (scatter and inner run); selection passes */
+    int32_t stop_reason, reserved;                            /* TSGO_MIX_*; 0 */
+    int64_t n_changed[TSGO_MIX_MAX_ROUNDS + 1];               /* per pass: groups whose selection moved, */
+    double  cost_sum[TSGO_MIX_MAX_ROUNDS + 1];                /* ... sum of the winners' costs (workgroup partials folded in order) */
+    double  chi2_inner[TSGO_MIX_MAX_ROUNDS + 1];              /* per round: tsgo_stats.chi2_last of the inner run (0 with inner_iterations = 0), */
+    int32_t inner_iterations_run[TSGO_MIX_MAX_ROUNDS + 1];    /* ... its iterations_run */
+    int32_t inner_stop[TSGO_MIX_MAX_ROUNDS + 1];              /* ... and stop_reason (TSGO_STOP_*) */
+    int64_t groups, members, members_by_class[5];             /* n_groups; group_off[n_groups]; members per tsgo_graph.e_type */
+    int64_t pcg_iters_total;                                  /* over all inner runs */
+    double  ms_total, ms_select, ms_inner;                    /* whole call; hipEvent time of the two kernels over all passes; wall time of the inner runs */
+} tsgo_mixture_stats;
+void tsgo_default_mixture(tsgo_mixture_params* p);            /* host-only too */
+int tsgo_max_mixture(tsgo_optimizer* opt, const tsgo_mixture_params* params, int64_t n_groups, const int64_t* group_off /* n_groups + 1 */,
+                     const int64_t* member_edge /* group_off[n_groups] input edge indices */,
+                     const double* log_weight /* one per member, may be NULL: 0 */,
+                     int32_t* selected_out /* one per group, may be NULL */, int64_t cap_groups,
+                     double* cost_out /* one per member, may be NULL */, int64_t cap_members,
+                     tsgo_mixture_stats* stats /* may be NULL */);
+
 const char* tsgo_last_error(void);
 
 /* ---- host-only: wire codec (libtsgo_host.so and libtsgo_hip.so) ---------------------------------

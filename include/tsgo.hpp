@@ -368,6 +368,30 @@ public:
         }
         return w;
     }
+    // Max-mixture edges (tsgo_max_mixture) on the graph last handed to Optimize or SetGraph: `groups` lists, per measurement, the input edge
+    // indices of its alternatives; exactly one of each group is switched on (the cheapest at the current estimates), the others are held at
+    // information 0, and rounds of selection and Optimize-style inner runs follow until no group changes.  params: DefaultMixture()
+    // adjusted; log_weight: empty = 0, otherwise one value per member in the order of `groups`.  Returns the selected position of every
+    // group; the graph's positions are updated in place when `graph` is given.  Throws on an error (no graph yet, an edge outside the
+    // graph or listed twice, an empty or too long group, members of different dof, a member without information, a parameter out of
+    // range, precision 32, an edge-sharded handle).
+    static tsgo_mixture_params DefaultMixture() { tsgo_mixture_params p; tsgo_default_mixture(&p); return p; }
+    std::vector<int32_t> MaxMixture(const tsgo_mixture_params& params, const std::vector<std::vector<int64_t>>& groups,
+                                    const std::vector<double>& log_weight = std::vector<double>(), Graph* graph = nullptr, tsgo_mixture_stats* stats = nullptr) {
+        std::vector<int64_t> off(1, 0), member;
+        for (const std::vector<int64_t>& g : groups) { member.insert(member.end(), g.begin(), g.end()); off.push_back((int64_t)member.size()); }
+        if (!log_weight.empty() && log_weight.size() != member.size()) throw std::runtime_error("MaxMixture: one log_weight per member");
+        std::vector<int32_t> sel(groups.size());
+        if (tsgo_max_mixture(handle, &params, (int64_t)groups.size(), off.data(), member.empty() ? nullptr : member.data(), log_weight.empty() ? nullptr : log_weight.data(),
+                             sel.empty() ? nullptr : sel.data(), (int64_t)sel.size(), nullptr, 0, stats))
+            throw std::runtime_error(tsgo_last_error());
+        if (graph) {
+            std::vector<double> out(graph->VertexCount() * 3);
+            if (tsgo_get_vertices(handle, out.data())) throw std::runtime_error(tsgo_last_error());
+            graph->SetPositions(out);
+        }
+        return sel;
+    }
     // Hands the graph to the handle without optimising it (what InitEstimates, EdgeReport or GateEdges need before a first Optimize).
     void SetGraph(const Graph& graph) {
         const tsgo_graph g = graph.View();

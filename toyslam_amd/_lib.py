@@ -117,6 +117,24 @@ class tsgo_gnc_stats(C.Structure):
                 ("pcg_iters_total", C.c_int64), ("ms_total", C.c_double), ("ms_reweight", C.c_double), ("ms_inner", C.c_double)]
 
 
+TSGO_MIX_MAX_ROUNDS = 128
+TSGO_MIX_MAX_MEMBERS = 64
+MIX_STOP = {0: "stable", 1: "rounds", 2: "solver"}      # TSGO_MIX_*
+
+
+class tsgo_mixture_params(C.Structure):
+    _fields_ = [("rounds_max", C.c_int32), ("inner_iterations", C.c_int32), ("keep_selection", C.c_int32), ("reserved", C.c_int32)]
+
+
+class tsgo_mixture_stats(C.Structure):
+    _R = TSGO_MIX_MAX_ROUNDS + 1
+    _fields_ = [("rounds", C.c_int32), ("passes", C.c_int32), ("stop_reason", C.c_int32), ("reserved", C.c_int32),
+                ("n_changed", C.c_int64 * _R), ("cost_sum", C.c_double * _R), ("chi2_inner", C.c_double * _R),
+                ("inner_iterations_run", C.c_int32 * _R), ("inner_stop", C.c_int32 * _R), ("groups", C.c_int64), ("members", C.c_int64),
+                ("members_by_class", C.c_int64 * 5), ("pcg_iters_total", C.c_int64), ("ms_total", C.c_double), ("ms_select", C.c_double),
+                ("ms_inner", C.c_double)]
+
+
 ROBUST_KERNELS = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}      # TSGO_ROBUST_*
 ROBUST_CLASSES = ("odom", "lm", "virtual", "pose_prior", "lm_prior")            # = tsgo_graph.e_type 0 .. 4
 
@@ -165,14 +183,14 @@ class tsgo_testing_warm_out(C.Structure):
                [("err", C.c_double * 6), ("scale", C.c_double), ("bdb", C.c_double), ("rdr", C.c_double)] + [(n, C.c_void_p) for n in ("hist", "b", "x0", "r0")]
 
 
-HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_default_gnc", "tsgo_default_dogleg", "tsgo_last_error", "tsgo_wire_decode", "tsgo_wire_new", "tsgo_wire_decode_into", "tsgo_wire_view", "tsgo_wire_free",
+HOST_SYMBOLS = ["tsgo_default_config", "tsgo_default_robust", "tsgo_default_gnc", "tsgo_default_mixture", "tsgo_default_dogleg", "tsgo_last_error", "tsgo_wire_decode", "tsgo_wire_new", "tsgo_wire_decode_into", "tsgo_wire_view", "tsgo_wire_free",
                 "tsgo_wire_encode_response", "tsgo_wire_encode_request", "tsgo_synth_create", "tsgo_synth_view",
                 "tsgo_synth_truth", "tsgo_synth_free", "tsgo_layout_probe", "tsgo_amg_probe", "tsgo_amg_probe_shard", "tsgo_init_tree", "tsgo_sample_noise"]
 DEVICE_SYMBOLS = ["tsgo_device_count", "tsgo_create", "tsgo_destroy", "tsgo_set_graph", "tsgo_reset_history", "tsgo_optimize", "tsgo_get_vertices",
                   "tsgo_linearize", "tsgo_solve_step", "tsgo_comm_unique_id", "tsgo_comm_init", "tsgo_comm_selftest", "tsgo_comm_time_allreduce", "tsgo_time_kernel", "tsgo_cycle_probe", "tsgo_profile_iteration",
                   "tsgo_marginals", "tsgo_joint_marginals", "tsgo_set_robust", "tsgo_get_robust", "tsgo_edge_report", "tsgo_gate_edges", "tsgo_init_estimates",
                   "tsgo_set_edge_information", "tsgo_get_edge_information", "tsgo_gnc", "tsgo_sample_marginals", "tsgo_set_dogleg", "tsgo_get_dogleg", "tsgo_get_dogleg_trace",
-                  "tsgo_set_edge_robust", "tsgo_get_edge_robust", "tsgo_set_fixed", "tsgo_get_fixed", "tsgo_set_estimates", "tsgo_edge_leverage"]
+                  "tsgo_set_edge_robust", "tsgo_get_edge_robust", "tsgo_set_fixed", "tsgo_get_fixed", "tsgo_set_estimates", "tsgo_edge_leverage", "tsgo_max_mixture"]
 TESTING_SYMBOLS = ["tsgo_local_group_create", "tsgo_local_group_destroy", "tsgo_comm_init_local", "tsgo_testing_apply",
                    "tsgo_testing_sym_scan", "tsgo_testing_sym_product", "tsgo_testing_schur_pattern", "tsgo_testing_lane_sums", "tsgo_testing_warm_start"]      # include/tsgo_testing.h: libtsgo_hip_testing.so only
 
@@ -183,6 +201,7 @@ def _declare_host(L):
     L.tsgo_default_robust.argtypes = [C.POINTER(tsgo_robust)]; L.tsgo_default_robust.restype = None
     L.tsgo_default_gnc.argtypes = [C.POINTER(tsgo_gnc_params)]; L.tsgo_default_gnc.restype = None
     L.tsgo_default_dogleg.argtypes = [C.POINTER(tsgo_dogleg_params)]; L.tsgo_default_dogleg.restype = None
+    L.tsgo_default_mixture.argtypes = [C.POINTER(tsgo_mixture_params)]; L.tsgo_default_mixture.restype = None
     L.tsgo_last_error.restype = C.c_char_p
     L.tsgo_wire_decode.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp)]
     L.tsgo_wire_new.argtypes = []; L.tsgo_wire_new.restype = vp
@@ -239,6 +258,7 @@ def _declare_device(L):
     L.tsgo_set_edge_information.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(tsgo_edge_info_stats)]
     L.tsgo_get_edge_information.argtypes = [vp, vp, C.c_int64]
     L.tsgo_gnc.argtypes = [vp, C.POINTER(tsgo_gnc_params), vp, C.c_int64, vp, C.c_int64, C.POINTER(tsgo_gnc_stats)]
+    L.tsgo_max_mixture.argtypes = [vp, C.POINTER(tsgo_mixture_params), C.c_int64, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, C.POINTER(tsgo_mixture_stats)]
     L.tsgo_set_fixed.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(tsgo_vertex_edit_stats)]
     L.tsgo_get_fixed.argtypes = [vp, vp, C.c_int64]
     L.tsgo_set_estimates.argtypes = [vp, C.c_int64, vp, vp, C.POINTER(tsgo_vertex_edit_stats)]

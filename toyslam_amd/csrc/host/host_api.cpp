@@ -37,6 +37,11 @@ extern "C" void tsgo_default_gnc(tsgo_gnc_params* p) {
     p->mu_step = 1.4; p->rounds_max = 64; p->inner_iterations = 10; p->keep_weights = 1; p->reserved = 0;
 }
 
+extern "C" void tsgo_default_mixture(tsgo_mixture_params* p) {
+    if (!p) return;
+    p->rounds_max = 32; p->inner_iterations = 5; p->keep_selection = 1; p->reserved = 0;
+}
+
 extern "C" void tsgo_sample_noise(uint64_t seed, uint32_t tag, uint32_t index, uint32_t sample, uint32_t words_out[4], double normals_out[4]) {
     const tsgo::Philox4 p = tsgo::philox4x32_10(index, tag, sample, 0u, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32));
     if (words_out) for (int k = 0; k < 4; ++k) words_out[k] = p.r[k];

@@ -1,5 +1,5 @@
 // tsgo_edge_walk.h — which lane evaluates which input edge: the ONE walk of the reader kernels that visit every input edge exactly once
-// (the edge report, tsgo_report_kernels.h; the GNC reweighting pass, tsgo_gnc_kernels.h; the dogleg loop's g'Hg pass, tsgo_dogleg_kernels.h; the leverage read-out, tsgo_leverage_kernels.h).  Device only.  Who does NOT use it and why:
+// (the edge report, tsgo_report_kernels.h; the GNC reweighting pass, tsgo_gnc_kernels.h; the max-mixture cost pass, tsgo_mixture_kernels.h; the dogleg loop's g'Hg pass, tsgo_dogleg_kernels.h; the leverage read-out, tsgo_leverage_kernels.h).  Device only.  Who does NOT use it and why:
 // the file table of tsgo_hip.hip.
 //
 // walk_edges_once, classes 0 .. 3, one lane of a by_pose slice (walk_of), in this order:

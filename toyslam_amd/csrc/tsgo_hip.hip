@@ -1,6 +1,6 @@
 // tsgo_hip.hip — device side of the C ABI in include/tsgo.h: buffers, launches, the Gauss-Newton
 // loop with the reference's stop rules (remote/optimizer/OptimizerCpu.h:80-180), hipGraph replay of
-// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_sample_kernels.h, tsgo_leverage_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h, tsgo_gnc_kernels.h, tsgo_dogleg_kernels.h.
+// the PCG iteration, RCCL all-reduces for edge-sharded runs.  Kernels: tsgo_kernels.h, tsgo_amg_kernels.h, tsgo_sym_kernels.h, tsgo_marginal_kernels.h, tsgo_sample_kernels.h, tsgo_leverage_kernels.h, tsgo_init_kernels.h, tsgo_edit_kernels.h, tsgo_gnc_kernels.h, tsgo_mixture_kernels.h, tsgo_dogleg_kernels.h.
 //
 // One translation unit; the engine class is laid out over this file and engine/*.inc (each included inside the class body):
 //   this file                      members (what the solver learns grouped by lifetime: SolverMemory; the structure index and its device maps), configuration / environment (host/knobs.h), device slabs, call-scoped device scratch (CallScratch, EventPair) and upload helpers; the C ABI at the end
@@ -20,7 +20,7 @@
 //   engine/engine_leverage.inc     tsgo_edge_leverage: C_e = J_e H^-1 J_e^T and the leverage of every input edge from the same samples (the sampling driver with one more read-out:
 //                                  k_lev_acc / k_lev_acc_lm_prior, tsgo_leverage_kernels.h, a fourth visitor of tsgo_edge_walk.h)
 //   engine/engine_report.inc       tsgo_edge_report: per-edge residual records and the per-class summary
-//   tsgo_edge_walk.h               (device only) the once-per-edge walk of the reader kernels, shared by the report, GNC, dogleg g'Hg and leverage passes: every input edge is visited by ONE lane
+//   tsgo_edge_walk.h               (device only) the once-per-edge walk of the reader kernels, shared by the report, GNC, max-mixture cost, dogleg g'Hg and leverage passes: every input edge is visited by ONE lane
 //                                  (pose-pose edges at their first endpoint, padding never), and a skipped slot is left before anything but its index and map words is
 //                                  read — why those passes write per edge with plain stores.  k_chi2 / k_lin_pose (and their landmark twins) intentionally do NOT use it:
 //                                  they have no slot -> edge maps, count padding through its zero weight, and must agree with each other on chi^2 bit for bit
@@ -30,6 +30,8 @@
 //                                  tsgo_set_fixed / tsgo_get_fixed / tsgo_set_estimates: the gauge terms and the estimates of listed vertices, in place
 //   engine/engine_edge_robust.inc  tsgo_set_edge_robust / tsgo_get_edge_robust: a palette of robust kernels and one byte per input edge; the per-slot byte arrays of the RK = 2 kernels
 //   engine/engine_gnc.inc          tsgo_gnc: graduated non-convexity (truncated least squares), one reweighting pass over the tables per round
+//   engine/engine_mixture.inc      tsgo_max_mixture: groups of alternative edges, one switched on; per pass the cost of every member (k_mix_cost, a fifth visitor of
+//                                  tsgo_edge_walk.h) and a thread per group that selects and scatters (k_mix_select); kernels: tsgo_mixture_kernels.h (f64 only)
 //   engine/engine_dogleg.inc       rules = 3, Powell's dogleg trust-region loop: one linearisation and one solve per ACCEPTED step, trials from the snapshot; tsgo_set_dogleg,
 //                                  tsgo_get_dogleg_trace.  Kernels: tsgo_dogleg_kernels.h (f64 only) — the gradient as dense vectors, g'Hg by the once-per-edge walk
 //                                  (a third visitor of tsgo_edge_walk.h), the step from the snapshot
@@ -78,6 +80,7 @@
 #include "tsgo_leverage_kernels.h"
 #include "tsgo_lm_kernels.h"
 #include "tsgo_marginal_kernels.h"
+#include "tsgo_mixture_kernels.h"
 #include "tsgo_report_kernels.h"
 #include "tsgo_sample_kernels.h"
 #include "tsgo_sym_kernels.h"
@@ -197,6 +200,8 @@ struct IEngine {
     virtual int set_edge_robust(int32_t n_entries, const tsgo_edge_robust_entry* entries, const uint8_t* of_edge, int64_t n_mask, tsgo_edge_robust_stats* st) = 0;
     virtual int get_edge_robust(int32_t* n_out, tsgo_edge_robust_entry* entries_out, uint8_t* of_edge_out, int64_t cap_edges) = 0;
     virtual int gnc(const tsgo_gnc_params& p, const uint8_t* subject, int64_t n_mask, double* w_out, int64_t cap_edges, tsgo_gnc_stats* st) = 0;
+    virtual int max_mixture(const tsgo_mixture_params& p, int64_t n_groups, const int64_t* group_off, const int64_t* member_edge, const double* log_weight,
+                            int32_t* selected_out, int64_t cap_groups, double* cost_out, int64_t cap_members, tsgo_mixture_stats* st) = 0;
 #ifdef TSGO_TESTING
     virtual int testing_apply(int which, const double* in, double* out, int n_cols) = 0;
     virtual int testing_warm_start(int n_plant, const double* plant, int fused, tsgo_testing_warm_out* out) = 0;
@@ -593,6 +598,7 @@ template <typename T> struct Engine : IEngine {
 #include "engine/engine_edit.inc"
 #include "engine/engine_edge_robust.inc"
 #include "engine/engine_gnc.inc"
+#include "engine/engine_mixture.inc"
 #include "engine/engine_dogleg.inc"
 #ifdef TSGO_TESTING
 #include "engine/engine_testing.inc"
@@ -776,6 +782,11 @@ int tsgo_set_estimates(tsgo_optimizer* o, int64_t n, const uint32_t* ids, const 
 int tsgo_gnc(tsgo_optimizer* o, const tsgo_gnc_params* params, const uint8_t* subject, int64_t n_mask, double* w_out, int64_t cap_edges, tsgo_gnc_stats* stats) {
     if (!o || !params) return tsgo::set_error(-1, "tsgo_gnc: null handle or params");
     return o->eng->gnc(*params, subject, n_mask, w_out, cap_edges, stats);
+}
+int tsgo_max_mixture(tsgo_optimizer* o, const tsgo_mixture_params* params, int64_t n_groups, const int64_t* group_off, const int64_t* member_edge, const double* log_weight,
+                     int32_t* selected_out, int64_t cap_groups, double* cost_out, int64_t cap_members, tsgo_mixture_stats* stats) {
+    if (!o || !params) return tsgo::set_error(-1, "tsgo_max_mixture: null handle or params");
+    return o->eng->max_mixture(*params, n_groups, group_off, member_edge, log_weight, selected_out, cap_groups, cost_out, cap_members, stats);
 }
 void tsgo_reset_history(tsgo_optimizer* o) {
     if (o && o->eng) o->eng->reset_history();

@@ -282,3 +282,21 @@ class GraphArrays:
                 v.position = np.array([[c, -s, p[0]], [s, c, p[1]], [0, 0, 1.0]])
             else:
                 v.position = np.array([p[0], p[1]])
+
+
+def with_null_twins(g, edges, kappa):
+    """The closure-or-nothing case of max-mixture edges (tsgo_max_mixture, HipOptimizer.max_mixture): g with a NULL TWIN appended for each
+    listed edge — the same type, ids and measurement, its information times kappa (0 < kappa << 1: the same mean, a very wide covariance)
+    — and the groups [[edge, twin], ...] in list order.  Position 0 of a group is the edge itself, position 1 its null hypothesis.
+    Returns (GraphArrays, groups)."""
+    edges = np.asarray(edges, np.int64).reshape(-1)
+    if not (np.isfinite(kappa) and kappa > 0):
+        raise ValueError("with_null_twins: kappa = %r must be finite and > 0" % (kappa,))
+    if len(edges) and (edges.min() < 0 or edges.max() >= g.n_edges):
+        raise ValueError("with_null_twins: an edge index is outside [0, %d)" % g.n_edges)
+    if len(np.unique(edges)) != len(edges):
+        raise ValueError("with_null_twins: an edge is listed twice")
+    out = GraphArrays(g.v_id.copy(), g.v_type.copy(), g.v_pos.copy(), np.concatenate([g.e_type, g.e_type[edges]]),
+                      np.concatenate([g.e_ids, g.e_ids[edges]]), np.concatenate([g.e_meas, g.e_meas[edges]]),
+                      np.concatenate([g.e_inf, g.e_inf[edges] * float(kappa)]), g.fixed.copy())
+    return out, [[int(e), g.n_edges + k] for k, e in enumerate(edges)]

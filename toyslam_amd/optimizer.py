@@ -481,6 +481,48 @@ iters=st.iterations_run, stop=STOP[st.stop_reason], chi2=np.array(st.chi2[:n]), 
                     subject_by_class={c: st.subject_by_class[k] for k, c in enumerate(_lib.ROBUST_CLASSES)}, cg_total=st.pcg_iters_total,
                     ms_total=st.ms_total, ms_reweight=st.ms_reweight, ms_inner=st.ms_inner)
 
+    def max_mixture(self, groups, log_weight=None, rounds_max=None, inner_iterations=None, keep_selection=True):
+        """Max-mixture edges (tsgo_max_mixture): `groups` is a list of lists of input edge indices, each list the alternatives of one
+        measurement (graph.with_null_twins builds the closure-or-nothing case).  Per pass the device evaluates every member's cost
+        s - sum ln(information) - 2 log_weight at the current estimates, switches the cheapest member of each group on and the others
+        off (information 0), then runs optimize(inner_iterations) under the handle's own rules and robust settings; the loop stops when
+        no group changes.  log_weight: shaped like `groups`, one entry per member; None = 0 everywhere.
+        keep_selection=False restores the information the handle held before the call, bit for bit.  Returns a dict: rounds, passes,
+        stop ("stable", "rounds", "solver"), selected (n_groups,) positions inside the groups, selected_edge (n_groups,) the edges they
+        name, cost (one array per group), the per-pass traces n_changed and cost_sum, the per-round traces chi2_inner, inner_iters and
+        inner_stop, members_by_class, cg_total, ms_total, ms_select, ms_inner."""
+        groups = [np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]
+        off = np.zeros(len(groups) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(g) for g in groups])
+        member = np.ascontiguousarray(np.concatenate(groups)) if groups else np.zeros(0, np.int64)
+        lw = None
+        if log_weight is not None:
+            flat = [np.asarray(w, dtype=np.float64).reshape(-1) for w in log_weight]
+            if [len(w) for w in flat] != [len(g) for g in groups]:
+                raise ValueError("max_mixture: log_weight must be shaped like groups (one list per group, one entry per member)")
+            lw = np.ascontiguousarray(np.concatenate(flat)) if flat else np.zeros(0)
+        p = _lib.tsgo_mixture_params()
+        self.lib.tsgo_default_mixture(C.byref(p))
+        if rounds_max is not None:
+            p.rounds_max = int(rounds_max)
+        if inner_iterations is not None:
+            p.inner_iterations = int(inner_iterations)
+        p.keep_selection = 1 if keep_selection else 0
+        sel = np.zeros(len(groups), dtype=np.int32)
+        cost = np.zeros(len(member))
+        st = _lib.tsgo_mixture_stats()
+        _lib.check(self.lib, self.lib.tsgo_max_mixture(self.h, C.byref(p), len(groups), off.ctypes.data, member.ctypes.data if len(member) else None,
+                                                       None if lw is None else lw.ctypes.data, sel.ctypes.data if len(sel) else None, len(sel),
+                                                       cost.ctypes.data if len(cost) else None, len(cost), C.byref(st)), "tsgo_max_mixture")
+        n, k = st.rounds, st.passes
+        return dict(rounds=n, passes=k, stop=_lib.MIX_STOP[st.stop_reason], selected=sel,
+                    selected_edge=np.array([g[s] for g, s in zip(groups, sel)], dtype=np.int64), cost=[cost[a:b] for a, b in zip(off[:-1], off[1:])],
+                    n_changed=np.array(st.n_changed[:k], dtype=np.int64), cost_sum=np.array(st.cost_sum[:k]),
+                    chi2_inner=np.array(st.chi2_inner[:n]), inner_iters=np.array(st.inner_iterations_run[:n], dtype=np.int64),
+                    inner_stop=[STOP[i] for i in st.inner_stop[:n]],
+                    members_by_class={c: st.members_by_class[i] for i, c in enumerate(_lib.ROBUST_CLASSES)}, cg_total=st.pcg_iters_total,
+                    ms_total=st.ms_total, ms_select=st.ms_select, ms_inner=st.ms_inner)
+
     def time_kernel(self, which, reps=50):
         us = C.c_double(); nbytes = C.c_double()
         _lib.check(self.lib, self.lib.tsgo_time_kernel(self.h, which, reps, C.byref(us), C.byref(nbytes)),
